@@ -14,13 +14,21 @@ A "step" is one pass of the hot path over the whole batch through the C-ABI with
          ONE RCCL all-gather reassembles f_star, a device gather un-permutes it to patch order; the result is checked
          against the rank's own slots.  Weak scaling (8192 patches per GPU); the gather of step k overlaps the kernel of k+1.
 
-Besides the headline the same JSON line carries "secondary": driver-timed records of the other BASELINE configurations,
-each with its own config.workload, roofline and (N = 1) cpu_baseline:
+A plain run measures the headline only: set-up, `--warmup` untimed steps, `--steps` timed steps, one JSON line.
+With --full the same line also carries (N = 1) the host-pointer entry and the CPU baseline of the headline, and
+"secondary": driver-timed records of the other BASELINE configurations, each with its own config.workload, roofline
+and (N = 1) cpu_baseline:
   N = 1: C3-per-GPU (8192 x 512 dense), C4 (sparse online, 32768 x 256 in 4 chunks, capacity 200: the basis-filling
          kernel and the reference's default hyper-parameters), C5 (probit IRLS, 4096 x 1024).
   N > 1: C3 (N x 8192 patches x 512 points -- 65536 at N = 8, BASELINE configs[2]) through the same sharded path.
 
-    python bench.py                       # N = 1
+--dump-outputs DIR writes what the last timed step computed, as float64 .npy files: f_star.npy (patches, 1, m) and, at
+N = 1, status.npy (patches,); at N > 1 f_star is the gathered result in patch order (rank 0 writes it).  Beyond 64 MB
+in all a fixed, seeded sample of the patches is written instead, with their indices in patch_index.npy.  The inputs
+are seeded: the same arguments give the same inputs on every run.
+
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]       # N = 1, headline only
+    python bench.py --full                                                    # N = 1, every record
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -88,6 +96,27 @@ def _kstats(ms):
     return {"median": float(np.median(a)), "mean": float(np.mean(a)), "min": float(np.min(a)), "max": float(np.max(a)), "steps": int(a.size)}
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this many bytes in all
+
+
+def dump_rows(P, row_bytes, seed=0):
+    """The patches --dump-outputs writes: None (all of them) when they fit in DUMP_BYTES, else a fixed, seeded sample in
+    patch order, sized so that the sampled rows and their float64 indices fit."""
+    if P * row_bytes <= DUMP_BYTES:
+        return None
+    k = DUMP_BYTES // (row_bytes + 8)
+    return np.sort(np.random.default_rng(seed).choice(P, k, replace=False))
+
+
+def write_outputs(d, arrays, rows):
+    """arrays: name -> host array of the timed path's last step, already restricted to `rows` (dump_rows); float64 .npy each"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(d, "patch_index.npy"), rows.astype(np.float64))
+
+
 def _oracle():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as O
@@ -143,8 +172,9 @@ def cpu_baseline_dense(off, x0, x1, y, f_gpu, budget_s):
 
 # ------------------------------------------------------------------------------------------------ dense (C2 headline, C3)
 
-def bench_dense(env, P, n, steps, warmup, seed=2):
-    """One GPU's (or, N > 1, the sharded job's) dense fit + predict.  Returns a dict of measurements; `P` is patches PER GPU."""
+def bench_dense(env, P, n, steps, warmup, seed=2, want_outputs=False):
+    """One GPU's (or, N > 1, the sharded job's) dense fit + predict.  Returns a dict of measurements; `P` is patches PER GPU.
+    want_outputs: also the last timed step's results for --dump-outputs ("outputs", "rows": see dump_rows)."""
     import torch
     import torch.distributed as dist
     from gp_compressor_amd import capi, dist as gdist, synth
@@ -225,6 +255,18 @@ def bench_dense(env, P, n, steps, warmup, seed=2):
         okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
         ok = bool(okt.item())
+    outputs = rows = None
+    if want_outputs:
+        if use_dist:
+            fg = gathers[last].out                               # (Pg, 1, M) on the device, patch order
+            rows = dump_rows(Pg, M * 8)
+            if rows is not None:
+                fg = fg[torch.from_numpy(rows).to(dev)]
+            outputs = {"f_star": fg.cpu().numpy()}
+        else:
+            rows = dump_rows(S, M * 8 + 8)
+            sel = slice(None) if rows is None else rows
+            outputs = {"f_star": f_host[sel], "status": st[sel]}
     kernel = ctx.last_dense_kernel()
     flops = algorithmic_flops(n, M) * P
     achieved = flops / (kern_ms * 1e-3) / 1e12
@@ -235,7 +277,8 @@ def bench_dense(env, P, n, steps, warmup, seed=2):
                 g_.close()
     del d_off, d_x0, d_x1, d_y, f_bufs, gathers
     return {"value": world * P * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps, "kern_ms": kern_ms, "kern_stats": kt, "ok": ok,
-            "kernel": kernel, "achieved": achieved, "exchange": exchange, "host": (off, x0, x1, y, f_host) if not use_dist else None}
+            "kernel": kernel, "achieved": achieved, "exchange": exchange, "host": (off, x0, x1, y, f_host) if not use_dist else None,
+            "outputs": outputs, "rows": rows}
 
 
 def dense_record(name, r, P, n, world, steps, warmup):
@@ -704,10 +747,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--patches", type=int, default=8192, help="patches per GPU (C2: 8192)")
     ap.add_argument("--points", type=int, default=256, help="points per patch (C2: 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: host-pointer entry, CPU baselines and the secondary records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no host-pointer entry and no CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary records")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's results to DIR/<name>.npy (float64)")
     ap.add_argument("--only", default="", help="profiling: run just one workload -- c3 | c4fill | c4defaults | c4defaults3 | c4fills | c4defaultss (with sigma) | c4fill100 (capacity 100) | c5 | c2var -- and print its record")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the headline's outputs; --only runs another workload")
 
     # stdout carries ONE JSON line: whatever else writes to fd 1 while the bench runs (RCCL prints a version banner there when a
     # communicator is created) is sent to stderr, and fd 1 comes back for the line itself
@@ -749,7 +799,7 @@ def main():
         torch.cuda.set_stream(torch.cuda.Stream(device=dev))
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)   # kernels and events share torch's current stream
     env = {"ctx": ctx, "dev": dev, "world": world, "rank": rank, "use_dist": use_dist}
-    cpu = world == 1 and not use_dist and not args.no_cpu_baseline
+    cpu = args.full and world == 1 and not use_dist and not args.no_cpu_baseline
     sec_steps = max(1, min(args.steps, 5))
 
     if args.only:
@@ -780,8 +830,11 @@ def main():
 
     P, n = args.patches, args.points
     _log(f"headline: dense {P} x {n}, world {world}, use_dist {use_dist}")
-    r = bench_dense(env, P, n, args.steps, args.warmup)
+    r = bench_dense(env, P, n, args.steps, args.warmup, want_outputs=bool(args.dump_outputs))
     _log(f"headline done: {r['value']:.0f} patches/s, exchange: {r.get('exchange')}")
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, r["outputs"], r["rows"])
+    r["outputs"] = None
     name = "C2 room scan" if (P, n) == (8192, 256) else "room scan (non-default size)"
     out = dense_record(name, r, P, n, world, args.steps, args.warmup)
     if cpu:
@@ -827,7 +880,7 @@ def main():
     r["host"] = None
 
     secondary = []
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # C3: BASELINE configs[2] -- 8192 patches x 512 points per GPU (65536 at N = 8), same (sharded, N > 1) path
         r3 = bench_dense(env, 8192, 512, sec_steps, 1, seed=3)
         rec3 = dense_record("C3 outdoor scan" + (" (one GPU's share)" if world == 1 else ""), r3, 8192, 512, world, sec_steps, 1)

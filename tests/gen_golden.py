@@ -5,6 +5,8 @@
                     (/root/reference/src/gaussian_noise.cpp, probit_noise.cpp compiled by oracle/Makefile into
                     oracle/_ref/libref_noise.so) on a grid of (s20, y, x, sigma_x); values stored as C99 hex
                     floats so that the comparison is bit-exact.  Needs /root/reference (this container only).
+  noise_ref_random.npz  the same objects at 2000 seeded random arguments (noise_random_args): `args` (s20, y, x,
+                    sigma_x) and `want` (gaussian_dx_ln, gaussian_dx2_ln, probit_dx_ln, probit_dx2_ln), float64 rows.
   dense_*.npz       dense GP (gaussian_process) inputs/outputs from the independent NumPy/LAPACK restatement
                     tests/np_restatement.py (NOT from the C oracle), incl. the reference's double noise (F5).
   sparse_*.npz      sparse online GP (sparse_gp / sparse_gp_field) sequences from the NumPy restatement.
@@ -55,6 +57,33 @@ def gen_noise():
         json.dump({"source": "reference objects gaussian_noise.cpp/probit_noise.cpp compiled with g++ -O3 (oracle/Makefile ref)",
                    "rows": rows}, f, indent=0)
     print("noise_ref.json:", len(rows), "rows")
+
+
+NOISE_FNS = ("gaussian_dx_ln", "gaussian_dx2_ln", "probit_dx_ln", "probit_dx2_ln")
+
+
+def noise_random_args(n=2000, seed=0):
+    """(n, 4) float64 rows (s20, y, x, sigma_x): labels +-1 or a normal target, half and half"""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for _ in range(n):
+        s20, sx = rng.uniform(1e-4, 10), rng.uniform(0, 5)
+        y = rng.choice([-1.0, 1.0]) if rng.random() < 0.5 else rng.normal()
+        x = rng.normal()
+        rows.append((s20, y, x, sx))
+    return np.array(rows, dtype=np.float64)
+
+
+def gen_noise_random():
+    oracle_lib.build()
+    ref = oracle_lib.ref_noise()
+    if ref is None:
+        print("oracle/_ref/libref_noise.so absent (reference tree not found): keeping the committed noise_ref_random.npz")
+        return
+    args = noise_random_args()
+    want = np.array([[getattr(ref, "ref_" + fn)(*a) for fn in NOISE_FNS] for a in args.tolist()], dtype=np.float64)
+    np.savez_compressed(os.path.join(GOLD, "noise_ref_random.npz"), args=args, want=want)
+    print("noise_ref_random.npz:", len(args), "rows")
 
 
 def gen_dense():
@@ -124,5 +153,6 @@ def gen_sparse():
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     gen_noise()
+    gen_noise_random()
     gen_dense()
     gen_sparse()

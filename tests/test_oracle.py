@@ -45,18 +45,20 @@ def test_noise_matches_reference_golden_bit_exact(oracle):
 
 
 def test_noise_matches_live_reference_objects(oracle):
+    """2000 seeded random arguments: the reference objects' answers stored in golden/noise_ref_random.npz (tests/gen_golden.py),
+    and the live objects as well when oracle/_ref is built."""
+    from gen_golden import NOISE_FNS, noise_random_args
+    g = np.load(os.path.join(GOLD, "noise_ref_random.npz"))
+    args, want = g["args"], g["want"]
+    assert np.array_equal(args, noise_random_args())
     ref = oracle.ref_noise()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine); golden test covers it")
     L = oracle.lib()
-    rng = np.random.default_rng(0)
-    for _ in range(2000):
-        s20, sx = rng.uniform(1e-4, 10), rng.uniform(0, 5)
-        y = rng.choice([-1.0, 1.0]) if rng.random() < 0.5 else rng.normal()
-        x = rng.normal()
-        for o, r_ in ((L.orc_gaussian_dx_ln, ref.ref_gaussian_dx_ln), (L.orc_gaussian_dx2_ln, ref.ref_gaussian_dx2_ln),
-                      (L.orc_probit_dx_ln, ref.ref_probit_dx_ln), (L.orc_probit_dx2_ln, ref.ref_probit_dx2_ln)):
-            assert o(s20, y, x, sx).hex() == r_(s20, y, x, sx).hex()
+    for a, w in zip(args.tolist(), want.tolist()):
+        for fn, w_ in zip(NOISE_FNS, w):
+            got = getattr(L, "orc_" + fn)(*a)
+            assert got.hex() == w_.hex(), (fn, a, got, w_)
+            if ref is not None:
+                assert got.hex() == getattr(ref, "ref_" + fn)(*a).hex(), (fn, a)
 
 
 def test_gaussian3d_matches_scalar(oracle):

@@ -32,12 +32,12 @@ if [ "${RUN_STAMP:-0}" = "1" ]; then
   fi
 fi
 if [ "${RUN_BENCH:-1}" = "1" ]; then
-  step 600 $OUT/bench_$TAG.log python bench.py --steps ${BENCH_STEPS:-10} --warmup 2
+  step 600 $OUT/bench_$TAG.log python bench.py --full --steps ${BENCH_STEPS:-10} --warmup 2
   tail -2 $OUT/bench_$TAG.log
 fi
 if [ "${RUN_PROF:-1}" = "1" ]; then
   rm -rf $OUT/prof_$TAG
-  step 600 $OUT/rocprof_$TAG.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline
+  step 600 $OUT/rocprof_$TAG.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline
   find $OUT/prof_$TAG -name "*kernel_stats.csv" | head -1 | xargs -r head -20
 fi
 echo "session done" | tee -a $OUT/session_$TAG.log

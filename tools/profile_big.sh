@@ -7,7 +7,7 @@ OUT=gpurun_out/prof_big
 rm -rf $OUT; mkdir -p $OUT
 for n in 512 1024; do
   P=$((2097152 / n / (n / 512)))
-  B="python3 bench.py --points $n --patches $P --steps 3 --warmup 1 --no-cpu-baseline"
+  B="python3 bench.py --full --points $n --patches $P --steps 3 --warmup 1 --no-cpu-baseline"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats$n -- $B > $OUT/bench_$n.log 2>&1
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch$n -- $B > /dev/null 2>&1
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write$n -- $B > /dev/null 2>&1

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=${1:-r01}
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
-BENCH="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+BENCH="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
 run() { echo "=== $*" | tee -a $OUT/session.log; timeout -k 10 400 "$@" >> $OUT/session.log 2>&1; rc=$?; echo "rc=$rc" | tee -a $OUT/session.log; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi; }
 run rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH
 run rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $BENCH

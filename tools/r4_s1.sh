@@ -9,7 +9,7 @@ step() { local secs=$1 log=$2; shift 2; echo "=== $* (limit ${secs}s) $(date +%T
          if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT: stopping" | tee -a $O/session1.log; exit 1; fi; return $rc; }
 step 900 $O/pytest1.log python -m pytest tests -q -m gpu
 tail -15 $O/pytest1.log
-step 600 $O/bench1.err bash -c "python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench1.json"
+step 600 $O/bench1.err bash -c "python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench1.json"
 python - <<PY
 import json
 r=json.load(open("$O/bench1.json"))

@@ -2,7 +2,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 O=gpurun_out/r4; mkdir -p $O
-GPC_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 timeout -k 10 600 python bench.py --steps 5 --warmup 2 > $O/bench_dist1.json 2> $O/bench_dist1.err; echo "dist rc=$?"; tail -3 $O/bench_dist1.err
+GPC_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 > $O/bench_dist1.json 2> $O/bench_dist1.err; echo "dist rc=$?"; tail -3 $O/bench_dist1.err
 python - <<PY
 import json
 r=json.load(open("$O/bench_dist1.json"))

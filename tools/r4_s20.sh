@@ -3,7 +3,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 O=gpurun_out/r4; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -q -m gpu > $O/pytest20.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest20.log
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err; echo "bench rc=$?"
 python - <<PY
 import json
 r=json.load(open("$O/bench20.json"))

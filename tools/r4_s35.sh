@@ -8,7 +8,7 @@ T=tests/test_dense_gpu.py::test_host_pointer_two_stream_mode_with_a_chunk_of_sma
 GPC_LIB_PATH=$PWD/gp_compressor_amd/libgpc_hip_oldapi.so timeout -k 10 300 python -m pytest $T -q -m gpu > $O/pytest35_old.log 2>&1; echo "old api rc=$? (1 expected)"; tail -5 $O/pytest35_old.log | cut -c1-200
 timeout -k 10 300 python -m pytest $T -q -m gpu > $O/pytest35_new.log 2>&1; echo "new api rc=$?"; tail -3 $O/pytest35_new.log
 timeout -k 10 600 python -m pytest tests/test_dense_gpu.py tests/test_sparse_gpu.py -q -m gpu > $O/pytest35.log 2>&1; echo "dense+sparse rc=$?"; tail -3 $O/pytest35.log
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench35.json 2> $O/bench35.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench35.json 2> $O/bench35.err; echo "bench rc=$?"
 python - <<PY
 import json
 r=json.load(open("$O/bench35.json"))

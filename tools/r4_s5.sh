@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 O=gpurun_out/r4; mkdir -p $O
 bash tools/profile_r04.sh > $O/prof_all.log 2>&1; tail -4 $O/prof_all.log
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench5.json 2> $O/bench5.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench5.json 2> $O/bench5.err; echo "bench rc=$?"
 python - <<PY
 import json
 r=json.load(open("$O/bench5.json"))

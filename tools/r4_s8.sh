@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 O=gpurun_out/r4; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -q -m gpu > $O/pytest8.log 2>&1; echo "pytest rc=$?"; tail -6 $O/pytest8.log
 bash tools/profile_r04.sh "c2 c4defaults c4defaultss c4defaults3 c4fills" > $O/prof8.log 2>&1; tail -3 $O/prof8.log
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench8.json 2> $O/bench8.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench8.json 2> $O/bench8.err; echo "bench rc=$?"
 python - <<PY
 import json
 r=json.load(open("$O/bench8.json"))
