@@ -47,6 +47,10 @@ struct SpState {
 #define SP_BMAX 24   // resident block of the small-basis add kernel (see sparse_add_kernel)
 #endif
 #define SP_BMID 48   // ... and of its second instance, which takes the patches that have outgrown SP_BMAX (round 4)
+// kernel_function(X, X) = p(0) exp(-0.5/p(1) |X - X|^2) (src/sparse_gp.hpp:98, :316): p(0) for a finite X (X - X = +0, exp(-0) is exactly 1,
+// so finite data keeps its bits) and NaN when a coordinate is NaN or +-inf (X - X = NaN): no select, three operations.
+__device__ static __forceinline__ double sp_kstar(double sf, double x0, double x1) { return sf + ((x0 - x0) + (x1 - x1)); }
+
 // ---- block-wide helpers (all SP_NTH threads call) -------------------------------------------------------
 
 // (every control used here -- quad permutes, row mirrors, row rotate -- has a source lane for every lane, so the destination's previous
@@ -106,9 +110,13 @@ __device__ static inline void sp_block_sum4(double (&v)[4], double* scratch /*4*
     for (int q = 0; q < N; ++q) v[q] = scratch[q] + scratch[4 + q] + scratch[8 + q] + scratch[12 + q];
 }
 
-// argmin with first-index tie break (the reference scans i ascending with a strict '<').  The order is total (value, then index, NaN
-// last), so the winner does not depend on the shape of the reduction; rows by DPP, the four row winners through SGPRs.
-#define SP_TAKE(ov, oi, val, idx) ((ov) < (val) || ((ov) == (val) && (oi) < (idx)) || ((val) != (val) && (ov) == (ov)))
+// arg-min as the reference scans (src/sparse_gp.hpp:210-217, :229-235: i ascending, `if (i == 0 || score < minscore)`): a NaN score at
+// index 0 sticks (every comparison with it is false), a NaN score at any other index is skipped, ties go to the first index.  As a total
+// order -- a NaN at index 0 first, then by value with NaN last, then by index -- the winner does not depend on the shape of the reduction;
+// rows by DPP, the four row winners through SGPRs.  The scans that feed it use the same order (SP_TAKE(score, i, best, loc)).
+#define SP_NAN0(v, i) ((i) == 0 && (v) != (v))
+#define SP_TAKE(ov, oi, val, idx) \
+    (SP_NAN0(ov, oi) || (!SP_NAN0(val, idx) && ((ov) < (val) || ((ov) == (val) && (oi) < (idx)) || ((val) != (val) && (ov) == (ov)))))
 __device__ static inline void sp_block_argmin(double& val, int& idx, double* sval, int* sidx)
 {
 #define SP_ARGMIN_STEP(CTRL)                                                                                          \
@@ -530,11 +538,11 @@ __device__ static int sp_full_update_delete(const SpState& S, int b, double rr, 
         const double c0 = (i < b) ? S.C[sp_at<PK>(i, i, ldm)] : 0.0, q0 = (i < b) ? S.Q[sp_at<PK>(i, i, ldm)] : 0.0;
         const double cd = c0 + (rr * sv[i]) * sv[i], qd = q0 + (ig * eh[i]) * eh[i];
         const double score = a2 / (qd + cd);
-        if (!have || score < best) { best = score; loc = i; have = true; }
+        if (!have || SP_TAKE(score, i, best, loc)) { best = score; loc = i; have = true; }
     }
     if (!have) best = __builtin_inf();
     sp_block_argmin(best, loc, sval, sidx);
-    if (loc < 0 || loc > b) loc = 0;          // all-NaN scores: the reference keeps minloc = 0
+    if (loc < 0 || loc > b) loc = 0;
     // columns loc and last of the updated matrices (delete_bv :259-278)
     for (int i = tid; i <= b; i += SP_NTH) {
         const bool old = (i < b) && (loc < b);
@@ -772,7 +780,7 @@ __global__ __launch_bounds__(SMALL ? 64 : SP_THREADS, SMALL ? 4 : 2) void sparse
                 for (int c = 0; c < ny; ++c) nyv[c] = A.y[(size_t)c * A.n_total + o + r_nxt];
                 if (it + 2 < n) r_nxt2 = A.perm ? A.perm[o + it + 2] : it + 2;
             }
-            const double kstar = sf;   // kernel_function(X, X) = p(0)*exp(0)  (:98)
+            const double kstar = sp_kstar(sf, px0, px1);   // kernel_function(X, X)  (:98)
 
             const bool from_prev = have_next;
             have_next = false;
@@ -786,6 +794,10 @@ __global__ __launch_bounds__(SMALL ? 64 : SP_THREADS, SMALL ? 4 : 2) void sparse
                     S.BV[1] = px1;
                 }
                 b = 1;
+                {   // isnan(C(0,0)) (:245) runs after the first point too: NaN when k* is (a coordinate NaN or +-inf)
+                    const double c00 = (double)(-1.0f) / (kstar + s20);
+                    if (c00 != c00 && st == GPC_STATUS_OK) st = GPC_STATUS_NAN;
+                }
                 if (A.trace && tid == 0) A.trace[o + it] = 0x81;
                 __syncthreads();
                 continue;
@@ -976,11 +988,11 @@ __global__ __launch_bounds__(SMALL ? 64 : SP_THREADS, SMALL ? 4 : 2) void sparse
                     double a2 = 0.0;
                     for (int c = 0; c < ny; ++c) { const double a = S.alpha[c * ld + i]; a2 += a * a; }
                     const double score = a2 / (S.Q[sp_at<RES>(i, i, S.ldm)] + S.C[sp_at<RES>(i, i, S.ldm)]);
-                    if (!have || score < best) { best = score; loc = i; have = true; }
+                    if (!have || SP_TAKE(score, i, best, loc)) { best = score; loc = i; have = true; }
                 }
                 if (!have) best = __builtin_inf();
                 sp_block_argmin(best, loc, sval, sidx);
-                if (loc < 0 || loc >= b) loc = 0;          // all-NaN scores: the reference keeps minloc = 0
+                if (loc < 0 || loc >= b) loc = 0;
                 b = sp_delete_bv<RB, TRI, RES>(S, b, loc, A.prm.ref_field_delete_bug, Cstar, Qstar, Crep, Qrep, tri);
                 have_next = false;
                 if (((dec >> 1) & 7) < 7) dec += 2;
@@ -994,7 +1006,7 @@ __global__ __launch_bounds__(SMALL ? 64 : SP_THREADS, SMALL ? 4 : 2) void sparse
                     bool have = false;
                     for (int i = tid; i < b; i += SP_NTH) {
                         const double score = (double)1.0f / S.Q[sp_at<RES>(i, i, S.ldm)];
-                        if (!have || score < best) { best = score; loc = i; have = true; }
+                        if (!have || SP_TAKE(score, i, best, loc)) { best = score; loc = i; have = true; }
                     }
                     if (!have) best = __builtin_inf();
                     // one wave: if no lane holds a score below the threshold the loop ends whatever the minimum is (>= 1e-9f, or NaN:
@@ -1157,7 +1169,6 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
                                                    // evaluates all three channels and selects (6 .. 9 VALU operations per channel loop)
     const double sf = A.prm.sigmaf_sq, s20 = A.prm.noise, eps_tol = A.prm.eps_tol;
     const int capacity = A.prm.capacity;
-    const double kstar = sf;
 
     for (int base = blockIdx.x * R;; base += gridDim.x * R) {
         int patch;
@@ -1222,6 +1233,9 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
         double c00r = 0.0;                         // REG: C(0, 0) as lane 0 carries it (the NaN check of :245 reads it every point)
 #pragma unroll
         for (int p = 0; p < (REG ? B : 1); ++p) { Cr[p] = 0.0; Qr[p] = 0.0; }
+        // (lanes beyond the rows of state -- G = 32, B = 24 -- have no row: Cl[i + B p] for i >= B is row i - B of the next slot.  Their loads
+        // are harmless and left unmasked -- a masked load keeps the old registers alive and spills the second rows phase -- but their
+        // registers must never be stored over it)
         auto rows_to_regs = [&]() {
             if constexpr (REG) {
 #pragma unroll
@@ -1234,8 +1248,10 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
         };
         auto rows_to_lds = [&]() {
             if constexpr (REG) {
+                if (B == G || i < B) {
 #pragma unroll
-                for (int p = 0; p < B; ++p) Cl[i + B * p] = Cr[p];
+                    for (int p = 0; p < B; ++p) Cl[i + B * p] = Cr[p];
+                }
             }
         };
         if (take) rows_to_regs();
@@ -1291,6 +1307,7 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
                     ms = sp_slot<QN>(i, 1);                                  // (meaningful for lane 0)
                     p00 = B * sp_slot<QN>(0, 1);
                     if (i == 0) {
+                        const double kstar = sp_kstar(sf, px0, px1);   // kernel_function(X, X)  (:98)
                         SP_FOR_C(c) al[c] = yv[c] / (kstar + s20);
                         Cl[B * ms] = (double)(-1.0f) / (kstar + s20);
                         Ql[B * ms] = (double)(1.0f) / kstar;
@@ -1352,6 +1369,7 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
                         sums[1] = sp_row_sum<G>(sums[1]);
                         sums[2] = sp_row_sum<G>(sums[2]);
                     }
+                    const double kstar = sp_kstar(sf, px0, px1);    // kernel_function(X, X)  (:98; formed here: a shorter live range)
                     const double s2 = kstar + dots[0];
                     double gamma = kstar - dots[1];
                     if (gamma < (double)1e-12f) gamma = 0;          // :146-151
@@ -1675,7 +1693,6 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_predict_kernel(SpPredParams
         }
         if (A.sigma) {
             double* sg = A.off ? A.sigma + po : A.sigma + (size_t)patch * m;
-            const double kstar = sf;
             for (int p0 = 0; p0 < m; p0 += SP_PC) {
                 const int pc = min(SP_PC, m - p0);
                 __syncthreads();
@@ -1701,6 +1718,7 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_predict_kernel(SpPredParams
                 racc[ig * SP_PC + pp] = acc;
                 __syncthreads();
                 if (tid < pc) {
+                    const double kstar = sp_kstar(sf, xs0[p0 + tid], xs1[p0 + tid]);   // (:316)
                     double kCk = 0.0;
                     for (int q = 0; q < SP_THREADS / SP_PC; ++q) kCk += racc[q * SP_PC + tid];
                     double sigma = (b == 0) ? kstar + s20 : s20 + kstar + kCk;
@@ -1745,7 +1763,7 @@ __global__ __launch_bounds__(64) void sparse_predict_small_kernel(SpPredParams A
     const int lane = threadIdx.x;
     const int ld = A.ld, ny = A.ny;
     gpc_exp_table_init(T);
-    const double sf = A.prm.sigmaf_sq, s20 = A.prm.noise, kstar = sf;
+    const double sf = A.prm.sigmaf_sq, s20 = A.prm.noise;
     for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
         const int b = __builtin_amdgcn_readfirstlane(A.b[patch]);
         if (b < b_lo || b > BM) continue;
@@ -1804,6 +1822,8 @@ __global__ __launch_bounds__(64) void sparse_predict_small_kernel(SpPredParams A
                         kCk += t * k[j];
                     }
                 }
+                // (:316; the point's coordinates are read again here: kept live from the top of the loop they cost a wave per SIMD)
+                const double kstar = sp_kstar(sf, xs0[p], xs1[p]);
                 double sigma = (b == 0) ? kstar + s20 : s20 + kstar + kCk;
                 if (sigma < 0) { sigma = 0; clamped = true; }                 // :334-337
                 if (A.conf) {
@@ -1920,7 +1940,7 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_likelihood_kernel(SpLikPara
                     for (int w = 0; w < SP_THREADS / SP_PC; ++w) s_ += racc[(q * 8 + w) * SP_PC + tid];
                     r[q] = s_;
                 }
-                const double kstar = sf;
+                const double kstar = sp_kstar(sf, A.x0[o + p0 + tid], A.x1[o + p0 + tid]);
                 double offv[3] = {0.0, 0.0, 0.0}, sq = 0.0;
                 for (int c = 0; c < ny; ++c) {
                     offv[c] = A.y[(size_t)c * A.n_total + o + p0 + tid] - r[3 + c];

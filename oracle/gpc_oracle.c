@@ -391,6 +391,7 @@ struct orc_sparse {
     double* t;
     int32_t n_full, n_sparse, n_deleted;
     uint8_t last_dec;  /* decision byte of the last add (layout: gpc_oracle_hp.c) */
+    int status;        /* sticky: GPC_STATUS_NAN (2) once isnan(C(0,0)) after a point (:245), 0 otherwise */
 };
 
 void orc_sparse_default_params(orc_sparse_params* p, int ny)
@@ -442,6 +443,7 @@ void orc_sparse_reset(orc_sparse* g)
     g->total_count = 0;
     g->b = 0;
     g->n_full = g->n_sparse = g->n_deleted = 0;
+    g->status = 0;
 }
 
 int orc_sparse_size(const orc_sparse* g) { return g->b; }
@@ -534,7 +536,8 @@ void orc_sparse_add(orc_sparse* g, double x0, double x1, const double* y)
         g->BV[1] = x1;
         g->n_full++;
         g->last_dec = 0x81;
-        return;   /* the reference only checks isnan(C(0,0)) after this (:245) */
+        if (isnan(Cm(0, 0))) g->status = ORC_STATUS_NAN;   /* :245 runs after the first point too */
+        return;
     }
 
     int b = g->b;
@@ -652,6 +655,8 @@ void orc_sparse_add(orc_sparse* g, double x0, double x1, const double* y)
             }
         }
     }
+    /* "sparse_gp::C has become Nan" (:245) */
+    if (isnan(Cm(0, 0))) g->status = ORC_STATUS_NAN;
 }
 
 /* src/sparse_gp.hpp:59-86 with the permutation made an explicit input (F7) */
@@ -870,6 +875,28 @@ void orc_sparse_get_state(const orc_sparse* g, double* alpha, double* C, double*
         }
     if (BV) memcpy(BV, g->BV, sizeof(double) * 2 * (size_t)b);
 }
+
+/* inverse of orc_sparse_get_state (same layouts); C or Q NULL loads zeros, as gpc_sparse_set_state does.  The loaded state
+ * starts with total_count = b and the status cleared. */
+void orc_sparse_set_state(orc_sparse* g, int b, const double* alpha, const double* C, const double* Q, const double* BV)
+{
+    const size_t ld = (size_t)g->ld;
+    if (b < 0) b = 0;
+    if (b > g->ld) b = g->ld;
+    g->b = b;
+    g->total_count = b;
+    g->status = 0;
+    for (int c = 0; c < g->p.ny; ++c)
+        for (int i = 0; i < b; ++i) Al(c, i) = alpha[(size_t)c * b + i];
+    for (int j = 0; j < b; ++j)
+        for (int i = 0; i < b; ++i) {
+            Cm(i, j) = C ? C[i + (size_t)j * b] : 0.0;
+            Qm(i, j) = Q ? Q[i + (size_t)j * b] : 0.0;
+        }
+    memcpy(g->BV, BV, sizeof(double) * 2 * (size_t)b);
+}
+
+int orc_sparse_get_status(const orc_sparse* g) { return g->status; }
 
 void orc_sparse_get_counters(const orc_sparse* g, int32_t* n_full, int32_t* n_sparse, int32_t* n_deleted)
 {

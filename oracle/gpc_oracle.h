@@ -125,6 +125,12 @@ void orc_sparse_likelihood(const orc_sparse* g, int n, const double* x0, const d
 void orc_sparse_train_sigmaf(const orc_sparse* g, int n, const double* x0, const double* x1, const double* y, double step,
                              int max_counter, double* p0_out, int32_t* iters, double* ls, double* delta_out);
 void orc_sparse_get_state(const orc_sparse* g, double* alpha, double* C, double* Q, double* BV);
+/* inverse of orc_sparse_get_state, same layouts (alpha ny planes of b, C and Q b x b column-major, BV 2 x b interleaved); C or Q
+ * NULL loads zeros (gpc_sparse_set_state) */
+void orc_sparse_set_state(orc_sparse* g, int b, const double* alpha, const double* C, const double* Q, const double* BV);
+/* sticky status: ORC_STATUS_NAN once isnan(C(0,0)) after any point, the first included (src/sparse_gp.hpp:245) */
+#define ORC_STATUS_NAN 2   /* = GPC_STATUS_NAN */
+int orc_sparse_get_status(const orc_sparse* g);
 /* statistics: how many full / sparse updates and deletions happened (for BV-count agreement reports) */
 void orc_sparse_get_counters(const orc_sparse* g, int32_t* n_full, int32_t* n_sparse, int32_t* n_deleted);
 

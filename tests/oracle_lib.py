@@ -129,6 +129,9 @@ def _bind(L):
     L.orc_sparse_likelihood.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp]
     L.orc_sparse_train_sigmaf.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, d, C.c_int, c_dp, c_ip, c_dp, c_dp]
     L.orc_sparse_get_state.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_dp]
+    L.orc_sparse_set_state.argtypes = [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp]
+    L.orc_sparse_get_status.restype = C.c_int
+    L.orc_sparse_get_status.argtypes = [C.c_void_p]
     L.orc_sparse_fit_predict_batch.restype = C.c_int
     L.orc_sparse_fit_predict_batch.argtypes = [C.POINTER(SparseParams), C.c_int, C.c_int, c_ip, c_dp, c_dp, c_dp, c_ip,
                                                C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]
@@ -312,6 +315,18 @@ class Sparse:
         BV = np.zeros((b, 2))
         self.L.orc_sparse_get_state(self.h, _dp(alpha), _dp(Ccm), _dp(Qcm), _dp(BV))
         return alpha, Ccm.T.copy(), Qcm.T.copy(), BV
+
+    def set_state(self, alpha, Cm, Qm, BV):
+        """inverse of state(): alpha (ny, b), C and Q (b, b) or None (zeros), BV (b, 2)"""
+        alpha = np.ascontiguousarray(np.atleast_2d(alpha), dtype=np.float64)
+        b = alpha.shape[1]
+        assert alpha.shape[0] == self.ny and BV.shape == (b, 2)
+        cm = lambda M: None if M is None else np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(b, b).T)   # column-major
+        self.L.orc_sparse_set_state(self.h, b, _dp(alpha), _dp(cm(Cm)), _dp(cm(Qm)), _dp(np.ascontiguousarray(BV, dtype=np.float64)))
+
+    def status(self):
+        """sticky status word: 2 (GPC_STATUS_NAN) once C(0, 0) was NaN after a point, else 0"""
+        return int(self.L.orc_sparse_get_status(self.h))
 
     def counters(self):
         a = np.zeros(3, dtype=np.int32)

@@ -31,6 +31,31 @@ def draw(rng, synth, res=0.15):
     return dict(ny=ny, cap=cap, kernel=kernel, P=P, n=n, off=off, x0=x0, x1=x1, y=y, perm=perm, kw=kw)
 
 
+def draw_poisoned(rng, synth, rng_poison):
+    """draw() (its own stream untouched), then one to three patches poisoned from `rng_poison` with one of the inputs of
+    tests/nonfinite_cases.py (a NaN or +inf y or coordinate on a middle point, +inf on the first point, or the patch cut to one NaN point)"""
+    import nonfinite_cases as NF
+    c = draw(rng, synth)
+    off, x0, x1, y = c["off"], c["x0"].copy(), c["x1"].copy(), c["y"].copy()
+    P = c["P"]
+    kinds = []
+    for j in rng_poison.choice(P, size=min(P, int(rng_poison.integers(1, 4))), replace=False):
+        j = int(j)
+        kind = str(rng_poison.choice(list(NF.POISONS) + ["one_point_nan"]))
+        if kind == "one_point_nan":
+            off, x0, x1, y, keep = NF.one_point_nan(off, x0, x1, y, j)
+            if c["perm"] is not None:
+                c["perm"] = np.ascontiguousarray(c["perm"][keep])
+                c["perm"][off[j]] = 0
+        else:
+            o, m = int(off[j]), int(off[j + 1] - off[j])
+            order = c["perm"][o:o + m] if c["perm"] is not None else np.arange(m)
+            NF.poison(kind, x0, x1, y, o, m, order)
+        kinds.append(kind)
+    c.update(off=off, x0=x0, x1=x1, y=y, poisoned=kinds)
+    return c
+
+
 def run(capi, ctx, c, env=None, predict=None):
     """three add calls (the first in a drawn insertion order) under the environment switches `env` ("A+B" for two); returns
     (status / trace per call, basis sizes, state)"""
@@ -74,14 +99,16 @@ def same(a, b, P):
     return True
 
 
-def sweep(capi, synth, ctx, ncfg, seed, progress=None):
+def sweep(capi, synth, ctx, ncfg, seed, progress=None, poisoned=False):
     """-> (mismatching configurations, histogram of the final basis sizes seen).  The caller sets GPC_SPARSE_FULL=1 (kernel SHAPES are compared
     in the full mode: the triangular passes of the four-wave shape sum a row in another order)."""
     rng = np.random.default_rng(seed)
+    rng_poison = np.random.default_rng(seed + 1000)
     grid = synth.grid(0.15, 12)
     bad, hist = [], {"max_b": 0, "le16": 0, "17_24": 0, "25_48": 0, "gt48": 0}
     for k in range(ncfg):
-        c = draw(rng, synth)
+        c = draw_poisoned(rng, synth, rng_poison) if poisoned else draw(rng, synth)
+        hist["poisoned"] = hist.get("poisoned", 0) + len(c.get("poisoned", ()))
         a, b = run(capi, ctx, c, predict=grid), run(capi, ctx, c, "GPC_SPARSE_NO_SMALL")
         pred_ok = a[3]
         a = a[:3]

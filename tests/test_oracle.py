@@ -650,3 +650,89 @@ def test_sparse_parity_statistics_gate(oracle):
     assert not s2["gate"]["ok"] and s2["blowups"]["gpu"] >= 8 and len(s2["blowups"]["patches"]) >= 8
     bad_t = ft * 1.5
     assert not SP.stats(op, off, x0, x1, y, xs0, xs1, f, bad_t, np.arange(64), threads=4)["gate"]["ok"]
+
+
+# ------------------------------------------------------------------ loading a state, the sticky NaN status, deletion on non-finite scores
+
+def test_sparse_set_state_round_trip(oracle):
+    """orc_sparse_set_state is the inverse of orc_sparse_get_state, bit for bit, and the loaded object goes on as the original does"""
+    import nonfinite_cases as NF
+    res = 0.15
+    off, x0, x1, y = synth.make_patches(1, 90, res=res, seed=61, ny=3)
+    op = oracle.sparse_params(3, p0=1.0, p1=(res / 8) ** 2, s20=1.0, capacity=20)
+    g = oracle.Sparse(op, 22)
+    g.add_measurements(x0[:60], x1[:60], y[:, :60])
+    st = g.state()
+    h = oracle.Sparse(op, 22)
+    h.set_state(*st)
+    assert h.size() == g.size() == 20 and h.status() == 0
+    for u, v in zip(st, h.state()):
+        assert np.array_equal(u, v)
+    tg = g.add_measurements(x0[60:], x1[60:], y[:, 60:], trace=True)
+    th = h.add_measurements(x0[60:], x1[60:], y[:, 60:], trace=True)
+    assert np.array_equal(tg, th)
+    for u, v in zip(g.state(), h.state()):
+        assert np.array_equal(u, v)
+    # NULL C and Q load zeros
+    a, _, _, BV = NF.lattice_state(7, 1, 3)
+    h1 = oracle.Sparse(oracle.sparse_params(1, capacity=10), 12)
+    h1.set_state(a, None, None, BV)
+    s1 = h1.state()
+    assert h1.size() == 7 and np.array_equal(s1[0], a) and np.array_equal(s1[3], BV)
+    assert not np.any(s1[1]) and not np.any(s1[2])
+
+
+def test_sparse_status_nan_is_sticky(oracle):
+    """status 2 exactly when some point left C(0, 0) NaN (src/sparse_gp.hpp:245 runs after the first point too)"""
+    res = 0.15
+    op = oracle.sparse_params(1, p0=1.0, p1=(res / 8) ** 2, s20=1e-4, capacity=20)
+    off, x0, x1, y = synth.make_patches(1, 40, res=res, seed=62)
+    # a first point with an infinite coordinate: k* = p0 exp(-0.5/p1 (inf - inf)^2) = NaN
+    g = oracle.Sparse(op, 22)
+    g.add(0.01, np.inf, 0.0)
+    assert g.status() == 2
+    a, C_, Q_, _ = g.state()
+    assert np.isnan(a[0, 0]) and np.isnan(C_[0, 0]) and np.isnan(Q_[0, 0])
+    g.add_measurements(x0, x1, y)
+    assert g.status() == 2 and np.all(np.isnan(g.state()[1]))
+    # finite data: status 0 after every point; a NaN y leaves C finite (status 0) but alpha NaN
+    g = oracle.Sparse(op, 22)
+    for i in range(20):
+        g.add(x0[i], x1[i], y[0, i])
+        assert g.status() == 0
+    g.add(x0[20], x1[20], np.nan)
+    assert g.status() == 0 and np.any(np.isnan(g.state()[0])) and not np.any(np.isnan(g.state()[1]))
+    # a NaN coordinate later on: k and k* NaN, the full update makes C NaN, and the status stays NaN whatever follows
+    g.add(np.nan, x1[21], y[0, 21])
+    assert g.status() == 2 and np.isnan(g.state()[1][0, 0])
+    g.add_measurements(x0[22:], x1[22:], y[:, 22:])
+    assert g.status() == 2
+    g.reset()
+    assert g.status() == 0
+
+
+@pytest.mark.parametrize("case", ["a", "b", "c"])
+@pytest.mark.parametrize("cap", [12, 48])
+def test_sparse_capacity_deletion_on_nonfinite_scores(oracle, case, cap):
+    """The vector a capacity deletion removes from a loaded state equals the reference's scan (src/sparse_gp.hpp:206-217, transcribed in
+    tests/nonfinite_cases.py): a NaN score at index 0 deletes vector 0, a NaN score elsewhere is skipped."""
+    import nonfinite_cases as NF
+    kw = NF.KW_LOAD
+    alpha, C_, Q_, BV = NF.loaded_case(case, cap, 1)
+    x0, x1, y = NF.new_points(1, 1, seed=cap)
+    op = oracle.sparse_params(1, p0=kw["sigmaf_sq"], p1=kw["l_sq"], s20=kw["noise"], capacity=cap)
+    opb = oracle.sparse_params(1, p0=kw["sigmaf_sq"], p1=kw["l_sq"], s20=kw["noise"], capacity=cap + 1)
+    big = oracle.Sparse(opb, cap + 2)       # the full update without the deletion
+    big.set_state(alpha, C_, Q_, BV)
+    assert big.add_measurements(x0, x1, y, trace=True)[0] == 0x01 and big.size() == cap + 1
+    a1, C1, Q1, _ = big.state()
+    loc = NF.ref_capacity_argmin(a1, np.diag(Q1), np.diag(C1))
+    assert loc == {"a": 0, "b": cap, "c": 0}[case]
+    big.delete_bv(loc)
+    g = oracle.Sparse(op, cap + 2)
+    g.set_state(alpha, C_, Q_, BV)
+    assert g.add_measurements(x0, x1, y, trace=True)[0] == 0x03 and g.size() == cap
+    for u, v in zip(g.state(), big.state()):
+        assert np.array_equal(u, v, equal_nan=True)
+    # (a) 0/0 on the deleted vector's diagonal makes the whole state NaN; (c) the NaN stays in alpha
+    assert g.status() == (2 if case == "a" else 0)
