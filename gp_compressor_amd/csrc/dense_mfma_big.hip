@@ -56,24 +56,10 @@ struct BigParams {
     int32_t* irls_iters;          // [P] solves performed, or nullptr
     double* irls_fhat;            // [n_total] latent mode at the training points, or nullptr
 };
-// BG_HINT bit 1: the backward solve reads the factor once -- its loads carry the non-temporal hint, so that they do not push the block rows
-// a step reads several times out of L2 (the one-wave kernel: 1.738 -> 1.680 ms with the same hint, dense_mfma_w1.hip)
+// The backward solve reads the factor once -- its loads carry the non-temporal hint (mf_img_load_nt), so that they do not push the block
+// rows a step reads several times out of L2 (the one-wave kernel: 1.738 -> 1.680 ms with the same hint, dense_mfma_w1.hip)
 // (C3 11.91 -> 11.78 ms, C5 299 -> 298 ms same box)
-#ifndef BG_HINT
-#define BG_HINT 1
-#endif
-#define BG_LOAD_BACK(p, l) ((BG_HINT & 1) ? mf_img_load_nt(p, l) : mf_img_load(p, l))
 #define BG_NPH 12
-// Diagnostic builds only (tools/r3_exp.sh; results are wrong by construction, timings tell what a phase costs under real overlap):
-//   -DBG_EXP_HOT     every j-indexed operand load reads tile column 0 (L1 hits): what the factor stream costs
-//   -DBG_EXP_NOGRAM  the Gram tiles are a constant diagonally dominant matrix (no exponentials)
-//   -DBG_EXP_NOBACK / -DBG_EXP_NOPRED  skip the backward solve / the predictive mean
-#ifdef BG_EXP_HOT
-__device__ static __forceinline__ int bg_exp_zero() { int z; asm volatile("s_mov_b32 %0, 0" : "=s"(z)); return z; }   // (not hoistable)
-#define BG_JX(j) bg_exp_zero()
-#else
-#define BG_JX(j) (j)
-#endif
 // -DBG_SUBSTAMPS (diagnostic build, tools/stamp_big.py): the factorisation step split into 5 diagonal-block tiles, 6 update loops,
 // 7 waiting for an L^-1 (workers) or a hand-over (wave 0), 8 TRSMs (workers) or the chain (wave 0), 9 end-of-step barrier
 #ifdef BG_SUBSTAMPS
@@ -291,11 +277,7 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
         // update / factor, publishing each L^-1 as it appears.  The rows r >= k+4 are dealt to the workers (or taken from a counter,
         // two-wave shape): update the four accumulators, then column by column  acc_c -= sum_{c2<c} L_r(k+c2) L_(k+c)(k+c2)^T,
         // L_r(k+c) = TRSM(acc_c).
-#ifdef BG_EXP_NOGRAM
-#define BG_GRAM_VALUE(xi0_, xi1_, pj_) ((pi_ == (pj_)) ? sf : 0.001 * sf)
-#else
 #define BG_GRAM_VALUE(xi0_, xi1_, pj_) (small_gram ? gpc_rbf_small(sf, cexp, xi0_, xi1_, px0[pj_], px1[pj_]) : gpc_rbf_neg(sf, cexp, xi0_, xi1_, px0[pj_], px1[pj_], T))
-#endif
 #define BG_INIT_TILE(dst, r_, kc_)                                                                                   \
     do {                                                                                                             \
         if ((r_) < nt) {                                                                                             \
@@ -386,8 +368,8 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
         _Pragma("unroll") for (int jq_ = 0; jq_ < 4 / NPC; ++jq_) {                                                  \
             const int jj_ = min((j0) + jq_, kl);                                                                     \
             _Pragma("unroll") for (int t = 0; t < NPC; ++t) {                                                        \
-                ga[st][jq_ * NPC + t] = mf_img_load(ra[t] + (size_t)BG_JX(jj_) * MF_IMG, lane);                             \
-                gb[st][jq_ * NPC + t] = mf_img_load(rb[t] + (size_t)BG_JX(jj_) * MF_IMG, lane);                             \
+                ga[st][jq_ * NPC + t] = mf_img_load(ra[t] + (size_t)jj_ * MF_IMG, lane);                             \
+                gb[st][jq_ * NPC + t] = mf_img_load(rb[t] + (size_t)jj_ * MF_IMG, lane);                             \
             }                                                                                                        \
         }                                                                                                            \
     } while (0)
@@ -445,7 +427,7 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                             const int jn = min(j + h + 1, kl);
 #pragma unroll
                             for (int i = 0; i < BG_C; ++i)
-                                if (i <= i_hi) op[h ^ 1][i] = mf_img_load(rrow[i] + (size_t)BG_JX(jn) * MF_IMG, lane);
+                                if (i <= i_hi) op[h ^ 1][i] = mf_img_load(rrow[i] + (size_t)jn * MF_IMG, lane);
 #pragma unroll
                             for (int d = 0; d < NDT; ++d) {
                                 const int bi = d >= 6 ? 3 : d >= 3 ? 2 : d >= 1 ? 1 : 0, bc = d - bi * (bi + 1) / 2;
@@ -508,9 +490,6 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                 // the serial chain of the block: factor (k,k); then row by row  L_ic = (T_ic - sum_{c2<c} L_ic2 L_cc2^T) L_cc^-T,
                 // T_ii -= sum_c L_ic L_ic^T, factor -- every L^-1 published as it appears, the block's tiles left in LDS for the workers
                 bool ok = mf_diag_factor<true>(Dmine, rsbuf, LinvC, LinvTg + (size_t)k * MF_IMG, g.pivot_tol);
-#ifdef BG_EXP_HOT
-                ok = true;
-#endif
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 if (g.export_factor) mf_img_store(LinvG + (size_t)k * MF_IMG, lane, mf_img_load(LinvC, lane));
                 if (!ok && lane == 0) flag[0] = 1;
@@ -542,9 +521,6 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
 #pragma unroll
                         for (int c = 0; c < i; ++c) Dii = bg_mfma4_neg(Lrow[c], Lrow[c], Dii);
                         ok = mf_diag_factor<true>(Dii, rsbuf, LinvC + i * 256, LinvTg + (size_t)(k + i) * MF_IMG, g.pivot_tol);
-#ifdef BG_EXP_HOT
-                        ok = true;
-#endif
                         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                                 if (g.export_factor) mf_img_store(LinvG + (size_t)(k + i) * MF_IMG, lane, mf_img_load(LinvC + i * 256, mf_opaque(lane)));
                         if (!ok && lane == 0) flag[0] = 1;
@@ -581,7 +557,7 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                         for (int h = 0; h < 2; ++h) {
                             const int jn = min(j + h + 1, k - 1);
 #pragma unroll
-                            for (int c = 0; c < BG_C; ++c) fa[h ^ 1][c] = mf_img_load(rc_[c] + (size_t)BG_JX(jn) * MF_IMG, ln);
+                            for (int c = 0; c < BG_C; ++c) fa[h ^ 1][c] = mf_img_load(rc_[c] + (size_t)jn * MF_IMG, ln);
                             if (j + h < k) {
 #pragma unroll
                                 for (int ch = 0; ch < BG_NYP; ++ch) {
@@ -680,8 +656,8 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                     const int kl = k - 1;
 #define BG_LOAD_STAGE(st, jj, NPC)                                                                                   \
     do {                                                                                                             \
-        _Pragma("unroll") for (int c = 0; c < BG_C; ++c) sa[st][c] = mf_img_load(rc_[c] + (size_t)BG_JX(jj) * MF_IMG, lane); \
-        _Pragma("unroll") for (int t = 0; t < NPC; ++t) sb[st][t] = mf_img_load(rw_[t] + (size_t)BG_JX(jj) * MF_IMG, lane);  \
+        _Pragma("unroll") for (int c = 0; c < BG_C; ++c) sa[st][c] = mf_img_load(rc_[c] + (size_t)(jj) * MF_IMG, lane); \
+        _Pragma("unroll") for (int t = 0; t < NPC; ++t) sb[st][t] = mf_img_load(rw_[t] + (size_t)(jj) * MF_IMG, lane);  \
     } while (0)
 #define BG_USE_STAGE(st, NPC)                                                                                        \
     do {                                                                                                             \
@@ -758,7 +734,6 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
 #endif
         __syncthreads();   // z (LDS, written by wave 0 step by step) is complete
         BG_STAMP(2);
-#ifndef BG_EXP_NOBACK
         // ---- backward solve L^T alpha = z, tile columns from the last to the first ----
         // Column k needs the tiles (i, k), i = k+1+wave+W t, and L_kk^-T: they do not depend on alpha, so the loads of
         // column k-1 are issued before the products of column k (the factor sits in HBM / Infinity Cache, ~2k cycles away).
@@ -767,15 +742,15 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
             d4 cur[BT], nxt[BT], lt_cur = d4{0.0, 0.0, 0.0, 0.0}, lt_nxt = lt_cur;
 #pragma unroll
             for (int t = 0; t < BT; ++t) cur[t] = nxt[t] = d4{0.0, 0.0, 0.0, 0.0};
-            if (wave == 0) lt_cur = BG_LOAD_BACK(LinvTg + (size_t)(nt - 1) * MF_IMG, lane);
+            if (wave == 0) lt_cur = mf_img_load_nt(LinvTg + (size_t)(nt - 1) * MF_IMG, lane);
             for (int k = nt - 1; k >= 0; --k) {
                 if (k > 0) {
 #pragma unroll
                     for (int t = 0; t < BT; ++t) {
                         const int i = k + wave + BG_WAVES * t;               // rows of column k-1: i >= k
-                        if (i < nt) nxt[t] = BG_LOAD_BACK(Lt + ((size_t)i * ntw + (k - 1)) * MF_IMG, lane);
+                        if (i < nt) nxt[t] = mf_img_load_nt(Lt + ((size_t)i * ntw + (k - 1)) * MF_IMG, lane);
                     }
-                    if (wave == 0) lt_nxt = BG_LOAD_BACK(LinvTg + (size_t)(k - 1) * MF_IMG, lane);
+                    if (wave == 0) lt_nxt = mf_img_load_nt(LinvTg + (size_t)(k - 1) * MF_IMG, lane);
                 }
                 d4 pa[3];
 #pragma unroll
@@ -829,7 +804,6 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                 lt_cur = lt_nxt;
             }
         }
-#endif
         if constexpr (!BG_IRLS) break;
         if constexpr (BG_IRLS) {
             // the solve gave u = B^-1 W^1/2 t:  a = W^1/2 u,  f_new = K a = t - W^-1 a = t - W^-1/2 u;  the step's max |f_new - f|
@@ -888,7 +862,6 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
         }
 
         BG_STAMP(3);
-#ifndef BG_EXP_NOPRED
         // ---- predictive mean ----
         if (A.xs0 == nullptr && A.grid_sz <= 32) {
             // separable grid: f[py][px] = sum_i Ey[py][i] * (sf alpha_i Ex[px][i]); 32-point chunks dealt to the waves
@@ -970,7 +943,6 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                     if (c < ny) fs[(size_t)c * m + p] = s_[c];
             }
         }
-#endif
         BG_STAMP(4);
         if (timed_out && lane == 0) flag[0] = 2;
         __syncthreads();
@@ -1001,7 +973,7 @@ static void big_shape(const DenseArgs& a, bool irls, int* waves, int* npad, int*
     // (273 .. 324 points): GP phase 3.29 against 3.42 ms.  At n = 512 (C3) the 8-wave shape used to win, 13.2 against 13.4 ms -- both
     // chain waves sat on SIMD 0, which then idled; with the second workgroup's chain on SIMD 2 (HW_ID wave slot, see the kernel) the
     // two-workgroup shape wins, 12.23 against 12.63 ms on the same box (round 3)
-    else if (a.n_max <= (getenv("GPC_BIG_W4_384") ? 384 : 512) && a.ny == 1 && !irls && !getenv("GPC_BIG_NO_W4")) { *waves = 4; *npad = 512; *per_cu = 2; }
+    else if (a.n_max <= 512 && a.ny == 1 && !irls && !getenv("GPC_BIG_NO_W4")) { *waves = 4; *npad = 512; *per_cu = 2; }
     else { *waves = 8; *npad = 1024; *per_cu = 1; }
 }
 
@@ -1010,8 +982,7 @@ size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out)
     int waves, npad, per_cu;
     big_shape(a, false, &waves, &npad, &per_cu);
     const int ntw = (a.n_max + MF_TS - 1) / MF_TS;
-    int cap = ctx->num_cus * per_cu;
-    if (const char* e = getenv("GPC_BIG_GRID")) cap = atoi(e) > 0 ? atoi(e) : cap;   // diagnostic: resident-workgroup experiments
+    const int cap = ctx->num_cus * per_cu;
     const int grid = a.P < cap ? a.P : cap;
     if (grid_out) *grid_out = grid;
     // with the variance requested the factor of every patch is kept (one slot per patch) + alpha + the per-wave V scratch of
@@ -1053,7 +1024,7 @@ int dense_irls_launch(gpc_ctx* ctx, const DenseArgs& a, const IrlsArgs& ir, int 
     g.irls_fhat = ir.fhat;
     if (!ctx->tickets) GPC_HIP(ctx, hipMalloc(&ctx->tickets, 64 * sizeof(int32_t)));
     GPC_HIP(ctx, hipMemsetAsync(ctx->tickets, 0, sizeof(int32_t), ctx->stream));
-    g.ticket = getenv("GPC_BIG_STATIC") ? nullptr : ctx->tickets;
+    g.ticket = ctx->tickets;
     int waves, npad, per_cu;
     big_shape(a, true, &waves, &npad, &per_cu);
     if (waves == 4) {

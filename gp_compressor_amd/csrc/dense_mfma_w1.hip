@@ -34,55 +34,15 @@
 #define W1_TRI_OF(npad) (W1_NT_OF(npad) * (W1_NT_OF(npad) + 1) / 2)  // images of a slot
 // offset (doubles) of tile (i, j), j <= i, in a slot
 #define W1_TILE(i, j) (((size_t)(i) * (size_t)((i) + 1) / 2 + (size_t)(j)) * MF_IMG)
-// Diagnostic build -DW1_EXP_HOT (results wrong by construction): every j-indexed operand load reads tile column 0 -- what the
-// latency of the factor stream costs
-#ifdef W1_EXP_HOT
-__device__ static __forceinline__ int w1_exp_zero() { int z; asm volatile("s_mov_b32 %0, 0" : "=s"(z)); return z; }   // (not hoistable)
-#define W1_JX(j) w1_exp_zero()
-#else
-#define W1_JX(j) (j)
-#endif
 
-// Non-temporal hints on the streams that are used once (-DW1_HINT=mask: 1 the backward solve's loads, 2 the row operands of the passes,
-// 4 the stores of the factor tiles), so that the block rows a step reads three times (sweep, column operands of two passes) have a better
-// chance to stay in L2.  Measured on one box, C2: none 1.738 ms, backward loads 1.680 (-3.4 %), row operands 1.755 (they ARE read again,
-// one step later), stores 1.742, all three 1.727: the backward solve's loads carry the hint.
-#ifndef W1_HINT
-#define W1_HINT 1
-#endif
-// Round 4 (each with its own switch, so that one library build can be timed against another on the same box):
-//   W1_TRSM_CHAIN  the four products of a TRSM chained through the accumulator instead of four independent products + an add tree
-//                  (12 VALU adds per TRSM, 136 TRSMs per patch)
-//   W1_CMASK       the diagonal factor with constant lane masks in SGPR pairs (mf_diag_factor_c: 4 instead of ~12 VALU per pivot)
-//   W1_CARRY       the row pass of a step that covers the NEXT block's rows runs last and its sixteen result tiles stay in registers:
-//                  the next step's block takes the products over those four tile columns from them, its sweep reads only the columns
-//                  before (48 of the 96 sweep images of a 16-row factor are not read at all)
-//   W1_LASTRES     the last step's block (six tiles + four L_cc^-T) goes into the backward solve from registers / LDS and is never
-//                  written to the workspace (n a multiple of 64 points' worth of tiles, no factor export)
-#ifndef W1_TRSM_CHAIN
-#define W1_TRSM_CHAIN 1
-#endif
-#ifndef W1_CMASK
-#define W1_CMASK 1
-#endif
-// (W1_CARRY and W1_LASTRES are OFF in the shipped build: hipcc answers both with register spills that move more bytes than they save --
-//  46 / 386 / 208 spilled VGPRs without / with the carry / with the resident last block, scratch stores and reloads in every step)
-#ifndef W1_CARRY
-#define W1_CARRY 0
-#endif
-#ifndef W1_LASTRES
-#define W1_LASTRES 0
-#endif
-#if W1_LASTRES && !W1_CMASK
-#error "W1_LASTRES needs the diagonal factor that can skip its L^-T store (W1_CMASK)"
-#endif
-#define W1_LOAD_BACK(p, l) ((W1_HINT & 1) ? mf_img_load_nt(p, l) : mf_img_load(p, l))
-#define W1_LOAD_ROWOP(p, l) ((W1_HINT & 2) ? mf_img_load_nt(p, l) : mf_img_load(p, l))
-#define W1_STORE_TILE(p, l, v)                                                                                        \
-    do {                                                                                                             \
-        if (W1_HINT & 4) mf_img_store_nt(p, l, v);                                                                     \
-        else mf_img_store(p, l, v);                                                                                  \
-    } while (0)
+// Non-temporal hint on the one stream that is used once and gains by it, the backward solve's loads (mf_img_load_nt), so that the block
+// rows a step reads three times (sweep, column operands of two passes) have a better chance to stay in L2.  Measured on one box, C2: none
+// 1.738 ms, backward loads 1.680 (-3.4 %), row operands of the passes 1.755 (they ARE read again, one step later), stores of the factor
+// tiles 1.742, all three 1.727.
+// Round 4: the four products of a TRSM are chained through the accumulator (w1_trsm: no add tree, 12 VALU adds less per TRSM, 136 TRSMs
+// per patch), and the diagonal factor keeps constant lane masks in SGPR pairs (mf_diag_factor_c: 4 instead of ~12 VALU per pivot).  Two
+// forms that cut the factor traffic -- the next block's row pass carried in registers, the last block resident for the backward solve --
+// were removed: hipcc answered both with register spills that moved more bytes than they saved (last in commit 6fe6b63).
 
 struct W1Params {
     DenseArgs a;
@@ -151,17 +111,10 @@ __device__ static __forceinline__ d4 w1_mfma4_neg(d4 a, d4 b, d4 acc)
 __device__ static __forceinline__ d4 w1_trsm(d4 lv, d4 src)
 {
     const d4 z4 = d4{0.0, 0.0, 0.0, 0.0};
-#if W1_TRSM_CHAIN
     d4 D = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[0], src[0], z4, 0, 0, 0);
     D = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[1], src[1], D, 0, 0, 0);
     D = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[2], src[2], D, 0, 0, 0);
     return __builtin_amdgcn_mfma_f64_16x16x4f64(lv[3], src[3], D, 0, 0, 0);
-#endif
-    const d4 D0 = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[0], src[0], z4, 0, 0, 0);
-    const d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[1], src[1], z4, 0, 0, 0);
-    const d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[2], src[2], z4, 0, 0, 0);
-    const d4 D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[3], src[3], z4, 0, 0, 0);
-    return (D0 + D1) + (D2 + D3);
 }
 
 // Gram tiles (tile row r, tile columns c0 .. c0 + CNT - 1) in the transposed C/D layout: register q of lane l of tile t =
@@ -184,13 +137,9 @@ __device__ static __forceinline__ void w1_gram_row(d4 (&v)[W1_C], const double* 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int pj = MF_TS * (c0 + t) + lg + 4 * q;
-#ifdef W1_EXP_NOGRAM       // diagnostic (results wrong by construction, the matrix stays SPD): what the Gram evaluations cost
-            v[t][q] = (pi == pj) ? 1.0 : 1e-3;
-#else
             const double d0 = xi0 - px0[pj], d1 = xi1 - px1[pj];
             const double sq = __builtin_fma(d0, d0, d1 * d1);
             v[t][q] = MODE == 0 ? gpc_exp_neg(cexp * sq, T) : gpc_expm_poly<MODE == 1 ? 7 : 5>(sq);
-#endif
         }
     }
     if (scale_sf) {
@@ -306,10 +255,6 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
             mode_g = __builtin_amdgcn_readfirstlane(tg <= GPC_EXP_TINY_MAX ? 2 : tg <= GPC_EXP_SMALL_MAX ? 1 : 0);
             mode_p = __builtin_amdgcn_readfirstlane(tp <= GPC_EXP_TINY_MAX ? 2 : tp <= GPC_EXP_SMALL_MAX ? 1 : 0);
             if (mode_g == 0) mode_p = 0;
-#ifdef W1_EXP_FORCE_MODE      // diagnostic: the regime chosen by hand (0 table, 1 degree 7, 2 degree 5)
-            mode_g = mode_g > 0 ? W1_EXP_FORCE_MODE : 0;
-            mode_p = mode_p > 0 ? W1_EXP_FORCE_MODE : 0;
-#endif
         }
         const bool scaled = mode_g > 0;
         {
@@ -376,98 +321,66 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                 }
             }
         };
-        constexpr int NLAST = W1_C * (W1_C + 1) / 2;   // stream positions of the last block: its six tiles and four L_cc^-T
         bool bad = false;
         W1_STAMP(0);
         // ---- tiled left-looking Cholesky, four tile columns (k .. k+3) per step ----
-        // Rotated loop (W1_CARRY): the accumulators of a step's diagonal block, tacc, and its forward-solve sums, part, are set up at
-        // the END of the previous step, right behind the row pass of the block's own rows -- that pass runs last, its sixteen result
-        // tiles cy[c][t] (the operand images of L_(k+4+t)(k+c)) are still in registers, and the block takes its products over those
-        // four tile columns from them.  The step then sweeps only the tile columns before (jend), from the workspace.  What crosses
-        // the loop's back edge is tacc and part (88 registers that the sweep needs anyway), never the sixteen tiles.
-#if W1_CARRY
-        d4 tacc[W1_NDT];
-        double part[W1_C];
-#endif
-        // block row bi of the step at kb (nb tile columns): Gram tiles (kb + bi, kb .. kb + bi), the last one the diagonal tile; WITH_CY:
-        // minus the products over the previous step's tile columns, and the forward-solve sums over them (z of those columns is final).
-        // From the last row down, so that the carry rows above bi are dead once it is done.
-#define W1_BLOCK_ROW(bi, kb, nb, WITH_CY)                                                                            \
+        // block row bi of the step at kb (nb tile columns): Gram tiles (kb + bi, kb .. kb + bi), the last one the diagonal tile
+#define W1_BLOCK_ROW(bi, kb, nb)                                                                                     \
     do {                                                                                                             \
         if ((bi) < (nb)) {                                                                                           \
             d4 gv[W1_C];                                                                                             \
             W1_GRAM_ROW(gv, (bi) + 1, true, (kb) + (bi), (kb));                                                      \
             _Pragma("unroll") for (int bc = 0; bc <= (bi); ++bc) tacc[(bi) * ((bi) + 1) / 2 + bc] = gv[bc];           \
-            if (WITH_CY) {                                                                                           \
-                _Pragma("unroll") for (int c = 0; c < W1_C; ++c) {                                                   \
-                    _Pragma("unroll") for (int bc = 0; bc <= (bi); ++bc)                                             \
-                        tacc[(bi) * ((bi) + 1) / 2 + bc] = w1_mfma4_neg(cy[c][bc], cy[c][bi], tacc[(bi) * ((bi) + 1) / 2 + bc]); \
-                    const double* zq = zv + MF_TS * ((kb) - W1_C + c) + lg;                                          \
-                    part[bi] += (cy[c][bi][0] * zq[0] + cy[c][bi][1] * zq[4]) + (cy[c][bi][2] * zq[8] + cy[c][bi][3] * zq[12]); \
-                }                                                                                                    \
-            }                                                                                                        \
-        } else {     /* (zeroed HERE, not up front: ten live zero tiles beside the sixteen carry tiles do not fit) */       \
+        } else {                                                                                                     \
             _Pragma("unroll") for (int bc = 0; bc <= (bi); ++bc) tacc[(bi) * ((bi) + 1) / 2 + bc] = d4{0.0, 0.0, 0.0, 0.0}; \
         }                                                                                                            \
     } while (0)
-#define W1_BLOCK_INIT(kb, nb, WITH_CY)                                                                               \
+#define W1_BLOCK_INIT(kb, nb)                                                                                        \
     do {                                                                                                             \
         _Pragma("unroll") for (int i = 0; i < W1_C; ++i) part[i] = 0.0;                                              \
-        /* (scheduling barriers: left alone, hipcc evaluates all ten Gram tiles first -- 80 registers beside the sixteen carry   \
-           tiles -- and spills the accumulators) */                                                                    \
+        /* (scheduling barriers and the order, last row first, are for the register allocator: left alone, hipcc evaluates all  \
+           ten Gram tiles first -- 80 registers -- and spills the accumulators) */                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
-        W1_BLOCK_ROW(3, kb, nb, WITH_CY);                                                                            \
+        W1_BLOCK_ROW(3, kb, nb);                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
-        W1_BLOCK_ROW(2, kb, nb, WITH_CY);                                                                            \
+        W1_BLOCK_ROW(2, kb, nb);                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
-        W1_BLOCK_ROW(1, kb, nb, WITH_CY);                                                                            \
+        W1_BLOCK_ROW(1, kb, nb);                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
-        W1_BLOCK_ROW(0, kb, nb, WITH_CY);                                                                            \
+        W1_BLOCK_ROW(0, kb, nb);                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
     } while (0)
-#if W1_CARRY
-        {
-            d4 cy[W1_C][4];       // (never read: step 0 has no columns before it)
-            const int nb0 = min(W1_C, nt);
-            W1_BLOCK_INIT(0, nb0, false);
-        }
-#endif
-        const bool lastres = W1_LASTRES && (nt & 3) == 0 && !g.export_factor;
         W1_STAMP(1);
         for (int k = 0;; k += W1_C) {                                      // (left by `break` at the last step)
             const int nc = min(W1_C, nt - k);                              // tile columns of this step
-            const int jend = (W1_CARRY && k > 0) ? k - W1_C : k;           // the sweep reads tile columns j < jend from the workspace
-            const int kl = jend - 1;
+            const int kl = k - 1;
+            // (not used, and not to be tidied away: a left-over of the removed resident-last-block variant.  Without this early k + W1_C
+            // hipcc emits other code for the kernel -- same registers, no spills, 8 bytes longer, schedule of the step moved (compiled both
+            // ways) -- so the line stays, and the kernel byte for byte the one that was measured)
             const bool last_step = k + W1_C >= nt;
+            (void)last_step;
             W1_FRESH_LANE();
             // ---- the diagonal block: T_(k+i)(k+c) = A - sum_{j<k} L_(k+i)j L_(k+c)j^T, tile d = i (i + 1) / 2 + c, one sweep over j;
             //      the forward-solve sums  part_c = sum_{j<k} L_(k+c)j z_j  from the same operands ----
             const double* rrow[W1_C];
 #pragma unroll
             for (int i = 0; i < W1_C; ++i) rrow[i] = Lt + W1_TILE(k + min(i, nc - 1), 0);
-#if !W1_CARRY
             d4 tacc[W1_NDT];
             double part[W1_C];
-#endif
             d4 op[2][W1_C];
 #pragma unroll
             for (int i = 0; i < W1_C; ++i) op[0][i] = op[1][i] = d4{0.0, 0.0, 0.0, 0.0};
-            if (jend > 0) {
+            if (k > 0) {
 #pragma unroll
                 for (int i = 0; i < W1_C; ++i) op[0][i] = mf_img_load(rrow[i], lane);
             }
-#if !W1_CARRY
-            {
-                d4 cy[W1_C][4];   // (never read)
-                W1_BLOCK_INIT(k, nc, false);
-            }
-#endif
-            for (int j = 0; j < jend; j += 2) {
+            W1_BLOCK_INIT(k, nc);
+            for (int j = 0; j < k; j += 2) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int jn = min(j + h + 1, kl);
 #pragma unroll
-                    for (int i = 0; i < W1_C; ++i) op[h ^ 1][i] = mf_img_load(rrow[i] + (size_t)W1_JX(jn) * MF_IMG, lane);
+                    for (int i = 0; i < W1_C; ++i) op[h ^ 1][i] = mf_img_load(rrow[i] + (size_t)jn * MF_IMG, lane);
 #pragma unroll
                     for (int d = 0; d < W1_NDT; ++d) {
                         const int bi = d >= 6 ? 3 : d >= 3 ? 2 : d >= 1 ? 1 : 0, bc = d - bi * (bi + 1) / 2;
@@ -486,21 +399,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
             d4 Lb[W1_C * (W1_C - 1) / 2];
 #pragma unroll
             for (int q = 0; q < W1_C * (W1_C - 1) / 2; ++q) Lb[q] = d4{0.0, 0.0, 0.0, 0.0};
-            // (W1_LASTRES: the last step's block never reaches the workspace -- its tiles go into the backward solve as registers, its
-            // L_cc^-T images are read back transposed from the L_cc^-1 images in LDS)
-            const bool keep = lastres && last_step;
-            // (W1_LASTRES_NOSTORE: the block's tiles and L_cc^-T are not even written -- 10 image writes less, but the conditional stores
-            // cost the chain 100 spilled VGPRs; by default only the READS of the backward solve go)
-#ifndef W1_LASTRES_NOSTORE
-#define W1_LASTRES_NOSTORE 0
-#endif
-            const bool skip_store = W1_LASTRES_NOSTORE && keep;
-#if W1_CMASK
-#define W1_DIAG(Wt, c_) mf_diag_factor_c(Wt, rsbuf, LinvC + (c_) * MF_IMG, skip_store ? nullptr : LinvTg + (size_t)(k + (c_)) * MF_IMG, ptol, lane)
-#else
-#define W1_DIAG(Wt, c_) mf_diag_factor<true>(Wt, rsbuf, LinvC + (c_) * MF_IMG, LinvTg + (size_t)(k + (c_)) * MF_IMG, ptol, lane)
-#endif
-            bool ok = W1_DIAG(tacc[0], 0);
+            bool ok = mf_diag_factor_c(tacc[0], rsbuf, LinvC, LinvTg + (size_t)k * MF_IMG, ptol, lane);
             W1_LDS_SYNC();
             if (g.export_factor) mf_img_store(Lt + W1_TILE(k, k), lane, mf_img_load(LinvC, lane));
 #pragma unroll
@@ -514,20 +413,16 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                         const d4 lvc = mf_img_load(LinvC + c * MF_IMG, mf_opaque(lane));
                         const d4 L = w1_trsm(lvc, Tt);                     // operand image of L_(k+i)(k+c)
                         Lb[i * (i - 1) / 2 + c] = L;
-                        if (!skip_store) W1_STORE_TILE(Lt + W1_TILE(k + i, k + c), lane, L);
+                        mf_img_store(Lt + W1_TILE(k + i, k + c), lane, L);
                     }
                     d4 Dii = tacc[i * (i + 1) / 2 + i];
 #pragma unroll
                     for (int c = 0; c < i; ++c) Dii = w1_mfma4_neg(Lb[i * (i - 1) / 2 + c], Lb[i * (i - 1) / 2 + c], Dii);
-                    ok = W1_DIAG(Dii, i);
+                    ok = mf_diag_factor_c(Dii, rsbuf, LinvC + i * MF_IMG, LinvTg + (size_t)(k + i) * MF_IMG, ptol, lane);
                     W1_LDS_SYNC();
                     if (g.export_factor) mf_img_store(Lt + W1_TILE(k + i, k + i), lane, mf_img_load(LinvC + i * MF_IMG, mf_opaque(lane)));
                 }
             }
-#undef W1_DIAG
-#if defined(W1_EXP_HOT) || defined(W1_EXP_NOPASSTRSM) || defined(W1_EXP_NOBACK)
-            ok = true;
-#endif
             if (!ok) { bad = true; break; }
             W1_STAMP(3);
             W1_FRESH_LANE();
@@ -564,46 +459,16 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
             W1_STAMP(4);
             const int rows_tot = nt - (k + nc);
             if (rows_tot == 0) {
-                // the last step: no rows below its block.  (The loop's only regular exit: values kept for the backward solve are live on
-                // this edge alone, not across the row passes of the earlier steps.)
-                if (keep) {
-#if !defined(W1_EXP_NOBACK)
-                    // W1_LASTRES: the last four columns of the backward solve right here, from the block's tiles in registers and the
-                    // L_cc^-1 images in LDS read transposed (tile (k + 1 + t, k) of column kk from the end is block tile
-                    // (4 - kk + t, 3 - kk)) -- nothing of the last block is written to or read from the workspace, and nothing of it
-                    // is live beyond this branch
-                    W1_FRESH_LANE();
-                    d4 pa0 = d4{0.0, 0.0, 0.0, 0.0};
-                    w1_static_for<0, NLAST>([&](auto P) __attribute__((always_inline)) {
-                        constexpr int q = decltype(P)::value;
-                        constexpr int kk = w1_stream_col(q), t = q - kk * (kk + 1) / 2;
-                        d4 img;
-                        if constexpr (t < kk) {
-                            constexpr int bi = W1_C - kk + t, bc = W1_C - 1 - kk;
-                            img = Lb[bi * (bi - 1) / 2 + bc];
-                        } else {
-                            const double* Mi = LinvC + (W1_C - 1 - kk) * MF_IMG;
-#pragma unroll
-                            for (int s_ = 0; s_ < 4; ++s_) img[s_] = Mi[mf_img_rc(lg + 4 * s_, lr)];
-                        }
-                        bw_step(P, img, pa0);
-                    });
-#endif
-                } else {
-                    __syncthreads();   // the block's tiles are in the workspace before the backward solve reads them back
-                }
+                // the last step: no rows below its block (the loop's only regular exit)
+                __syncthreads();   // the block's tiles are in the workspace before the backward solve reads them back
                 break;
             }
             if (k > 0) __syncthreads();     // the chain's tiles are in the workspace before the row passes read them back
             // ---- rows k + 4 .. nt - 1 (rows below a block exist only when the block has all four columns), FOUR per pass: update the
             //      sixteen accumulators over j < k, then column by column  T_r(k+c) -= sum_{c2<c} L_r(k+c2) L_(k+c)(k+c2)^T,
-            //      L_r(k+c) = T L_cc^-T.  The pass of the NEXT block's rows (first_row 0) runs LAST and its result tiles stay in cy for
-            //      the next step's block (W1_CARRY). ----
+            //      L_r(k+c) = T L_cc^-T.  The pass of the NEXT block's rows (first_row 0) runs LAST. ----
             const int npass = (rows_tot + 3) / 4;      // (a descending loop makes hipcc spill 90 more registers: the passes run 4, 8, .., then 0)
             const int klp = k - 1;
-#if W1_CARRY
-            d4 cy[W1_C][4];                            // the accumulators of a pass; after the loops: the tiles of the pass that ran last
-#endif
             if (k == 0) {
                 // Step 0 has no update loop, so its registers are free: the block's lower tiles stay resident (no reload from the
                 // workspace -- at eight patches per CU those reloads miss L2) and four independent TRSM chains interleave.
@@ -611,9 +476,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                     const int first_row0 = (pi_ + 1 < npass) ? 4 * (pi_ + 1) : 0;
                     const int np4 = min(4, rows_tot - first_row0);
                     W1_FRESH_LANE();
-#if !W1_CARRY
-                    d4 cy[W1_C][4];
-#endif
+                    d4 cy[W1_C][4];                    // the accumulators of a pass
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int r_ = W1_C + first_row0 + min(t, np4 - 1);       // (t >= np4: a copy of the last row, never stored)
@@ -634,7 +497,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
 #pragma unroll
                             for (int c2 = 0; c2 < c; ++c2) cy[c][t] = w1_mfma4_neg(Lb[c * (c - 1) / 2 + c2], cy[c2][t], cy[c][t]);
                             cy[c][t] = w1_trsm(lv, cy[c][t]);
-                            if (t < np4) W1_STORE_TILE(Lt + W1_TILE(W1_C + first_row0 + t, c), lane, cy[c][t]);
+                            if (t < np4) mf_img_store(Lt + W1_TILE(W1_C + first_row0 + t, c), lane, cy[c][t]);
                         }
                     }
                     W1_STAMP(7);
@@ -650,9 +513,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                     const int first_row = (pi_ + 1 < npass) ? 4 * (pi_ + 1) : 0;
                     const int np4 = min(4, rows_tot - first_row);
                     W1_FRESH_LANE();
-#if !W1_CARRY
-                    d4 cy[W1_C][4];
-#endif
+                    d4 cy[W1_C][4];                    // the accumulators of a pass
                     int rr[4];
                     const double* rw_[4];
 #pragma unroll
@@ -664,7 +525,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
 #pragma unroll
                     for (int c = 0; c < W1_C; ++c) A2[0][c] = mf_img_load(rrow[c], lane);
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) B[t] = W1_LOAD_ROWOP(rw_[t], lane);
+                    for (int t = 0; t < 4; ++t) B[t] = mf_img_load(rw_[t], lane);
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         d4 gv[W1_C];
@@ -683,13 +544,13 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
         /* (the scheduling barriers pin the requests where they are written: left alone, hipcc sinks every one of them to its  \
            first use -- request, s_waitcnt vmcnt(0), MFMA -- and the prefetch is gone) */                              \
         if (PREFETCH) {                                                                                              \
-            _Pragma("unroll") for (int c = 0; c < W1_C; ++c) A2[(st) ^ 1][c] = mf_img_load(rrow[c] + (size_t)W1_JX(jn) * MF_IMG, lane); \
+            _Pragma("unroll") for (int c = 0; c < W1_C; ++c) A2[(st) ^ 1][c] = mf_img_load(rrow[c] + (size_t)(jn) * MF_IMG, lane); \
         }                                                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
         _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                              \
             _Pragma("unroll") for (int c = 0; c < W1_C; ++c) cy[c][t] = w1_mfma4_neg(A2[st][c], B[t], cy[c][t]);      \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
-            if (PREFETCH) B[t] = W1_LOAD_ROWOP(rw_[t] + (size_t)W1_JX(jn) * MF_IMG, lane);                           \
+            if (PREFETCH) B[t] = mf_img_load(rw_[t] + (size_t)(jn) * MF_IMG, lane);                                    \
             else {     /* the last j: the block's lower tiles for the TRSMs take the place of the operands that are done */ \
                 if (t < 3) Lq[t] = mf_img_load(Lt + W1_TILE(k + (t == 0 ? 1 : 2), k + (t == 2 ? 1 : 0)), lane);      \
                 else {                                                                                               \
@@ -715,25 +576,15 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                         const d4 lv = mf_img_load(LinvC + c * MF_IMG, mf_opaque(lane));
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
-#ifndef W1_EXP_NOPASSTRSM      // (diagnostic: what the TRSM chains of the row passes cost -- stores only)
 #pragma unroll
                             for (int c2 = 0; c2 < c; ++c2) cy[c][t] = w1_mfma4_neg(Lq[c * (c - 1) / 2 + c2], cy[c2][t], cy[c][t]);
                             cy[c][t] = w1_trsm(lv, cy[c][t]);
-#endif
-                            if (t < np4) W1_STORE_TILE(Lt + W1_TILE(rr[t], k + c), lane, cy[c][t]);
+                            if (t < np4) mf_img_store(Lt + W1_TILE(rr[t], k + c), lane, cy[c][t]);
                         }
                     }
                     W1_STAMP(7);
                 }
             }
-#if W1_CARRY
-            // ---- the next step's block, while the tiles of its rows over this step's columns are in registers ----
-            W1_FRESH_LANE();
-            {
-                const int kn = k + W1_C, nbn = min(W1_C, nt - kn);
-                W1_BLOCK_INIT(kn, nbn, true);
-            }
-#endif
             __syncthreads();   // the column block is in the workspace (this wave's own stores, read back by its next sweep and passes)
             W1_STAMP(8);
         }
@@ -748,7 +599,6 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
             return;
         }
 
-#ifndef W1_EXP_NOBACK
         // ---- backward solve L^T alpha = z, tile columns from the last to the first; alpha replaces z in place ----
         // Column k: w_k = sum_{i>k} L_ik^T alpha_i on the VALU (the products contract over the ROW index, which the image layout
         // cannot feed to an MFMA) with the transposing DPP row reduction, then alpha_k = L_kk^-T (z_k - w_k): four MFMAs.
@@ -770,33 +620,24 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                 const double* ad = (t < kk) ? Lt + W1_TILE(kq + 1 + t, kq) : LinvTg + (size_t)kq * MF_IMG;
                 return kk < nt ? ad : Lt;
             };
-            // W1_LASTRES: the first NLAST positions -- the last block -- were consumed where the factorization ended; the stream starts
-            // behind them
-            const int bw_start = lastres ? NLAST : 0;
-            w1_static_for<0, NLAST + W1_BW>([&](auto P) __attribute__((always_inline)) {
+            w1_static_for<0, W1_BW>([&](auto P) __attribute__((always_inline)) {
                 constexpr int q = decltype(P)::value;
-                if constexpr (q < SLEN) {
-                    if (q >= bw_start && q < bw_start + W1_BW) win[q % W1_BW] = W1_LOAD_BACK(stream_addr(P), lane);
-                }
+                win[q] = mf_img_load_nt(stream_addr(P), lane);
             });
             d4 pa = d4{0.0, 0.0, 0.0, 0.0};
             w1_static_for<0, SLEN>([&](auto P) __attribute__((always_inline)) {
                 constexpr int q = decltype(P)::value;
-                if (q >= NLAST || q >= bw_start) {
-                    bw_step(P, win[q % W1_BW], pa);
-                    if constexpr (q + W1_BW < SLEN) {
-                        win[q % W1_BW] = W1_LOAD_BACK(stream_addr(std::integral_constant<int, q + W1_BW>{}), lane);
-                    }
+                bw_step(P, win[q % W1_BW], pa);
+                if constexpr (q + W1_BW < SLEN) {
+                    win[q % W1_BW] = mf_img_load_nt(stream_addr(std::integral_constant<int, q + W1_BW>{}), lane);
                 }
             });
         }
-#endif
         W1_STAMP(9);
         double* av = zv;
         if (A.alpha_out)
             for (int i = lane; i < n; i += 64) A.alpha_out[o + i] = av[i] * g.a_out;      // (unit scale: the weights of K are a' / sigma_f^2)
 
-#ifndef W1_EXP_NOPRED
         // ---- predictive mean ----
         W1_FRESH_LANE();
         if (m <= 0) {
@@ -888,7 +729,6 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                 fs[p] = sfp * s_;
             }
         }
-#endif
         if (lane == 0 && A.status) A.status[patch] = GPC_STATUS_OK;
 #ifdef W1_STAMPS
         W1_STAMP(10);
@@ -962,9 +802,6 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
         GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * W1_NPH, ctx->stream));
     }
 #endif
-    // (diagnostic: GPC_W1_LDS_PAD bytes of unused dynamic LDS per workgroup cap the workgroups resident on a CU)
-    const char* pad_e = getenv("GPC_W1_LDS_PAD");
-    const size_t pad = pad_e ? (size_t)atoi(pad_e) : 0;
     for (int base = 0; base < a.P; base += grid) {
         // a launch works on patches base .. base + cnt - 1: the kernel's patch index is its workgroup index; `off`, f*, V* and status
         // are passed shifted (off[] holds absolute point offsets, so x, y and alpha stay as they are)
@@ -974,8 +811,8 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
         g.a.off = a.off + base;
         g.a.f_star = a.f_star ? a.f_star + (size_t)base * a.ny * a_in.m : nullptr;
         g.a.status = a.status ? a.status + base : nullptr;
-        if (npad == 256) hipLaunchKernelGGL((dense_w1_kernel<256>), dim3(cnt), dim3(64), pad, ctx->stream, g);
-        else hipLaunchKernelGGL((dense_w1_kernel<W1_NPAD_MAX>), dim3(cnt), dim3(64), pad, ctx->stream, g);
+        if (npad == 256) hipLaunchKernelGGL((dense_w1_kernel<256>), dim3(cnt), dim3(64), 0, ctx->stream, g);
+        else hipLaunchKernelGGL((dense_w1_kernel<W1_NPAD_MAX>), dim3(cnt), dim3(64), 0, ctx->stream, g);
         GPC_HIP(ctx, hipGetLastError());
         if (v_star) {
             DenseArgs av = g.a;

@@ -406,7 +406,7 @@ static int dense_dispatch_locked(gpc_ctx* ctx, DenseArgs& a)
             return dense_mfma_launch(ctx, a);                                                               // one shape for the whole batch
         // (a batch whose patches all have n_max points -- P n_max == n_total: every n_i <= n_max and they add up to n_total -- has one
         // size class and the host knows it: no classification, no empty class launches waiting for a CU beside the tiled kernel)
-        const bool uniform = (long long)a.P * a.n_max == (long long)a.n_total && !getenv("GPC_NO_UNIFORM");
+        const bool uniform = (long long)a.P * a.n_max == (long long)a.n_total;
         if (!a.v_star && a.n_max <= GPC_MAX_POINTS && !no_split && !(uniform && a.n_max > 17 * 16)) {
             const bool nt17 = a.ny == 1 && !getenv("GPC_NO_NT17");
             const bool need_big = !(nt17 && a.n_max <= 17 * 16);
@@ -433,28 +433,24 @@ static int dense_dispatch_locked(gpc_ctx* ctx, DenseArgs& a)
             GPC_HIP(ctx, hipGetLastError());
             // The classes are independent: they run on three streams (forked from and joined to the context's), so that
             // the tail of one kernel -- its last workgroups running on a mostly idle chip -- fills with the next one's work.
-            const bool fork = !getenv("GPC_NO_FORK");
             hipStream_t main_s = ctx->stream;
-            bool forked = false;
             // an error after the fork must not leave work (or the caller's buffers) in flight on the side streams
             auto bail = [&](int code) {
                 ctx->stream = main_s;
-                if (forked) { (void)hipStreamSynchronize(ctx->s_in); (void)hipStreamSynchronize(ctx->s_out); }
+                (void)hipStreamSynchronize(ctx->s_in);
+                (void)hipStreamSynchronize(ctx->s_out);
                 return code;
             };
-            if (fork) {
-                rc = gpc_aux_streams(ctx);
-                if (rc != GPC_OK) return rc;
-                GPC_HIP(ctx, hipEventRecord(ctx->ev[0][13], main_s));
-                GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_in, ctx->ev[0][13], 0));
-                GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_out, ctx->ev[0][13], 0));
-                forked = true;
-            }
+            rc = gpc_aux_streams(ctx);
+            if (rc != GPC_OK) return rc;
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[0][13], main_s));
+            GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_in, ctx->ev[0][13], 0));
+            GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_out, ctx->ev[0][13], 0));
             // largest patches first: the tiled kernel's workgroups are the long ones
             if (need_big) {
                 DenseArgs b = a;
                 b.sel = sel2; b.sel_count = counts + 2;
-                if (fork) ctx->stream = ctx->s_out;
+                ctx->stream = ctx->s_out;
                 rc = dense_big_launch(ctx, b, grid_b);
                 ctx->stream = main_s;
                 if (rc != GPC_OK) return bail(rc);
@@ -475,7 +471,7 @@ static int dense_dispatch_locked(gpc_ctx* ctx, DenseArgs& a)
                 s.n_max = 17 * 16;
                 s.sel = sel1; s.sel_count = counts + 1;
                 s.P = c1;
-                if (fork) ctx->stream = ctx->s_in;
+                ctx->stream = ctx->s_in;
                 rc = dense_mfma_launch(ctx, s);
                 if (rc == GPC_OK) rc = overflow(s, c1, 1);
                 ctx->stream = main_s;
@@ -499,12 +495,10 @@ static int dense_dispatch_locked(gpc_ctx* ctx, DenseArgs& a)
                 rc = overflow(s, 0, 0);
                 if (rc != GPC_OK) return bail(rc);
             }
-            if (fork) {
-                GPC_HIP(ctx, hipEventRecord(ctx->ev[1][13], ctx->s_in));
-                GPC_HIP(ctx, hipEventRecord(ctx->ev[2][13], ctx->s_out));
-                GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][13], 0));
-                GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][13], 0));
-            }
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[1][13], ctx->s_in));
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[2][13], ctx->s_out));
+            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][13], 0));
+            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][13], 0));
             ctx->last_dense_kernel = !need_big ? "dense_mfma_nt16 + dense_mfma_nt17" : nt17 ? "dense_mfma_nt16 + dense_mfma_nt17 + dense_mfma_big"
                                                                                              : "dense_mfma_nt16 + dense_mfma_big";
             return rc;
@@ -592,8 +586,7 @@ private:
     CopyPool()
     {
         unsigned hc = std::thread::hardware_concurrency();
-        int n = (int)std::min(4u, hc > 2 ? hc / 2 : 1u);      // measured on the 16-CPU share of a 1-GPU box: 4 threads 4.35 ms per C2 call, 8: 6.6, 12: 4.4
-        if (const char* e = getenv("GPC_COPY_THREADS")) n = std::max(1, atoi(e));
+        const int n = (int)std::min(4u, hc > 2 ? hc / 2 : 1u);      // measured on the 16-CPU share of a 1-GPU box: 4 threads 4.35 ms per C2 call, 8: 6.6, 12: 4.4
         parts_ = n;
         for (int t = 1; t < n; ++t) th_.emplace_back([this, t] { run(t); });
     }

@@ -2067,7 +2067,7 @@ static size_t sp_pred_lds(int ld, bool sigma, bool fast)
 // The predict launches: the two instances of the small-basis kernel (b <= 16, 17 .. 32) and sparse_predict_kernel for the rest (it skips what
 // they took: A.small_max).  The three work on disjoint patches, and at the reference's defaults each is a short launch that ends in a tail of a few
 // long patches: they run SIDE BY SIDE on the context's stream and its two copy streams (forked and joined with events; the streams exist since
-// gpc_ctx_create).  GPC_SPARSE_NO_SMALL_PREDICT=1: everything through the regular kernel; GPC_SPARSE_PREDICT_NO_FORK=1: one after the other.
+// gpc_ctx_create).
 static int sp_predict_launch(gpc_ctx* ctx, SpPredParams& A, int grid, size_t lds)
 {
     A.small_max = -1;
@@ -2079,7 +2079,7 @@ static int sp_predict_launch(gpc_ctx* ctx, SpPredParams& A, int grid, size_t lds
     }
     // (with sigma only: measured at the reference's defaults, 32768 patches -- sigma-predict 1.14 -> 0.84 ms; the mean-only launches are too
     // short to pay for the fork and join, 0.23 -> 0.28 ms)
-    const bool fork = ctx->s_in && ctx->s_out && A.sigma != nullptr && !getenv("GPC_SPARSE_PREDICT_NO_FORK");
+    const bool fork = ctx->s_in && ctx->s_out && A.sigma != nullptr;
     hipStream_t s32 = fork ? ctx->s_in : main_s, sreg = fork ? ctx->s_out : main_s;
     // (the third launch goes to the context's OWN stream: the legacy default stream does not overlap its kernels with another stream's, and
     // a caller's stream may share a hardware queue with s_in or s_out -- gpc_api.hip, dense_host; own_stream, s_in and s_out never do)
@@ -2090,7 +2090,7 @@ static int sp_predict_launch(gpc_ctx* ctx, SpPredParams& A, int grid, size_t lds
         GPC_HIP(ctx, hipStreamWaitEvent(sreg, ctx->ev[0][14], 0));
         if (s16 != main_s) GPC_HIP(ctx, hipStreamWaitEvent(s16, ctx->ev[0][14], 0));
     }
-    const int waves = std::min(A.P, ctx->num_cus * (getenv("GPC_SP_SMALL_WAVES") ? atoi(getenv("GPC_SP_SMALL_WAVES")) : 16));
+    const int waves = std::min(A.P, ctx->num_cus * 16);
     const size_t l16 = sizeof(double) * (size_t)(64 + 16 * 16 + 5 * 16), l32 = sizeof(double) * (size_t)(64 + 32 * 32 + 5 * 32);
     A.small_max = 32;
     // (the regular kernel first: its few patches are the longest)
@@ -2260,7 +2260,6 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
     int per_cu = (int)((160u * 1024u) / lds);
     const int per_cu_max = 2 * SP_THREADS / nth;
     per_cu = per_cu > per_cu_max ? per_cu_max : (per_cu < 1 ? 1 : per_cu);
-    if (const char* e = getenv("GPC_SPARSE_PER_CU")) per_cu = std::max(1, atoi(e));   // diagnostic: resident-state experiments
     int grid = std::min(g->P, ctx->num_cus * per_cu);
     A.start_it = nullptr;
     A.done_it = nullptr;
@@ -2280,8 +2279,6 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
         if (gauss && !getenv("GPC_SPARSE_NO_ROWS")) {
             constexpr int G = 16, R = 64 / G;
             const size_t lds_r = sizeof(double) * (size_t)(64 + R * (2 * G * G + 4 * G + 16));
-            int per_cu_r = std::min(8, (int)((160u * 1024u) / lds_r));
-            if (const char* e = getenv("GPC_SPARSE_ROWS_PER_CU")) per_cu_r = std::max(1, std::min(per_cu_r, atoi(e)));   // diagnostic
             A.done_it = g->done_it;
             if (!getenv("GPC_SPARSE_NO_LIST")) {
                 A.list = L[0];
@@ -2291,10 +2288,9 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
             const int waves = (g->P + R - 1) / R;
             // (a wave per four patches, placed by the hardware as slots come free: patches that leave the phase early end their wave early,
             // and persistent waves striding over the batch carried that imbalance to the end -- 1.93 -> 1.88 ms for the colour GP's pass,
-            // level for the depth GP; GPC_SPARSE_ROWS_PERSISTENT=1: eight waves per CU striding, as before)
-            const int grid_r = getenv("GPC_SPARSE_ROWS_PERSISTENT") ? std::min(waves, ctx->num_cus * per_cu_r) : waves;
-            if (A.ny == 1) hipLaunchKernelGGL((sparse_add_rows_kernel<G, 1>), dim3(grid_r), dim3(64), lds_r, ctx->stream, A);
-            else hipLaunchKernelGGL((sparse_add_rows_kernel<G, 3>), dim3(grid_r), dim3(64), lds_r, ctx->stream, A);
+            // level for the depth GP)
+            if (A.ny == 1) hipLaunchKernelGGL((sparse_add_rows_kernel<G, 1>), dim3(waves), dim3(64), lds_r, ctx->stream, A);
+            else hipLaunchKernelGGL((sparse_add_rows_kernel<G, 3>), dim3(waves), dim3(64), lds_r, ctx->stream, A);
             GPC_HIP(ctx, hipGetLastError());
             A.start_it = g->done_it;
         }
@@ -2326,7 +2322,6 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
         const size_t lds_s = sp_add_lds_small();
         int per_cu_s = (int)((160u * 1024u) / lds_s);
         per_cu_s = per_cu_s > 16 ? 16 : per_cu_s;
-        if (const char* e = getenv("GPC_SPARSE_SMALL_PER_CU")) per_cu_s = std::max(1, std::min(per_cu_s, atoi(e)));   // diagnostic: occupancy experiments
         A.done_it = g->done_it;
         A.ticket_slot = 1;
         if (!rows2 && A.list) {

@@ -134,3 +134,20 @@ def test_staging_copy_is_safe_from_two_threads(capi):
         t.join(timeout=120)
     assert sorted(done) == [1, 2, 3], "a copy never returned (lost wake-up)"
     assert not bad, bad
+
+
+def test_design_switch_table_lists_every_getenv_of_the_library():
+    """DESIGN.md section "Switches" is the one list of the environment switches the library reads: the GPC_* names inside
+    getenv("...") calls of csrc/*.hip and csrc/*.h and the names in the first column of that table are the same set."""
+    import glob
+    csrc = os.path.join(ROOT, "gp_compressor_amd", "csrc")
+    read = set()
+    for f in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        read |= set(re.findall(r'getenv\(\s*"(GPC_[A-Z0-9_]+)"\s*\)', open(f).read()))
+    assert len(read) > 20, "no getenv calls parsed"
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = re.search(r"^## [0-9a-z]+\. Switches\n(.*?)(?=^## )", design, flags=re.S | re.M)
+    assert sec, "DESIGN.md has no section \"Switches\""
+    rows = re.findall(r"^\| `(GPC_[A-Z0-9_]+)` \|", sec.group(1), flags=re.M)
+    assert len(rows) == len(set(rows)), sorted(r for r in set(rows) if rows.count(r) > 1)
+    assert set(rows) == read, {"only in the sources": sorted(read - set(rows)), "only in the table": sorted(set(rows) - read)}

@@ -36,7 +36,7 @@ def main():
         c = SW.draw(rng, synth)
     base = SW.run(capi, ctx, c, "GPC_SPARSE_NO_SMALL")
     report = {}
-    for env in (None, "GPC_SPARSE_NO_ROWS2", "GPC_SPARSE_NO_MID", "GPC_SPARSE_NO_ROWS", "GPC_SPARSE_NO_LIST", "GPC_SPARSE_ROWS_PERSISTENT",
+    for env in (None, "GPC_SPARSE_NO_ROWS2", "GPC_SPARSE_NO_MID", "GPC_SPARSE_NO_ROWS", "GPC_SPARSE_NO_LIST",
                 "GPC_SPARSE_NO_ROWS2+GPC_SPARSE_NO_MID"):
         cur = SW.run(capi, ctx, c, env, predict=synth.grid(0.15, 12))
         report[env or "default"] = ("OK" if SW.same(cur, base, c["P"]) else "DIFF") + ("" if cur[3] else " + predict kernels disagree")
