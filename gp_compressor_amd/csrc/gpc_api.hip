@@ -10,34 +10,6 @@
 #include "gpc_device.h"
 #include "gpc_internal.h"
 
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(gpc_ctx* ctx, size_t bytes)
-    {
-        if (bytes == 0) bytes = 8;
-        GPC_HIP(ctx, hipMalloc(&p, bytes));
-        return GPC_OK;
-    }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-int host_n_max(gpc_ctx* ctx, int P, const int32_t* off, int* n_max, int* n_total)
-{
-    if (P > 0 && off[0] != 0) return gpc_fail(ctx, GPC_EINVAL, "off[0] must be 0");
-    int mx = 0;
-    for (int i = 0; i < P; ++i) {
-        int n = off[i + 1] - off[i];
-        if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "off must be non-decreasing (patch %d)", i);
-        mx = std::max(mx, n);
-    }
-    *n_max = mx;
-    *n_total = P > 0 ? off[P] : 0;
-    return GPC_OK;
-}
-}  // namespace
-
 extern "C" {
 
 int gpc_version(void) { return GPC_VERSION; }
@@ -671,7 +643,7 @@ static int dense_host(gpc_ctx* ctx, const gpc_params* params, int P, const int32
     if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
     if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
     int n_max = 0, n_total = 0;
-    int rc = host_n_max(ctx, P, off, &n_max, &n_total);
+    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
     if (rc != GPC_OK) return rc;
     rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, ny, m, f_star);
     if (rc != GPC_OK) return rc;
@@ -956,46 +928,29 @@ int gpc_dense_irls_fit_predict(gpc_ctx* ctx, const gpc_params* params, const gpc
         m = sz * sz;
     }
     int n_max = 0, n_total = 0;
-    int rc = host_n_max(ctx, P, off, &n_max, &n_total);
+    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
     if (rc != GPC_OK) return rc;
     rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
     if (rc != GPC_OK) return rc;
     if (P == 0) return GPC_OK;
+    if (!grid && m && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
     GPC_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf d_off, d_x0, d_x1, d_y, d_xs0, d_xs1, d_f, d_al, d_fh, d_it, d_st;
-    const size_t N = (size_t)n_total;
-    if ((rc = d_off.alloc(ctx, sizeof(int32_t) * (P + 1))) || (rc = d_x0.alloc(ctx, 8 * N)) || (rc = d_x1.alloc(ctx, 8 * N)) ||
-        (rc = d_y.alloc(ctx, 8 * N)) || (rc = d_f.alloc(ctx, 8 * (size_t)P * m)) || (rc = d_al.alloc(ctx, 8 * N)) ||
-        (rc = d_fh.alloc(ctx, 8 * N)) || (rc = d_it.alloc(ctx, sizeof(int32_t) * P)) || (rc = d_st.alloc(ctx, sizeof(int32_t) * P)))
-        return rc;
-    if (!grid && ((rc = d_xs0.alloc(ctx, 8 * (size_t)m)) || (rc = d_xs1.alloc(ctx, 8 * (size_t)m)))) return rc;
-    hipStream_t s = gpc_stream_of(ctx);
-    GPC_HIP(ctx, hipMemcpyAsync(d_off.p, off, sizeof(int32_t) * (P + 1), hipMemcpyHostToDevice, s));
-    if (N) {
-        GPC_HIP(ctx, hipMemcpyAsync(d_x0.p, x0, 8 * N, hipMemcpyHostToDevice, s));
-        GPC_HIP(ctx, hipMemcpyAsync(d_x1.p, x1, 8 * N, hipMemcpyHostToDevice, s));
-        GPC_HIP(ctx, hipMemcpyAsync(d_y.p, y, 8 * N, hipMemcpyHostToDevice, s));
-    }
-    if (!grid && m) {
-        if (!xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
-        GPC_HIP(ctx, hipMemcpyAsync(d_xs0.p, xs0, 8 * (size_t)m, hipMemcpyHostToDevice, s));
-        GPC_HIP(ctx, hipMemcpyAsync(d_xs1.p, xs1, 8 * (size_t)m, hipMemcpyHostToDevice, s));
-    }
-    rc = gpc_dense_irls_fit_predict_dev(ctx, params, irls, P, d_off.as<int32_t>(), n_max, n_total, d_x0.as<double>(), d_x1.as<double>(),
-                                        d_y.as<double>(), m, grid ? nullptr : d_xs0.as<double>(), grid ? nullptr : d_xs1.as<double>(),
-                                        res, sz, d_f.as<double>(), d_al.as<double>(), d_fh.as<double>(), d_it.as<int32_t>(),
-                                        d_st.as<int32_t>());
-    if (rc != GPC_OK) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    if (m) GPC_HIP(ctx, hipMemcpyAsync(f_star, d_f.p, 8 * (size_t)P * m, hipMemcpyDeviceToHost, s));
-    if (alpha_out && N) GPC_HIP(ctx, hipMemcpyAsync(alpha_out, d_al.p, 8 * N, hipMemcpyDeviceToHost, s));
-    if (fhat_out && N) GPC_HIP(ctx, hipMemcpyAsync(fhat_out, d_fh.p, 8 * N, hipMemcpyDeviceToHost, s));
-    if (iters) GPC_HIP(ctx, hipMemcpyAsync(iters, d_it.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost, s));
-    if (status) GPC_HIP(ctx, hipMemcpyAsync(status, d_st.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost, s));
-    GPC_HIP(ctx, hipStreamSynchronize(s));
-    return GPC_OK;
+    const size_t N = (size_t)n_total, Pz = (size_t)P, Pm = Pz * (size_t)m;
+    GpcStaging st(ctx, "gpc_dense_irls_fit_predict");
+    const int32_t* d_off = st.up(off, Pz + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
+    const double *d_xs0 = grid ? nullptr : st.up(xs0, (size_t)m), *d_xs1 = grid ? nullptr : st.up(xs1, (size_t)m);
+    double *d_f = st.out<double>(Pm), *d_al = st.out<double>(N), *d_fh = st.out<double>(N);
+    int32_t *d_it = st.out<int32_t>(Pz), *d_st = st.out<int32_t>(Pz);
+    if (st.ok())
+        st.rc = gpc_dense_irls_fit_predict_dev(ctx, params, irls, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res, sz, d_f, d_al,
+                                               d_fh, d_it, d_st);
+    st.down(f_star, d_f, Pm);
+    st.down(alpha_out, d_al, N);
+    st.down(fhat_out, d_fh, N);
+    st.down(iters, d_it, Pz);
+    st.down(status, d_st, Pz);
+    return st.finish();
 }
 
 __global__ void gpc_noise_eval_kernel(int model, double s20, int n, const double* y, const double* x, const double* sx, double* q, double* r)
@@ -1019,12 +974,11 @@ int gpc_noise_eval(gpc_ctx* ctx, int noise_model, double s20, int n, const doubl
     if (!y || !x || !sigma_x || !q || !r) return gpc_fail(ctx, GPC_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     GPC_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf d;
     const size_t nb = 8 * (size_t)n;
-    int rc = d.alloc(ctx, 5 * nb);
-    if (rc != GPC_OK) return rc;
-    char* b = d.as<char>();
     hipStream_t s = ctx->stream;
+    GpcStaging st(ctx, "gpc_noise_eval", s);   // (under ctx->mu: the stream is handed in)
+    char* b = st.out<char>(5 * nb);
+    if (!b) return st.finish();
     GPC_HIP(ctx, hipMemcpyAsync(b, y, nb, hipMemcpyHostToDevice, s));
     GPC_HIP(ctx, hipMemcpyAsync(b + nb, x, nb, hipMemcpyHostToDevice, s));
     GPC_HIP(ctx, hipMemcpyAsync(b + 2 * nb, sigma_x, nb, hipMemcpyHostToDevice, s));

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/gpc.h"
 
@@ -93,6 +94,89 @@ static inline hipStream_t gpc_stream_of(gpc_ctx* ctx)
     std::lock_guard<std::mutex> lk(ctx->mu);
     return ctx->stream;
 }
+
+// Checks a host `off` array of P patches (off[0] == 0, non-decreasing) and reports the largest patch and the number of points
+// (either may be nullptr).
+static inline int gpc_check_host_off(gpc_ctx* ctx, int P, const int32_t* off, int* n_max, int* n_total)
+{
+    if (P > 0 && off[0] != 0) return gpc_fail(ctx, GPC_EINVAL, "off[0] must be 0");
+    int mx = 0;
+    for (int i = 0; i < P; ++i) {
+        const int n = off[i + 1] - off[i];
+        if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "off must be non-decreasing (patch %d)", i);
+        mx = n > mx ? n : mx;
+    }
+    if (n_max) *n_max = mx;
+    if (n_total) *n_total = P > 0 ? off[P] : 0;
+    return GPC_OK;
+}
+
+// Device staging of a host-pointer entry point: the entry validates its arguments, then reads as a list of up() / out(), the
+// call of its _dev twin (`if (st.ok()) st.rc = ..._dev(...)`), a list of down() and `return st.finish()`.  The first failing HIP
+// call is remembered and every later call is a no-op (up / out then return nullptr).  finish() -- and the destructor, on an
+// early return -- synchronises the stream BEFORE it frees the buffers, so the entry is synchronous for its caller and no copy or
+// kernel in flight loses its memory.  Sizes are element counts.  The entry does not hold ctx->mu (the _dev twin takes it).
+struct GpcStaging {
+    gpc_ctx* ctx;
+    const char* entry;   // for the error text
+    hipStream_t stream;
+    hipError_t err = hipSuccess;
+    int rc = GPC_OK;     // what the _dev twin returned
+    std::vector<void*> bufs;
+    bool live = true;    // until release()
+
+    GpcStaging(gpc_ctx* c, const char* name, hipStream_t s) : ctx(c), entry(name), stream(s) {}
+    GpcStaging(gpc_ctx* c, const char* name) : GpcStaging(c, name, gpc_stream_of(c)) {}
+    GpcStaging(const GpcStaging&) = delete;
+    GpcStaging& operator=(const GpcStaging&) = delete;
+    ~GpcStaging() { release(); }
+
+    bool ok() const { return err == hipSuccess && rc == GPC_OK; }
+    // device buffer of n elements (at least 8 bytes), optionally zeroed
+    template <class T> T* out(size_t n, bool zero = false)
+    {
+        if (!ok()) return nullptr;
+        void* d = nullptr;
+        const size_t bytes = n * sizeof(T) > 8 ? n * sizeof(T) : 8;
+        if ((err = hipMalloc(&d, bytes)) != hipSuccess) return nullptr;
+        bufs.push_back(d);
+        if (zero) err = hipMemsetAsync(d, 0, bytes, stream);
+        return static_cast<T*>(d);
+    }
+    // ... filled from n host elements (no copy when h is nullptr or n == 0)
+    template <class T> T* up(const T* h, size_t n)
+    {
+        T* d = out<T>(n);
+        if (d && h && n) err = hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, stream);
+        return d;
+    }
+    // n elements back to the host (skipped when h is nullptr or n == 0, and after a failure)
+    template <class T> void down(T* h, const T* d, size_t n)
+    {
+        if (ok() && h && n) err = hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, stream);
+    }
+    // what has been downloaded so far is in host memory when this returns
+    void sync()
+    {
+        if (ok()) err = hipStreamSynchronize(stream);
+    }
+    void release()
+    {
+        if (!live) return;
+        live = false;
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (err == hipSuccess) err = e;
+        for (void* d : bufs) (void)hipFree(d);
+    }
+    // the _dev twin's code if it failed (with its own error text), else the staging's
+    int finish()
+    {
+        release();
+        if (rc != GPC_OK) return rc;
+        if (err != hipSuccess) return gpc_fail(ctx, err == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "%s: %s", entry, hipGetErrorString(err));
+        return GPC_OK;
+    }
+};
 
 // grow-only workspace; returns nullptr + sets error on failure.  Caller holds ctx->mu.
 static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)

@@ -130,48 +130,21 @@ int gpc_reproject(gpc_ctx* ctx, int P, int m, const int32_t* bv_count, const dou
     if (!xs0 || !xs1 || !f_star || !rotations || !means || !cloud) return gpc_fail(ctx, GPC_EINVAL, "xs0/xs1/f_star/rotations/means/cloud is NULL");
     if (c_star && !rgb_means) return gpc_fail(ctx, GPC_EINVAL, "c_star needs rgb_means");
     GPC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = gpc_stream_of(ctx);
-    const size_t Pm = (size_t)P * m;
-    void *d_bv = nullptr, *d_xs0 = nullptr, *d_xs1 = nullptr, *d_f = nullptr, *d_c = nullptr, *d_R = nullptr, *d_mu = nullptr,
-         *d_cm = nullptr, *d_cloud = nullptr, *d_n = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_bv, d_xs0, d_xs1, d_f, d_c, d_R, d_mu, d_cm, d_cloud, d_n})
-            if (p) (void)hipFree(p);
-    };
-    auto up = [&](void** d, const void* h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s);
-        return e;
-    };
-    hipError_t e = hipSuccess;
-    if (bv_count) e = up(&d_bv, bv_count, 4 * (size_t)P);
-    if (e == hipSuccess) e = up(&d_xs0, xs0, 8 * (size_t)m);
-    if (e == hipSuccess) e = up(&d_xs1, xs1, 8 * (size_t)m);
-    if (e == hipSuccess) e = up(&d_f, f_star, 8 * Pm);
-    if (e == hipSuccess && c_star) e = up(&d_c, c_star, 8 * Pm * 3);
-    if (e == hipSuccess) e = up(&d_R, rotations, 8 * (size_t)P * 9);
-    if (e == hipSuccess) e = up(&d_mu, means, 8 * (size_t)P * 3);
-    if (e == hipSuccess && c_star) e = up(&d_cm, rgb_means, 8 * (size_t)P * 3);
-    if (e == hipSuccess) e = hipMalloc(&d_cloud, sizeof(gpc_point_xyzrgb) * Pm);
-    if (e == hipSuccess) e = hipMalloc(&d_n, sizeof(int32_t));
-    if (e != hipSuccess) {
-        cleanup();
-        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_reproject: %s", hipGetErrorString(e));
-    }
-    int rc = gpc_reproject_dev(ctx, P, m, (const int32_t*)d_bv, (const double*)d_xs0, (const double*)d_xs1, (const double*)d_f,
-                               (const double*)d_c, (const double*)d_R, (const double*)d_mu, (const double*)d_cm,
-                               (gpc_point_xyzrgb*)d_cloud, (int32_t*)d_n);
-    if (rc == GPC_OK) {
-        e = hipMemcpyAsync(n_points, d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess && *n_points > 0)
-            e = hipMemcpy(cloud, d_cloud, sizeof(gpc_point_xyzrgb) * (size_t)*n_points, hipMemcpyDeviceToHost);
-    }
-    hipError_t e2 = hipStreamSynchronize(s);
-    cleanup();
-    if (rc != GPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return gpc_fail(ctx, GPC_EHIP, "gpc_reproject: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return GPC_OK;
+    const size_t Pz = (size_t)P, Pm = Pz * (size_t)m;
+    GpcStaging st(ctx, "gpc_reproject");
+    const int32_t* d_bv = bv_count ? st.up(bv_count, Pz) : nullptr;
+    const double *d_xs0 = st.up(xs0, (size_t)m), *d_xs1 = st.up(xs1, (size_t)m), *d_f = st.up(f_star, Pm);
+    const double* d_c = c_star ? st.up(c_star, Pm * 3) : nullptr;
+    const double *d_R = st.up(rotations, Pz * 9), *d_mu = st.up(means, Pz * 3);
+    const double* d_cm = c_star ? st.up(rgb_means, Pz * 3) : nullptr;
+    gpc_point_xyzrgb* d_cloud = st.out<gpc_point_xyzrgb>(Pm);
+    int32_t* d_n = st.out<int32_t>(1);
+    if (st.ok()) st.rc = gpc_reproject_dev(ctx, P, m, d_bv, d_xs0, d_xs1, d_f, d_c, d_R, d_mu, d_cm, d_cloud, d_n);
+    // the count first, then only that many records
+    st.down(n_points, d_n, 1);
+    st.sync();
+    if (st.ok() && *n_points > 0) st.down(cloud, d_cloud, (size_t)*n_points);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// sparse.hip -- batched online sparse GP (Csato-Opper) : sparse_gp<rbf_kernel, gaussian_noise> and
+// sparse.hip -- the ADD path of the batched online sparse GP (Csato-Opper) : sparse_gp<rbf_kernel, gaussian_noise> and
 // sparse_gp_field<rbf_kernel, gaussian_noise_3d> of the reference, one patch per workgroup.
 //
 // Follows /root/reference/src/sparse_gp.hpp:89-249 (add), :252-295 (delete_bv), :299-351 (predict) and the
@@ -13,24 +13,12 @@
 // trained GPs):  alpha [P][ny][ld], C [P][ld][ld], Q [P][ld][ld] column-major like Eigen, BV [P][ld][2] (AoS,
 // = Eigen 2 x b column-major), b [P], total_count [P];  ld = capacity + 1 rounded up to 16 (a full update may hold capacity+1
 // basis vectors until the deletion that follows it), or GPC_MAX_BV when capacity == -1.
+//
+// The predict / likelihood / train kernels are in sparse_predict.hip, the gpc_sparse_* entry points in sparse_api.hip.
+#include <algorithm>
 #include <cstdlib>
-#include <vector>
 
-#include "gpc_device.h"
-#include "gpc_internal.h"
-
-#define SP_THREADS 256
-
-struct gpc_sparse {
-    gpc_ctx* ctx;
-    gpc_params prm;
-    int P, ny, ld;
-    double *alpha, *C, *Q, *BV;
-    int32_t *b, *count, *stat;
-    int32_t* done_it;   // P: hand-over between the phases of an add call (allocated with the object)
-    int32_t* list;      // P + 4: work list of the phases after the rows phase, then its length and three ticket counters
-    uint8_t* trace;     // diagnostic (gpc_sparse_set_trace): device buffer for the decision bytes of the next add calls, or nullptr
-};
+#include "sparse_internal.h"
 
 struct SpState {
     double *alpha, *C, *Q, *BV;   // this patch
@@ -47,9 +35,6 @@ struct SpState {
 #define SP_BMAX 24   // resident block of the small-basis add kernel (see sparse_add_kernel)
 #endif
 #define SP_BMID 48   // ... and of its second instance, which takes the patches that have outgrown SP_BMAX (round 4)
-// kernel_function(X, X) = p(0) exp(-0.5/p(1) |X - X|^2) (src/sparse_gp.hpp:98, :316): p(0) for a finite X (X - X = +0, exp(-0) is exactly 1,
-// so finite data keeps its bits) and NaN when a coordinate is NaN or +-inf (X - X = NaN): no select, three operations.
-__device__ static __forceinline__ double sp_kstar(double sf, double x0, double x1) { return sf + ((x0 - x0) + (x1 - x1)); }
 
 // ---- block-wide helpers (all SP_NTH threads call) -------------------------------------------------------
 
@@ -1548,681 +1533,23 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
     }
 }
 
-struct SpPredParams {
-    gpc_params prm;
-    double c_exp;
-    int P, ny, ld, m, conf;
-    int fast;   // LDS holds a second [ld][SP_PC] buffer: V = C K by sp_ck_chunk
-    const double *xs0, *xs1;
-    const double *alpha, *C, *BV;
-    const int32_t* b;
-    double *f_star, *sigma;
-    int32_t* status_out;
-    const int32_t* stat;
-    // ragged form (gpc_sparse_predict_points): patch i predicts at ITS OWN points off[i] .. off[i+1]-1 of xs0/xs1 and writes rows
-    // off[i] .. of the output planes (plane stride n_total) -- predict_measurements(f, X_i, sigma) as the reference's training-set
-    // RMS block calls it (/root/reference/src/gp_compressor.cpp:303-315).  nullptr: the shared grid of load_compressed.
-    const int32_t* off;
-    int n_total;
-    int small_max;   // patches with at most this many basis vectors are the business of sparse_predict_small_kernel (-1: none)
-};
-
-#define SP_PC 32   // grid points per chunk of the sigma path
-
-// V = C K for a chunk of SP_PC = 32 points on the MFMA pipe: C (b x b, global, column-major) times K (b x 32, LDS).
-// v_mfma_f64_16x16x4_f64 with M = 16 rows of C, N = 16 points, K = 4 columns of C per instruction: the A operand of lane l
-// is C[i0 + (l & 15)][j0 + (l >> 4)] (one 8-byte global load per lane, 16 contiguous rows per column), the B operand is
-// K[j0 + (l >> 4)][p0 + (l & 15)] (one conflict-free LDS read).  Wave w owns the row tiles w, w+4, w+8, w+12 for both point
-// tiles (8 accumulators); the loads of the next K-step are issued before the MFMAs of the current one, unconditionally
-// (clamped addresses, masked values).  The result goes to LDS as Vc[row][point].  1300 MFMAs per chunk at b = 200.
-// (The first version had every (point, column-group) thread walk its own columns of C with one broadcast global load and one
-// LDS read per FMA: 1 TFLOP/s; a register-tiled VALU version was LDS-latency-bound with one wave per SIMD: 2.5 TFLOP/s.)
-typedef double sp_d4 __attribute__((ext_vector_type(4)));
-#define SP_RT 4   // row tiles per wave (4 waves x 4 x 16 rows = 256 = GPC_MAX_BV)
-__device__ static inline void sp_ck_chunk(const double* __restrict__ Cg, int ld, int b, const double* Kc, double* Vc)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lr = lane & 15, lg = lane >> 4;
-    const int nrt = (b + 15) >> 4;
-    sp_d4 acc[SP_RT][2];
-#pragma unroll
-    for (int t = 0; t < SP_RT; ++t) acc[t][0] = acc[t][1] = sp_d4{0.0, 0.0, 0.0, 0.0};
-    int rowc[SP_RT];       // clamped row of this lane in tile t
-    bool rowok[SP_RT];
-#pragma unroll
-    for (int t = 0; t < SP_RT; ++t) {
-        const int i = 16 * (wave + 4 * t) + lr;
-        rowok[t] = i < b;
-        rowc[t] = min(i, b - 1);
-    }
-    // Round 4: the A operands of SP_PF K-steps are in flight (a K-step is 8 MFMAs = 512 cycles of the pipe per wave; with one step of
-    // look-ahead every step waited out most of a ~2000-cycle load: the sigma path of a 200-vector basis ran at 0.18 of the FP64 peak)
-    constexpr int SP_PF = 4;
-    double an[SP_PF][SP_RT];
-#pragma unroll
-    for (int u = 0; u < SP_PF; ++u) {
-        const int jc = min(4 * u + lg, b - 1);
-#pragma unroll
-        for (int t = 0; t < SP_RT; ++t) an[u][t] = Cg[rowc[t] + (size_t)jc * ld];
-    }
-    for (int jb = 0; jb < b; jb += 4 * SP_PF) {
-#pragma unroll
-        for (int u = 0; u < SP_PF; ++u) {
-            const int j0 = jb + 4 * u;
-            if (j0 < b) {                                  // (wave-uniform)
-                const bool jok = j0 + lg < b;
-                double ac[SP_RT];
-#pragma unroll
-                for (int t = 0; t < SP_RT; ++t) ac[t] = (jok && rowok[t]) ? an[u][t] : 0.0;
-                {
-                    const int jn = min(j0 + 4 * SP_PF + lg, b - 1);
-#pragma unroll
-                    for (int t = 0; t < SP_RT; ++t) an[u][t] = Cg[rowc[t] + (size_t)jn * ld];
-                }
-                const int jl = min(j0 + lg, b - 1);
-                const double b0 = jok ? Kc[jl * SP_PC + lr] : 0.0;
-                const double b1 = jok ? Kc[jl * SP_PC + 16 + lr] : 0.0;
-#pragma unroll
-                for (int t = 0; t < SP_RT; ++t) {
-                    if (wave + 4 * t < nrt) {     // wave-uniform
-                        acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[t], b0, acc[t][0], 0, 0, 0);
-                        acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[t], b1, acc[t][1], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    // C/D layout: lane l, register r = V[i0 + (l >> 4) + 4 r][p0 + (l & 15)]
-#pragma unroll
-    for (int t = 0; t < SP_RT; ++t) {
-        if (wave + 4 * t < nrt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = 16 * (wave + 4 * t) + lg + 4 * r;
-                if (i < b) {
-                    Vc[i * SP_PC + lr] = acc[t][0][r];
-                    Vc[i * SP_PC + 16 + lr] = acc[t][1][r];
-                }
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(SP_THREADS) void sparse_predict_kernel(SpPredParams A)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int ld = A.ld, ny = A.ny;
-    double* T = reinterpret_cast<double*>(smem);   // 64
-    double* bv = T + 64;                           // 2*ld
-    double* al = bv + 2 * ld;                      // ny*ld
-    int* clamp = reinterpret_cast<int*>(al + 3 * ld);   // 2 doubles of room
-    double* racc = al + 3 * ld + 2;                // [8][SP_PC]
-    double* Kc = racc + 8 * SP_PC;                 // [ld][SP_PC]   (sigma path only; LDS is sized for it only then)
-    double* Vc = Kc + (size_t)ld * SP_PC;          // [ld][SP_PC]   (A.fast only)
-    gpc_exp_table_init(T);
-    const double sf = A.prm.sigmaf_sq, s20 = A.prm.noise;
-
-    for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
-        const int b = A.b[patch];
-        if (b <= A.small_max) continue;                 // (workgroup-uniform, before any barrier) sparse_predict_small_kernel took it
-        const double* Cg = A.C + (size_t)patch * ld * ld;
-        __syncthreads();
-        for (int i = tid; i < b; i += SP_THREADS) {
-            bv[2 * i] = A.BV[(size_t)patch * ld * 2 + 2 * i];
-            bv[2 * i + 1] = A.BV[(size_t)patch * ld * 2 + 2 * i + 1];
-            for (int c = 0; c < ny; ++c) al[c * ld + i] = A.alpha[((size_t)patch * ny + c) * ld + i];
-        }
-        if (tid == 0) *clamp = 0;
-        __syncthreads();
-        const int po = A.off ? A.off[patch] : 0;                           // first point of this patch in xs0 / xs1
-        const int m = A.off ? A.off[patch + 1] - po : A.m;
-        const size_t fstride = A.off ? (size_t)A.n_total : (size_t)m;     // distance between the output planes
-        const double* xs0 = A.xs0 + po;
-        const double* xs1 = A.xs1 + po;
-        double* fs = A.off ? A.f_star + po : A.f_star + (size_t)patch * ny * m;
-        // mean: f = alpha^T k (:329); b == 0 -> 0 (:321-327)
-        for (int p = tid; p < m; p += SP_THREADS) {
-            const double q0 = xs0[p], q1 = xs1[p];
-            double s[3] = {0.0, 0.0, 0.0};
-            for (int i = 0; i < b; ++i) {
-                const double k = gpc_rbf_neg(sf, A.c_exp, q0, q1, bv[2 * i], bv[2 * i + 1], T);
-                for (int c = 0; c < ny; ++c) s[c] += al[c * ld + i] * k;
-            }
-            for (int c = 0; c < ny; ++c) fs[(size_t)c * fstride + p] = s[c];
-        }
-        if (A.sigma) {
-            double* sg = A.off ? A.sigma + po : A.sigma + (size_t)patch * m;
-            for (int p0 = 0; p0 < m; p0 += SP_PC) {
-                const int pc = min(SP_PC, m - p0);
-                __syncthreads();
-                for (int e = tid; e < b * SP_PC; e += SP_THREADS) {
-                    const int pp = e & (SP_PC - 1), i = e / SP_PC;
-                    Kc[i * SP_PC + pp] = (pp < pc) ? gpc_rbf_neg(sf, A.c_exp, xs0[p0 + pp], xs1[p0 + pp], bv[2 * i], bv[2 * i + 1], T) : 0.0;
-                }
-                __syncthreads();
-                if (A.fast) {
-                    sp_ck_chunk(Cg, ld, b, Kc, Vc);
-                    __syncthreads();
-                }
-                const int pp = tid & (SP_PC - 1), ig = tid / SP_PC;   // 8 row groups
-                double acc = 0.0;
-                for (int j = ig; j < b; j += SP_THREADS / SP_PC) {
-                    // (C k)_j  (:330; C is symmetric)
-                    double t = 0.0;
-                    if (A.fast) t = Vc[j * SP_PC + pp];
-                    else
-                        for (int i = 0; i < b; ++i) t += Kc[i * SP_PC + pp] * Cg[i + (size_t)j * ld];
-                    acc += t * Kc[j * SP_PC + pp];
-                }
-                racc[ig * SP_PC + pp] = acc;
-                __syncthreads();
-                if (tid < pc) {
-                    const double kstar = sp_kstar(sf, xs0[p0 + tid], xs1[p0 + tid]);   // (:316)
-                    double kCk = 0.0;
-                    for (int q = 0; q < SP_THREADS / SP_PC; ++q) kCk += racc[q * SP_PC + tid];
-                    double sigma = (b == 0) ? kstar + s20 : s20 + kstar + kCk;
-                    if (sigma < 0) { sigma = 0; *clamp = 1; }                 // :334-337
-                    if (A.conf) {
-                        sigma /= kstar + s20;
-                        sigma = (double)100.0f * ((double)1.0f - sigma);    // :340-345
-                    } else {
-                        sigma = sqrt(sigma);
-                    }
-                    sg[p0 + tid] = sigma;
-                }
-            }
-        }
-        __syncthreads();
-        if (tid == 0 && A.status_out) {
-            int st = A.stat[patch];
-            if (st == GPC_STATUS_OK && *clamp) st = GPC_STATUS_SIGMA_CLAMPED;
-            A.status_out[patch] = st;
-        }
-    }
-}
-
-// ---- predict with a SMALL basis: one wave per patch, a lane per grid point (round 4) ------------------------------------------------
-// At the reference's default hyper-parameters a patch keeps ~13 basis vectors (8 .. 41 over a batch), and predict_measurements ALWAYS
-// computes sigma = sqrt(s20 + k* + k^T C k) (/root/reference/src/sparse_gp.hpp:299-351; the caller drops it, src/gp_compressor.cpp:333-334).
-// sparse_predict_kernel is shaped for a basis of 100 .. 200 -- a 256-thread workgroup per patch, chunks of 32 points, K and V = C K
-// through LDS, the MFMA pipe, five barriers per chunk -- and at b = 13 its sigma path took 4.3 ms for 32768 patches (the mean 0.5 ms):
-// 1.2 TFLOP/s on 6 GFLOP.  Here a lane owns a grid point: its b kernel values stay in registers (BM = 16 or 32 of them, zero beyond b),
-// C sits in LDS zero-padded to BM x BM and is read by broadcast, the mean and k^T C k are register FMAs -- no barrier, no reduction, no
-// second evaluation of k.  Mean: the same operations in the same order as sparse_predict_kernel (bit-identical); sigma: t_j = sum_i
-// C_ij k_i, then sum_j t_j k_j, a summation order of its own, held by the tolerance against the oracle.  Patches with more than BM
-// vectors are left to sparse_predict_kernel (SpPredParams::small_max), patches within the other instance's range to that one.
-template <int BM>
-__global__ __launch_bounds__(64) void sparse_predict_small_kernel(SpPredParams A, int b_lo)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* T = reinterpret_cast<double*>(smem);   // 64
-    double* Cl = T + 64;                           // [BM][BM] column-major, zero-padded
-    double* al = Cl + BM * BM;                     // [3][BM]
-    double* bv = al + 3 * BM;                      // [BM][2]
-    const int lane = threadIdx.x;
-    const int ld = A.ld, ny = A.ny;
-    gpc_exp_table_init(T);
-    const double sf = A.prm.sigmaf_sq, s20 = A.prm.noise;
-    for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
-        const int b = __builtin_amdgcn_readfirstlane(A.b[patch]);
-        if (b < b_lo || b > BM) continue;
-        __builtin_amdgcn_wave_barrier();           // (one wave: LDS instructions execute in order; the compiler must keep them so)
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        const double* Cg = A.C + (size_t)patch * ld * ld;
-        for (int e = lane; e < BM * BM; e += 64) {
-            const int i = e % BM, j = e / BM;
-            Cl[e] = (i < b && j < b) ? Cg[i + (size_t)j * ld] : 0.0;
-        }
-        if (lane < BM) {
-            const bool in = lane < b;
-            bv[2 * lane] = in ? A.BV[(size_t)patch * ld * 2 + 2 * lane] : 0.0;
-            bv[2 * lane + 1] = in ? A.BV[(size_t)patch * ld * 2 + 2 * lane + 1] : 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) al[c * BM + lane] = (in && c < ny) ? A.alpha[((size_t)patch * ny + c) * ld + lane] : 0.0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const int po = A.off ? A.off[patch] : 0;
-        const int m = A.off ? A.off[patch + 1] - po : A.m;
-        const size_t fstride = A.off ? (size_t)A.n_total : (size_t)m;
-        const double* xs0 = A.xs0 + po;
-        const double* xs1 = A.xs1 + po;
-        double* fs = A.off ? A.f_star + po : A.f_star + (size_t)patch * ny * m;
-        double* sg = A.sigma ? (A.off ? A.sigma + po : A.sigma + (size_t)patch * m) : nullptr;
-        bool clamped = false;
-        // (the lane's grid coordinates are loaded per iteration, on purpose: holding a shared grid in registers -- 28 VGPRs, two waves per
-        // SIMD less -- measured 1.24 against 1.12 ms for the sigma-predict of the defaults batch, staging it in LDS once per wave 1.30)
-        double nq0 = 0.0, nq1 = 0.0;             // the NEXT 64 points' coordinates are requested before this block's arithmetic
-        if (lane < m) { nq0 = xs0[lane]; nq1 = xs1[lane]; }
-        for (int p = lane; p < m; p += 64) {
-            const double q0 = nq0, q1 = nq1;
-            if (p + 64 < m) { nq0 = xs0[p + 64]; nq1 = xs1[p + 64]; }
-            double k[BM];
-            double s[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-            for (int i = 0; i < BM; ++i) {
-                k[i] = 0.0;
-                if (i < b) {                                    // (wave-uniform)
-                    k[i] = gpc_rbf_neg(sf, A.c_exp, q0, q1, bv[2 * i], bv[2 * i + 1], T);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        if (c < ny) s[c] += al[c * BM + i] * k[i];   // f = alpha^T k (:329), in sparse_predict_kernel's order
-                }
-            }
-            for (int c = 0; c < ny; ++c) fs[(size_t)c * fstride + p] = s[c];
-            if (sg) {
-                double kCk = 0.0;
-#pragma unroll
-                for (int j = 0; j < BM; ++j) {
-                    if (j < b) {                                // (wave-uniform)
-                        double t = 0.0;
-#pragma unroll
-                        for (int i = 0; i < BM; ++i) t += k[i] * Cl[i + BM * j];     // (C k)_j (:330; rows beyond b are zero)
-                        kCk += t * k[j];
-                    }
-                }
-                // (:316; the point's coordinates are read again here: kept live from the top of the loop they cost a wave per SIMD)
-                const double kstar = sp_kstar(sf, xs0[p], xs1[p]);
-                double sigma = (b == 0) ? kstar + s20 : s20 + kstar + kCk;
-                if (sigma < 0) { sigma = 0; clamped = true; }                 // :334-337
-                if (A.conf) {
-                    sigma /= kstar + s20;
-                    sigma = (double)100.0f * ((double)1.0f - sigma);    // :340-345
-                } else {
-                    sigma = sqrt(sigma);
-                }
-                sg[p] = sigma;
-            }
-        }
-        const bool any_clamp = __builtin_amdgcn_ballot_w64(clamped) != 0;
-        if (lane == 0 && A.status_out) {
-            int st = A.stat[patch];
-            if (st == GPC_STATUS_OK && any_clamp) st = GPC_STATUS_SIGMA_CLAMPED;
-            A.status_out[patch] = st;
-        }
-    }
-}
-
-// ---- registration inner loop: likelihoods and their derivatives on ragged point sets ----
-// sparse_gp::compute_likelihoods -> likelihood (/root/reference/src/sparse_gp.hpp:387-427) and compute_derivatives ->
-// likelihood_dx (:463-508) with rbf_kernel::kernel_dx (src/rbf_kernel.cpp:33-41); field variants
-// src/sparse_gp_field.hpp:322-392.  Per point: k (b), v = C k (the O(b^2) part), then
-//   sigma = s20 + k^T v + k**,  off = y - alpha^T k,  sigma_dx = 2 k_dx^T v,  k_dx row j = -(p0/p1) (x - BV_j) exp(..) = -(x - BV_j) k_j / p1
-//   l = exp(-|off|^2 / (2 sigma)) / sqrt((2 pi)^ny sigma)
-//   dX = exppart * (-sigma_dx + 2 (k_dx^T alpha) off + sigma_dx / sigma |off|^2),  exppart = exp(-|off|^2/(2 sigma)) / (2 sigma^1.5)
-// Same work distribution as the sigma path of sparse_predict_kernel: chunks of SP_PC points, thread = (point, one of 8
-// row groups of C), partial sums reduced through LDS.
-struct SpLikParams {
-    gpc_params prm;
-    double c_exp;
-    int P, ny, ld, n_total;
-    int fast;   // LDS holds a second [ld][SP_PC] buffer: V = C K by sp_ck_chunk
-    const int32_t* off;
-    const double *x0, *x1, *y;
-    const double *alpha, *C, *BV;
-    const int32_t* b;
-    double *dX, *l;
-    double* raw;   // train_sigmaf pass (prm.sigmaf_sq == 1): per point e^T C e, alpha^T e, sum_j |x - BV_j|^2 e_j alpha_j
-};
-#define SP_NQ 12   // partial sums per thread: kCk, 2 x (k_dx^T v), ny x mu, 2 x ny x (k_dx^T alpha)
-
-__global__ __launch_bounds__(SP_THREADS) void sparse_likelihood_kernel(SpLikParams A)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int ld = A.ld, ny = A.ny;
-    double* T = reinterpret_cast<double*>(smem);   // 64
-    double* bv = T + 64;                           // 2*ld
-    double* al = bv + 2 * ld;                      // 3*ld
-    double* racc = al + 3 * ld;                    // [SP_NQ][8][SP_PC]
-    double* Kc = racc + SP_NQ * 8 * SP_PC;         // [ld][SP_PC]
-    double* Vc = Kc + (size_t)ld * SP_PC;          // [ld][SP_PC]   (A.fast only)
-    gpc_exp_table_init(T);
-    const double sf = A.prm.sigmaf_sq, s20 = A.prm.noise, inv_l = 1.0 / A.prm.l_sq;
-
-    for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
-        const int b = A.b[patch];
-        const int o = A.off[patch], n = A.off[patch + 1] - o;
-        const double* Cg = A.C + (size_t)patch * ld * ld;
-        __syncthreads();
-        for (int i = tid; i < b; i += SP_THREADS) {
-            bv[2 * i] = A.BV[(size_t)patch * ld * 2 + 2 * i];
-            bv[2 * i + 1] = A.BV[(size_t)patch * ld * 2 + 2 * i + 1];
-            for (int c = 0; c < ny; ++c) al[c * ld + i] = A.alpha[((size_t)patch * ny + c) * ld + i];
-        }
-        for (int p0 = 0; p0 < n; p0 += SP_PC) {
-            const int pc = min(SP_PC, n - p0);
-            __syncthreads();
-            for (int e = tid; e < b * SP_PC; e += SP_THREADS) {
-                const int pp = e & (SP_PC - 1), i = e / SP_PC;
-                Kc[i * SP_PC + pp] = (pp < pc) ? gpc_rbf_neg(sf, A.c_exp, A.x0[o + p0 + pp], A.x1[o + p0 + pp], bv[2 * i], bv[2 * i + 1], T) : 0.0;
-            }
-            __syncthreads();
-            if (A.fast) {
-                sp_ck_chunk(Cg, ld, b, Kc, Vc);
-                __syncthreads();
-            }
-            const int pp = tid & (SP_PC - 1), ig = tid / SP_PC;   // 8 row groups
-            const bool live = pp < pc;
-            const double q0 = live ? A.x0[o + p0 + pp] : 0.0, q1 = live ? A.x1[o + p0 + pp] : 0.0;
-            double acc[SP_NQ];
-#pragma unroll
-            for (int q = 0; q < SP_NQ; ++q) acc[q] = 0.0;
-            for (int j = ig; j < b; j += SP_THREADS / SP_PC) {
-                double t = 0.0;                                   // v_j = (C k)_j, C symmetric
-                if (A.fast) t = Vc[j * SP_PC + pp];
-                else
-                    for (int i = 0; i < b; ++i) t += Kc[i * SP_PC + pp] * Cg[i + (size_t)j * ld];
-                const double kj = Kc[j * SP_PC + pp];
-                const double g0 = -(q0 - bv[2 * j]) * kj * inv_l, g1 = -(q1 - bv[2 * j + 1]) * kj * inv_l;   // k_dx row j
-                acc[0] += t * kj;
-                acc[1] += g0 * t;
-                acc[2] += g1 * t;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    if (c < ny) {
-                        const double a = al[c * ld + j];
-                        acc[3 + c] += a * kj;
-                        acc[6 + c] += g0 * a;
-                        acc[9 + c] += g1 * a;
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < SP_NQ; ++q) racc[(q * 8 + ig) * SP_PC + pp] = acc[q];
-            __syncthreads();
-            if (tid < pc) {
-                double r[SP_NQ];
-#pragma unroll
-                for (int q = 0; q < SP_NQ; ++q) {
-                    double s_ = 0.0;
-                    for (int w = 0; w < SP_THREADS / SP_PC; ++w) s_ += racc[(q * 8 + w) * SP_PC + tid];
-                    r[q] = s_;
-                }
-                const double kstar = sp_kstar(sf, A.x0[o + p0 + tid], A.x1[o + p0 + tid]);
-                double offv[3] = {0.0, 0.0, 0.0}, sq = 0.0;
-                for (int c = 0; c < ny; ++c) {
-                    offv[c] = A.y[(size_t)c * A.n_total + o + p0 + tid] - r[3 + c];
-                    sq += offv[c] * offv[c];
-                }
-                if (A.l) {
-                    const double sigma = s20 + kstar + r[0];                                    // :420-425
-                    const double two_pi = (double)2.0f * 3.14159265358979323846;
-                    const double norm = (ny == 1) ? two_pi * sigma : two_pi * two_pi * two_pi * sigma;
-                    A.l[o + p0 + tid] = (double)1.0f / sqrt(norm) * exp((double)(-0.5f) / sigma * sq);
-                }
-                if (A.dX) {
-                    const double sigma = s20 + r[0] + kstar;                                    // :485
-                    const double sqrtsigma = sqrt(sigma);
-                    const double exppart = (double)0.5f / (sigma * sqrtsigma) * exp((double)(-0.5f) / sigma * sq);
-                    double* d = A.dX + (size_t)(o + p0 + tid) * 3;
-                    for (int dd = 0; dd < 2; ++dd) {
-                        const double sigma_dx = (double)2.0f * r[1 + dd];
-                        double ko = 0.0;
-                        for (int c = 0; c < ny; ++c) ko += r[6 + 3 * dd + c] * offv[c];
-                        d[1 + dd] = exppart * (-sigma_dx + (double)2.0f * ko + sigma_dx / sigma * sq);
-                    }
-                    d[0] = (ny == 1) ? (double)(-1.0f) / (sigma * sqrtsigma) * offv[0] * exppart : 0.0;   // field: dx(0) = 0
-                }
-                if (A.raw) {
-                    const double u0 = A.x0[o + p0 + tid], u1 = A.x1[o + p0 + tid];
-                    double h = 0.0;
-                    for (int j = 0; j < b; ++j) {
-                        const double d0 = u0 - bv[2 * j], d1 = u1 - bv[2 * j + 1];
-                        h += (d0 * d0 + d1 * d1) * Kc[j * SP_PC + tid] * al[j];
-                    }
-                    double* w = A.raw + (size_t)(o + p0 + tid) * 3;
-                    w[0] = r[0]; w[1] = r[3]; w[2] = h;
-                }
-            }
-        }
-    }
-}
-
-// ---- row f4: the live part of sparse_gp::train_parameters (src/sparse_gp.hpp:586-640) ---------------------------------
-// The inner do-loop holds the state (alpha, C, BV) fixed and moves only kernel.param()(0) = sigma_f^2 = p, and every
-// quantity it evaluates is a polynomial in p over per-point sums that do not depend on p:
-//     k = p e,   alpha^T k = p a_i,   k_dtheta(:,0)^T alpha = a_i,   k_dtheta(:,1)^T alpha = p 0.5f/p1^2 h_i,   k^T C k = p^2 q_i
-// with e_j = exp(-0.5f/p1 |x_i - BV_j|^2), a_i = alpha^T e, h_i = sum_j |x_i - BV_j|^2 e_j alpha_j, q_i = e^T C e.  The O(n b^2)
-// sums come from one pass of sparse_likelihood_kernel (MFMA C K) with sigma_f^2 = 1; the <= 102 iterations are then O(n)
-// each and run here, one wave per patch.
-struct SpTrainParams {
-    int P, max_counter;
-    double sf, l_sq, s20, step;
-    const int32_t *off, *b;
-    const double *raw, *y;
-    double *p0, *ls, *delta;
-    int32_t* iters;
-};
-
-__device__ static inline double sp_wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);    // the same bits in every lane
-    return v;
-}
-
-__global__ __launch_bounds__(SP_THREADS) void sparse_train_kernel(SpTrainParams A)
-{
-    const int lane = threadIdx.x & 63;
-    const int patch = blockIdx.x * (SP_THREADS / 64) + (threadIdx.x >> 6);
-    if (patch >= A.P) return;
-    const int o = A.off[patch], n = A.off[patch + 1] - o;
-    double p = A.sf, d0 = 0.0, d1 = 0.0;
-    int iters = 0;
-    if (A.b[patch] >= 20) {                                        // "if (first && BV.cols() < 20) return;"  (:609-611)
-        const double logsqrt2pi = (double)0.5f * log((double)2.0f * 3.14159265358979323846);
-        const double hc = (double)0.5f / (A.l_sq * A.l_sq);
-        const double* raw = A.raw + (size_t)o * 3;
-        const double* y = A.y + o;
-        int counter = 0;
-        do {
-            d0 = d1 = 0.0;
-            for (int i = lane; i < n; i += 64) {                   // likelihood_dtheta (:510-519), summed over the points (:619-623)
-                const double a = raw[3 * i + 1], h = raw[3 * i + 2];
-                const double r = p * a - y[i];
-                d0 += r * a;
-                d1 += r * (p * hc * h);
-            }
-            d0 = sp_wave_sum(d0);
-            d1 = sp_wave_sum(d1);
-            p += A.step * d0;                                      // :624
-            double ls = 0.0;
-            for (int i = lane; i < n; i += 64) {                   // log_likelihood (:356-385) with the updated parameter
-                const double q = raw[3 * i], a = raw[3 * i + 1];
-                const double mu = p * a, sigma = A.s20 + p + p * p * q;
-                const double cent2 = (y[i] - mu) * (y[i] - mu);
-                ls += -logsqrt2pi - (double)0.5f * log(sigma) - (double)0.5f * cent2 / sigma;
-            }
-            ls = sp_wave_sum(ls);
-            if (lane == 0) A.ls[(size_t)patch * (A.max_counter + 2) + counter] = ls;
-            iters = counter + 1;
-            if (counter > A.max_counter) break;                    // :630-633
-            ++counter;
-        } while (sqrt(d0 * d0 + d1 * d1) > (double)1e-2f);         // :636 (a NaN gradient ends the loop as well)
-    }
-    if (lane == 0) {
-        A.p0[patch] = p;
-        A.iters[patch] = iters;
-        A.delta[2 * patch] = d0;
-        A.delta[2 * patch + 1] = d1;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 
 static size_t sp_add_lds_small(int bm = SP_BMAX) { return sizeof(double) * (size_t)(64 + 16 + 6 + 4 * (bm + 2) + 22 * (bm + 1) + 2 * bm * bm); }
 static size_t sp_add_lds(int ld, bool tri = false) { return sizeof(double) * (size_t)(64 + 16 + 6 + 4 * (ld + 1) + 8 * ld + 9 * ld + 5 * ld + (tri ? 4 * ld : 0)); }
-static size_t sp_lik_lds(int ld, bool fast)
-{
-    return sizeof(double) * (size_t)(64 + 5 * ld + SP_NQ * 8 * SP_PC + (size_t)ld * SP_PC * (fast ? 2 : 1));
-}
-static size_t sp_pred_lds(int ld, bool sigma, bool fast)
-{
-    return sizeof(double) * (size_t)(64 + 5 * ld + (sigma ? (size_t)ld * SP_PC * (fast ? 2 : 1) : 0) + 8 * SP_PC + 2);
-}
 
-// The two instances of the small-basis predict kernel (b <= 16, 17 .. 32), ahead of sparse_predict_kernel on the same stream; sets
-// A.small_max so that the regular kernel skips what they took.  GPC_SPARSE_NO_SMALL_PREDICT=1: everything through the regular kernel.
-// The predict launches: the two instances of the small-basis kernel (b <= 16, 17 .. 32) and sparse_predict_kernel for the rest (it skips what
-// they took: A.small_max).  The three work on disjoint patches, and at the reference's defaults each is a short launch that ends in a tail of a few
-// long patches: they run SIDE BY SIDE on the context's stream and its two copy streams (forked and joined with events; the streams exist since
-// gpc_ctx_create).
-static int sp_predict_launch(gpc_ctx* ctx, SpPredParams& A, int grid, size_t lds)
+// the rows kernel for the object's ny (1: sparse_gp, 3: sparse_gp_field)
+template <int G, int B, bool LIST>
+static void sp_rows_launch(const SpAddParams& A, int grid, size_t lds, hipStream_t s)
 {
-    A.small_max = -1;
-    hipStream_t main_s = ctx->stream;
-    if (getenv("GPC_SPARSE_NO_SMALL_PREDICT") || A.ld < 1) {
-        hipLaunchKernelGGL(sparse_predict_kernel, dim3(grid), dim3(SP_THREADS), lds, main_s, A);
-        GPC_HIP(ctx, hipGetLastError());
-        return GPC_OK;
-    }
-    // (with sigma only: measured at the reference's defaults, 32768 patches -- sigma-predict 1.14 -> 0.84 ms; the mean-only launches are too
-    // short to pay for the fork and join, 0.23 -> 0.28 ms)
-    const bool fork = ctx->s_in && ctx->s_out && A.sigma != nullptr;
-    hipStream_t s32 = fork ? ctx->s_in : main_s, sreg = fork ? ctx->s_out : main_s;
-    // (the third launch goes to the context's OWN stream: the legacy default stream does not overlap its kernels with another stream's, and
-    // a caller's stream may share a hardware queue with s_in or s_out -- gpc_api.hip, dense_host; own_stream, s_in and s_out never do)
-    hipStream_t s16 = (fork && ctx->own_stream) ? ctx->own_stream : main_s;
-    if (fork) {
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[0][14], main_s));
-        GPC_HIP(ctx, hipStreamWaitEvent(s32, ctx->ev[0][14], 0));
-        GPC_HIP(ctx, hipStreamWaitEvent(sreg, ctx->ev[0][14], 0));
-        if (s16 != main_s) GPC_HIP(ctx, hipStreamWaitEvent(s16, ctx->ev[0][14], 0));
-    }
-    const int waves = std::min(A.P, ctx->num_cus * 16);
-    const size_t l16 = sizeof(double) * (size_t)(64 + 16 * 16 + 5 * 16), l32 = sizeof(double) * (size_t)(64 + 32 * 32 + 5 * 32);
-    A.small_max = 32;
-    // (the regular kernel first: its few patches are the longest)
-    hipLaunchKernelGGL(sparse_predict_kernel, dim3(grid), dim3(SP_THREADS), lds, sreg, A);
-    GPC_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((sparse_predict_small_kernel<32>), dim3(std::min(A.P, ctx->num_cus * 12)), dim3(64), l32, s32, A, 17);
-    GPC_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((sparse_predict_small_kernel<16>), dim3(waves), dim3(64), l16, s16, A, 0);
-    GPC_HIP(ctx, hipGetLastError());
-    if (fork) {
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[1][14], s32));
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[2][14], sreg));
-        GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][14], 0));
-        GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][14], 0));
-        if (s16 != main_s) {
-            GPC_HIP(ctx, hipEventRecord(ctx->ev[1][12], s16));
-            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][12], 0));
-        }
-    }
-    return GPC_OK;
+    if (A.ny == 1) hipLaunchKernelGGL((sparse_add_rows_kernel<G, 1, B, LIST>), dim3(grid), dim3(64), lds, s, A);
+    else hipLaunchKernelGGL((sparse_add_rows_kernel<G, 3, B, LIST>), dim3(grid), dim3(64), lds, s, A);
 }
 
-extern "C" {
-
-int gpc_sparse_create(gpc_ctx* ctx, const gpc_params* params, int P, int ny, gpc_sparse** out)
+int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, const int32_t* perm,
+                  int32_t* status)
 {
-    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
-    if (!out) return gpc_fail(ctx, GPC_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (!params) return gpc_fail(ctx, GPC_EINVAL, "params is NULL");
-    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative P");
-    if (ny != 1 && ny != 3) return gpc_fail(ctx, GPC_EINVAL, "ny must be 1 (sparse_gp) or 3 (sparse_gp_field), got %d", ny);
-    if (params->capacity == 0 || params->capacity < -1) return gpc_fail(ctx, GPC_EINVAL, "capacity must be > 0 or -1");
-    if (params->capacity > GPC_MAX_BV - 1) return gpc_fail(ctx, GPC_ERANGE, "capacity %d > %d", params->capacity, GPC_MAX_BV - 1);
-    if (params->noise_model < 0 || params->noise_model > 2) return gpc_fail(ctx, GPC_EINVAL, "noise_model must be 0, 1 or 2");
-    if (params->noise_model != 0 && ny != 1) return gpc_fail(ctx, GPC_EINVAL, "probit noise needs ny == 1");
-    if (!(params->l_sq > 0.0) || !(params->sigmaf_sq > 0.0)) return gpc_fail(ctx, GPC_EINVAL, "kernel parameters out of range");
-    gpc_sparse* g = new (std::nothrow) gpc_sparse();
-    if (!g) return GPC_ENOMEM;
-    g->ctx = ctx; g->prm = *params; g->P = P; g->ny = ny;
-    // capacity + 1 rows (a full update holds capacity + 1 basis vectors until the deletion that follows it), rounded up to 16
-    // doubles = 128 B: every column of C and Q then starts on a cache line, and a wave's 64-row segment is exactly 4 lines.
-    // With ld = 201 the segments straddled lines -- 5 fetched per 4 used, re-fetched from HBM by the next row trip -- and
-    // the add path, which is bound by exactly this stream, read 27 % more than it consumed (profiles/r02_summary.json).
-    g->ld = params->capacity == -1 ? GPC_MAX_BV : ((params->capacity + 1 + 15) & ~15);
-    g->alpha = g->C = g->Q = g->BV = nullptr;
-    g->b = g->count = g->stat = nullptr;
-    g->done_it = nullptr;
-    g->list = nullptr;
-    g->trace = nullptr;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t ld = (size_t)g->ld, Pn = (size_t)(P > 0 ? P : 1);
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(&g->alpha, 8 * Pn * ny * ld);
-    if (e == hipSuccess) e = hipMalloc(&g->C, 8 * Pn * ld * ld);
-    if (e == hipSuccess) e = hipMalloc(&g->Q, 8 * Pn * ld * ld);
-    if (e == hipSuccess) e = hipMalloc(&g->BV, 8 * Pn * ld * 2);
-    if (e == hipSuccess) e = hipMalloc(&g->b, 4 * Pn);
-    if (e == hipSuccess) e = hipMalloc(&g->count, 4 * Pn);
-    if (e == hipSuccess) e = hipMalloc(&g->stat, 4 * Pn);
-    if (e == hipSuccess) e = hipMalloc(&g->done_it, 4 * Pn);
-    if (e == hipSuccess) e = hipMalloc(&g->list, 4 * (3 * Pn + 12));      // three work lists of P entries, then their 3 x 4 counters
-    if (e == hipSuccess) e = hipMemsetAsync(g->b, 0, 4 * Pn, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(g->count, 0, 4 * Pn, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(g->stat, 0, 4 * Pn, ctx->stream);
-    if (e != hipSuccess) {
-        int rc = gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_create: %s", hipGetErrorString(e));
-        for (void* p : {(void*)g->alpha, (void*)g->C, (void*)g->Q, (void*)g->BV, (void*)g->b, (void*)g->count, (void*)g->stat, (void*)g->done_it, (void*)g->list})
-            if (p) (void)hipFree(p);
-        delete g;
-        return rc;
-    }
-    gpc_ctx_ref(ctx);
-    *out = g;
-    return GPC_OK;
-}
-
-// Safe in either order with gpc_ctx_destroy: a context destroyed first has synchronised its stream already and stays
-// allocated (dead) until its last child is gone.
-void gpc_sparse_destroy(gpc_sparse* g)
-{
-    if (!g) return;
     gpc_ctx* ctx = g->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (!ctx->dead.load()) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (!ctx->dead.load()) (void)hipStreamSynchronize(ctx->stream);
-    }
-    for (void* p : {(void*)g->alpha, (void*)g->C, (void*)g->Q, (void*)g->BV, (void*)g->b, (void*)g->count, (void*)g->stat, (void*)g->done_it, (void*)g->list})
-        if (p) (void)hipFree(p);
-    delete g;
-    gpc_ctx_unref(ctx);
-}
-
-int gpc_sparse_ld(const gpc_sparse* g) { return g ? g->ld : GPC_EINVAL; }
-
-int gpc_sparse_set_trace(gpc_sparse* g, uint8_t* trace_dev)
-{
-    if (!g) return GPC_EINVAL;
-    if (g->ctx->dead.load()) return GPC_EINVAL;
-    std::lock_guard<std::mutex> lk(g->ctx->mu);
-    g->trace = trace_dev;
-    return GPC_OK;
-}
-
-int gpc_sparse_reset(gpc_sparse* g)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t Pn = (size_t)(g->P > 0 ? g->P : 1);
-    GPC_HIP(ctx, hipMemsetAsync(g->b, 0, 4 * Pn, ctx->stream));
-    GPC_HIP(ctx, hipMemsetAsync(g->count, 0, 4 * Pn, ctx->stream));
-    GPC_HIP(ctx, hipMemsetAsync(g->stat, 0, 4 * Pn, ctx->stream));
-    return GPC_OK;
-}
-
-int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total, const double* x0, const double* x1,
-                       const double* y, const int32_t* perm, int32_t* status)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (n_total < 0 || n_max < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
-    if (g->P == 0) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
     SpAddParams A;
     A.prm = g->prm;
     A.c_exp = (double)(-0.5f) / g->prm.l_sq;
@@ -2273,6 +1600,8 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
     int32_t* const L[3] = {g->list, g->list + g->P, g->list + 2 * (size_t)g->P};
     int32_t* const N[3] = {g->list + 3 * (size_t)g->P, g->list + 3 * (size_t)g->P + 4, g->list + 3 * (size_t)g->P + 8};
     int cur = 0;                                   // the list the next phase draws from
+    auto hand_on = [&]() { A.out_list = L[cur + 1]; A.out_list_n = N[cur + 1]; };   // the phase in hand appends what it does not finish to the next list
+    auto advance = [&]() { ++cur; A.list = L[cur]; A.list_n = N[cur]; A.out_list = A.out_list_n = nullptr; };   // ... which the next phase draws from
     if (!getenv("GPC_SPARSE_NO_SMALL")) {
         // rows phase first (Gaussian noise): four patches per wave while a patch needs at most 16 basis vectors and no deletion;
         // what it does not finish goes on the work list of the phases below
@@ -2289,8 +1618,7 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
             // (a wave per four patches, placed by the hardware as slots come free: patches that leave the phase early end their wave early,
             // and persistent waves striding over the batch carried that imbalance to the end -- 1.93 -> 1.88 ms for the colour GP's pass,
             // level for the depth GP)
-            if (A.ny == 1) hipLaunchKernelGGL((sparse_add_rows_kernel<G, 1>), dim3(waves), dim3(64), lds_r, ctx->stream, A);
-            else hipLaunchKernelGGL((sparse_add_rows_kernel<G, 3>), dim3(waves), dim3(64), lds_r, ctx->stream, A);
+            sp_rows_launch<G, G, false>(A, waves, lds_r, ctx->stream);
             GPC_HIP(ctx, hipGetLastError());
             A.start_it = g->done_it;
         }
@@ -2306,17 +1634,12 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
             const size_t lds_2 = sizeof(double) * (size_t)(64 + R2 * (2 * B2 * B2 + 4 * B2));
             const int per_cu_2 = std::min(8, (int)((160u * 1024u) / lds_2));
             A.ticket_slot = 1;
-            A.out_list = L[cur + 1];
-            A.out_list_n = N[cur + 1];
+            hand_on();
             const int waves2 = (g->P + R2 - 1) / R2;
-            if (A.ny == 1) hipLaunchKernelGGL((sparse_add_rows_kernel<G2, 1, B2, true>), dim3(std::min(waves2, ctx->num_cus * per_cu_2)), dim3(64), lds_2, ctx->stream, A);
-            else hipLaunchKernelGGL((sparse_add_rows_kernel<G2, 3, B2, true>), dim3(std::min(waves2, ctx->num_cus * per_cu_2)), dim3(64), lds_2, ctx->stream, A);
+            sp_rows_launch<G2, B2, true>(A, std::min(waves2, ctx->num_cus * per_cu_2), lds_2, ctx->stream);
             GPC_HIP(ctx, hipGetLastError());
             rows2 = true;
-            ++cur;
-            A.list = L[cur];
-            A.list_n = N[cur];
-            A.out_list = A.out_list_n = nullptr;
+            advance();
         }
         // small-basis phase: one wave per patch, C and Q in LDS, until a patch outgrows SP_BMAX basis vectors
         const size_t lds_s = sp_add_lds_small();
@@ -2324,21 +1647,13 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
         per_cu_s = per_cu_s > 16 ? 16 : per_cu_s;
         A.done_it = g->done_it;
         A.ticket_slot = 1;
-        if (!rows2 && A.list) {
-            A.out_list = L[cur + 1];
-            A.out_list_n = N[cur + 1];
-        }
+        if (!rows2 && A.list) hand_on();
         if (!gauss)
             hipLaunchKernelGGL((sparse_add_kernel<true, true>), dim3(std::min(g->P, ctx->num_cus * per_cu_s)), dim3(64), lds_s, ctx->stream, A);
         else if (!rows2)
             hipLaunchKernelGGL((sparse_add_kernel<true, false>), dim3(std::min(g->P, ctx->num_cus * per_cu_s)), dim3(64), lds_s, ctx->stream, A);
         GPC_HIP(ctx, hipGetLastError());
-        if (!rows2 && A.list) {
-            ++cur;
-            A.list = L[cur];
-            A.list_n = N[cur];
-            A.out_list = A.out_list_n = nullptr;
-        }
+        if (!rows2 && A.list) advance();
         A.start_it = g->done_it;
         // mid phase (Gaussian noise, round 4): the patches that have outgrown SP_BMAX vectors -- a few hundred of 32768 at the reference's
         // defaults, each a chain of up to n points -- go through a second instance of the one-wave kernel with a resident block of
@@ -2348,15 +1663,11 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
             const size_t lds_m = sp_add_lds_small(SP_BMID);
             const int per_cu_m = std::max(1, (int)((160u * 1024u) / lds_m));
             A.ticket_slot = 1;
-            A.out_list = L[cur + 1];
-            A.out_list_n = N[cur + 1];
+            hand_on();
             hipLaunchKernelGGL((sparse_add_kernel<true, false, false, false, SP_BMID>), dim3(std::min(g->P, ctx->num_cus * per_cu_m)), dim3(64), lds_m,
                                ctx->stream, A);
             GPC_HIP(ctx, hipGetLastError());
-            ++cur;
-            A.list = L[cur];
-            A.list_n = N[cur];
-            A.out_list = A.out_list_n = nullptr;
+            advance();
         }
         A.ticket_slot = 1;
         A.done_it = nullptr;
@@ -2372,460 +1683,3 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }
-
-int gpc_sparse_predict_dev(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
-                           int conf, int32_t* status)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (m < 0) return gpc_fail(ctx, GPC_EINVAL, "negative m");
-    if (m > 0 && (!xs0 || !xs1 || !f_star)) return gpc_fail(ctx, GPC_EINVAL, "xs0/xs1/f_star is NULL");
-    if (g->P == 0 || m == 0) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
-    SpPredParams A;
-    A.prm = g->prm;
-    A.c_exp = (double)(-0.5f) / g->prm.l_sq;
-    A.P = g->P; A.ny = g->ny; A.ld = g->ld; A.m = m; A.conf = conf;
-    A.xs0 = xs0; A.xs1 = xs1; A.alpha = g->alpha; A.C = g->C; A.BV = g->BV; A.b = g->b;
-    A.f_star = f_star; A.sigma = sigma; A.status_out = status; A.stat = g->stat;
-    A.off = nullptr; A.n_total = 0;
-    A.fast = (sigma != nullptr && sp_pred_lds(g->ld, true, true) <= 160u * 1024u) ? 1 : 0;
-    const size_t lds = sp_pred_lds(g->ld, sigma != nullptr, A.fast != 0);
-    // per call: the attribute is per device, and a process may hold contexts on several GPUs (idempotent, host-side only)
-    GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_predict_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    int per_cu = (int)((160u * 1024u) / lds);
-    { const int cap_blocks = sigma ? 4 : 8;   // mean only: a patch is a few hundred kernel evaluations, more resident blocks hide their latency
-      per_cu = per_cu > cap_blocks ? cap_blocks : (per_cu < 1 ? 1 : per_cu); }
-    int grid = std::min(g->P, ctx->num_cus * per_cu);
-    return sp_predict_launch(ctx, A, grid, lds);
-}
-
-// predict_measurements on every patch's OWN point set (ragged, like the add call's batch): the reference's per-patch training-set
-// RMS block (/root/reference/src/gp_compressor.cpp:303-315) calls gps[i].predict_measurements(f, X_i, sigma) exactly so.
-int gpc_sparse_predict_points_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1,
-                                  double* f, double* sigma, int conf, int32_t* status)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (n_total > 0 && (!x0 || !x1 || !f)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/f is NULL");
-    if (g->P == 0) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
-    SpPredParams A;
-    A.prm = g->prm;
-    A.c_exp = (double)(-0.5f) / g->prm.l_sq;
-    A.P = g->P; A.ny = g->ny; A.ld = g->ld; A.m = 0; A.conf = conf;
-    A.xs0 = x0; A.xs1 = x1; A.alpha = g->alpha; A.C = g->C; A.BV = g->BV; A.b = g->b;
-    A.f_star = f; A.sigma = sigma; A.status_out = status; A.stat = g->stat;
-    A.off = off; A.n_total = n_total;
-    A.fast = (sigma != nullptr && sp_pred_lds(g->ld, true, true) <= 160u * 1024u) ? 1 : 0;
-    const size_t lds = sp_pred_lds(g->ld, sigma != nullptr, A.fast != 0);
-    GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_predict_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    int per_cu = (int)((160u * 1024u) / lds);
-    per_cu = per_cu > 4 ? 4 : (per_cu < 1 ? 1 : per_cu);
-    int grid = std::min(g->P, ctx->num_cus * per_cu);
-    return sp_predict_launch(ctx, A, grid, lds);
-}
-
-// caller holds ctx->mu.  raw != nullptr: the train_sigmaf pass (sigma_f^2 = 1, per-point sums only)
-static int sp_likelihood_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
-                                double* dX, double* l, double* raw)
-{
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    SpLikParams A;
-    A.prm = g->prm;
-    A.raw = raw;
-    if (raw) A.prm.sigmaf_sq = 1.0;
-    A.c_exp = (double)(-0.5f) / g->prm.l_sq;
-    A.P = g->P; A.ny = g->ny; A.ld = g->ld; A.n_total = n_total;
-    A.off = off; A.x0 = x0; A.x1 = x1; A.y = y;
-    A.alpha = g->alpha; A.C = g->C; A.BV = g->BV; A.b = g->b;
-    A.dX = dX; A.l = l;
-    A.fast = (sp_lik_lds(g->ld, true) <= 160u * 1024u) ? 1 : 0;
-    const size_t lds = sp_lik_lds(g->ld, A.fast != 0);
-    // per call: the attribute is per device, and a process may hold contexts on several GPUs (idempotent, host-side only)
-    GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_likelihood_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    int per_cu = (int)((160u * 1024u) / lds);
-    per_cu = per_cu > 4 ? 4 : (per_cu < 1 ? 1 : per_cu);
-    int grid = std::min(g->P, ctx->num_cus * per_cu);
-    hipLaunchKernelGGL(sparse_likelihood_kernel, dim3(grid), dim3(SP_THREADS), lds, ctx->stream, A);
-    GPC_HIP(ctx, hipGetLastError());
-    return GPC_OK;
-}
-
-int gpc_sparse_likelihood_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1,
-                              const double* y, double* dX, double* l)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
-    if (g->prm.noise_model != 0) return gpc_fail(ctx, GPC_EINVAL, "likelihoods are defined for the Gaussian noise model");
-    if (g->P == 0 || n_total == 0 || (!dX && !l)) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
-    return sp_likelihood_launch(g, off, n_total, x0, x1, y, dX, l, nullptr);
-}
-
-#define GPC_TRAIN_MAX_COUNTER 10000
-
-int gpc_sparse_train_sigmaf_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
-                                double step, int max_counter, double* p0, int32_t* iters, double* ls, double* delta)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (g->ny != 1) return gpc_fail(ctx, GPC_EINVAL, "train_parameters exists for sparse_gp (ny == 1) only");
-    if (g->prm.noise_model != 0) return gpc_fail(ctx, GPC_EINVAL, "likelihoods are defined for the Gaussian noise model");
-    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (max_counter < 0 || max_counter > GPC_TRAIN_MAX_COUNTER) return gpc_fail(ctx, GPC_EINVAL, "max_counter must be in [0, %d]", GPC_TRAIN_MAX_COUNTER);
-    if (!(step == step)) return gpc_fail(ctx, GPC_EINVAL, "step is NaN");
-    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
-    if (g->P > 0 && (!p0 || !iters || !ls || !delta)) return gpc_fail(ctx, GPC_EINVAL, "p0/iters/ls/delta is NULL");
-    if (g->P == 0) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
-    int rc = gpc_ws_reserve(ctx, sizeof(double) * 3 * (size_t)(n_total > 0 ? n_total : 1));
-    if (rc != GPC_OK) return rc;
-    double* raw = static_cast<double*>(ctx->ws);
-    if (n_total > 0) {
-        rc = sp_likelihood_launch(g, off, n_total, x0, x1, y, nullptr, nullptr, raw);
-        if (rc != GPC_OK) return rc;
-    }
-    SpTrainParams T;
-    T.P = g->P; T.max_counter = max_counter;
-    T.sf = g->prm.sigmaf_sq; T.l_sq = g->prm.l_sq; T.s20 = g->prm.noise; T.step = step;
-    T.off = off; T.b = g->b; T.raw = raw; T.y = y;
-    T.p0 = p0; T.ls = ls; T.delta = delta; T.iters = iters;
-    const int wpb = SP_THREADS / 64;
-    hipLaunchKernelGGL(sparse_train_kernel, dim3((g->P + wpb - 1) / wpb), dim3(SP_THREADS), 0, ctx->stream, T);
-    GPC_HIP(ctx, hipGetLastError());
-    return GPC_OK;
-}
-
-int gpc_sparse_train_sigmaf(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y, double step,
-                            int max_counter, double* p0, int32_t* iters, double* ls, double* delta)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    const int P = g->P;
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (P == 0) return GPC_OK;
-    if (off[0] != 0) return gpc_fail(ctx, GPC_EINVAL, "off[0] must be 0");
-    for (int i = 0; i < P; ++i)
-        if (off[i + 1] < off[i]) return gpc_fail(ctx, GPC_EINVAL, "off must be non-decreasing (patch %d)", i);
-    if (max_counter < 0 || max_counter > GPC_TRAIN_MAX_COUNTER) return gpc_fail(ctx, GPC_EINVAL, "max_counter must be in [0, %d]", GPC_TRAIN_MAX_COUNTER);
-    const size_t N = (size_t)off[P], Pz = (size_t)P, W = (size_t)max_counter + 2;
-    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
-    if (!p0 || !iters || !ls || !delta) return gpc_fail(ctx, GPC_EINVAL, "p0/iters/ls/delta is NULL");
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_off = nullptr, *d_x0 = nullptr, *d_x1 = nullptr, *d_y = nullptr, *d_p0 = nullptr, *d_it = nullptr, *d_ls = nullptr, *d_de = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_off, d_x0, d_x1, d_y, d_p0, d_it, d_ls, d_de})
-            if (p) (void)hipFree(p);
-    };
-    hipStream_t s = gpc_stream_of(ctx);
-    hipError_t e = hipMalloc(&d_off, 4 * (Pz + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_x0, 8 * (N + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_x1, 8 * (N + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_y, 8 * (N + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_p0, 8 * Pz);
-    if (e == hipSuccess) e = hipMalloc(&d_it, 4 * Pz);
-    if (e == hipSuccess) e = hipMalloc(&d_ls, 8 * Pz * W);
-    if (e == hipSuccess) e = hipMalloc(&d_de, 16 * Pz);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ls, 0, 8 * Pz * W, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off, 4 * (Pz + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_x0, x0, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_x1, x1, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_y, y, 8 * N, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_train_sigmaf: %s", hipGetErrorString(e));
-    }
-    int rc = gpc_sparse_train_sigmaf_dev(g, (const int32_t*)d_off, (int)N, (const double*)d_x0, (const double*)d_x1, (const double*)d_y,
-                                         step, max_counter, (double*)d_p0, (int32_t*)d_it, (double*)d_ls, (double*)d_de);
-    if (rc == GPC_OK) e = hipMemcpyAsync(p0, d_p0, 8 * Pz, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess) e = hipMemcpyAsync(iters, d_it, 4 * Pz, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess) e = hipMemcpyAsync(ls, d_ls, 8 * Pz * W, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess) e = hipMemcpyAsync(delta, d_de, 16 * Pz, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    cleanup();
-    if (rc != GPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess)
-        return gpc_fail(ctx, GPC_EHIP, "gpc_sparse_train_sigmaf: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return GPC_OK;
-}
-
-int gpc_sparse_likelihood(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y,
-                          double* dX, double* l)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    const int P = g->P;
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (P == 0) return GPC_OK;
-    if (off[0] != 0) return gpc_fail(ctx, GPC_EINVAL, "off[0] must be 0");
-    for (int i = 0; i < P; ++i)
-        if (off[i + 1] < off[i]) return gpc_fail(ctx, GPC_EINVAL, "off must be non-decreasing (patch %d)", i);
-    const size_t N = (size_t)off[P];
-    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
-    if (N == 0 || (!dX && !l)) return GPC_OK;
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_off = nullptr, *d_x0 = nullptr, *d_x1 = nullptr, *d_y = nullptr, *d_dX = nullptr, *d_l = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_off, d_x0, d_x1, d_y, d_dX, d_l})
-            if (p) (void)hipFree(p);
-    };
-    hipStream_t s = gpc_stream_of(ctx);
-    hipError_t e = hipMalloc(&d_off, 4 * (size_t)(P + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_x0, 8 * N);
-    if (e == hipSuccess) e = hipMalloc(&d_x1, 8 * N);
-    if (e == hipSuccess) e = hipMalloc(&d_y, 8 * N * g->ny);
-    if (e == hipSuccess && dX) e = hipMalloc(&d_dX, 8 * N * 3);
-    if (e == hipSuccess && l) e = hipMalloc(&d_l, 8 * N);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off, 4 * (size_t)(P + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_x0, x0, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_x1, x1, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_y, y, 8 * N * g->ny, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_likelihood: %s", hipGetErrorString(e));
-    }
-    int rc = gpc_sparse_likelihood_dev(g, (const int32_t*)d_off, (int)N, (const double*)d_x0, (const double*)d_x1,
-                                       (const double*)d_y, (double*)d_dX, (double*)d_l);
-    if (rc == GPC_OK && dX) e = hipMemcpyAsync(dX, d_dX, 8 * N * 3, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess && l) e = hipMemcpyAsync(l, d_l, 8 * N, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    cleanup();
-    if (rc != GPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess)
-        return gpc_fail(ctx, GPC_EHIP, "gpc_sparse_likelihood: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return GPC_OK;
-}
-
-int gpc_sparse_add(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y,
-                   const int32_t* perm, int32_t* status)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    const int P = g->P;
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (P == 0) return GPC_OK;
-    if (off[0] != 0) return gpc_fail(ctx, GPC_EINVAL, "off[0] must be 0");
-    int n_max = 0;
-    for (int i = 0; i < P; ++i) {
-        const int n = off[i + 1] - off[i];
-        if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "off must be non-decreasing (patch %d)", i);
-        n_max = std::max(n_max, n);
-    }
-    const size_t N = (size_t)off[P];
-    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
-    if (perm)
-        for (int i = 0; i < P; ++i)
-            for (int k = off[i]; k < off[i + 1]; ++k)
-                if (perm[k] < 0 || perm[k] >= off[i + 1] - off[i])
-                    return gpc_fail(ctx, GPC_EINVAL, "perm[%d] = %d outside patch %d", k, perm[k], i);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_off = nullptr, *d_x0 = nullptr, *d_x1 = nullptr, *d_y = nullptr, *d_perm = nullptr, *d_st = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_off, d_x0, d_x1, d_y, d_perm, d_st})
-            if (p) (void)hipFree(p);
-    };
-    hipStream_t s = gpc_stream_of(ctx);
-    hipError_t e = hipMalloc(&d_off, 4 * (size_t)(P + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_x0, 8 * std::max<size_t>(N, 1));
-    if (e == hipSuccess) e = hipMalloc(&d_x1, 8 * std::max<size_t>(N, 1));
-    if (e == hipSuccess) e = hipMalloc(&d_y, 8 * std::max<size_t>(N, 1) * g->ny);
-    if (e == hipSuccess && perm) e = hipMalloc(&d_perm, 4 * std::max<size_t>(N, 1));
-    if (e == hipSuccess) e = hipMalloc(&d_st, 4 * (size_t)P);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off, 4 * (size_t)(P + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_x0, x0, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_x1, x1, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_y, y, 8 * N * g->ny, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N && perm) e = hipMemcpyAsync(d_perm, perm, 4 * N, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_add: %s", hipGetErrorString(e));
-    }
-    int rc = gpc_sparse_add_dev(g, (const int32_t*)d_off, n_max, (int)N, (const double*)d_x0, (const double*)d_x1,
-                                (const double*)d_y, (const int32_t*)d_perm, (int32_t*)d_st);
-    if (rc == GPC_OK && status) e = hipMemcpyAsync(status, d_st, 4 * (size_t)P, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    cleanup();
-    if (rc != GPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess)
-        return gpc_fail(ctx, GPC_EHIP, "gpc_sparse_add: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return GPC_OK;
-}
-
-int gpc_sparse_predict(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
-                       int conf, int32_t* status)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (m < 0) return gpc_fail(ctx, GPC_EINVAL, "negative m");
-    if (m > 0 && (!xs0 || !xs1 || !f_star)) return gpc_fail(ctx, GPC_EINVAL, "xs0/xs1/f_star is NULL");
-    const int P = g->P;
-    if (P == 0 || m == 0) return GPC_OK;
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_xs0 = nullptr, *d_xs1 = nullptr, *d_f = nullptr, *d_s = nullptr, *d_st = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_xs0, d_xs1, d_f, d_s, d_st})
-            if (p) (void)hipFree(p);
-    };
-    hipStream_t s = gpc_stream_of(ctx);
-    const size_t fbytes = 8 * (size_t)P * g->ny * m, sbytes = 8 * (size_t)P * m;
-    hipError_t e = hipMalloc(&d_xs0, 8 * (size_t)m);
-    if (e == hipSuccess) e = hipMalloc(&d_xs1, 8 * (size_t)m);
-    if (e == hipSuccess) e = hipMalloc(&d_f, fbytes);
-    if (e == hipSuccess && sigma) e = hipMalloc(&d_s, sbytes);
-    if (e == hipSuccess) e = hipMalloc(&d_st, 4 * (size_t)P);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_xs0, xs0, 8 * (size_t)m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_xs1, xs1, 8 * (size_t)m, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_predict: %s", hipGetErrorString(e));
-    }
-    int rc = gpc_sparse_predict_dev(g, m, (const double*)d_xs0, (const double*)d_xs1, (double*)d_f, (double*)d_s, conf,
-                                    (int32_t*)d_st);
-    if (rc == GPC_OK) e = hipMemcpyAsync(f_star, d_f, fbytes, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess && sigma) e = hipMemcpyAsync(sigma, d_s, sbytes, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess && status) e = hipMemcpyAsync(status, d_st, 4 * (size_t)P, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    cleanup();
-    if (rc != GPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess)
-        return gpc_fail(ctx, GPC_EHIP, "gpc_sparse_predict: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return GPC_OK;
-}
-
-int gpc_sparse_predict_points(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, double* f, double* sigma,
-                              int conf, int32_t* status)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    const int P = g->P;
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    if (P == 0) return GPC_OK;
-    if (off[0] != 0) return gpc_fail(ctx, GPC_EINVAL, "off[0] must be 0");
-    for (int i = 0; i < P; ++i)
-        if (off[i + 1] < off[i]) return gpc_fail(ctx, GPC_EINVAL, "off must be non-decreasing (patch %d)", i);
-    const size_t N = (size_t)off[P];
-    if (N > 0 && (!x0 || !x1 || !f)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/f is NULL");
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_off = nullptr, *d_x0 = nullptr, *d_x1 = nullptr, *d_f = nullptr, *d_s = nullptr, *d_st = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_off, d_x0, d_x1, d_f, d_s, d_st})
-            if (p) (void)hipFree(p);
-    };
-    hipStream_t s = gpc_stream_of(ctx);
-    const size_t N1 = std::max<size_t>(N, 1);
-    hipError_t e = hipMalloc(&d_off, 4 * (size_t)(P + 1));
-    if (e == hipSuccess) e = hipMalloc(&d_x0, 8 * N1);
-    if (e == hipSuccess) e = hipMalloc(&d_x1, 8 * N1);
-    if (e == hipSuccess) e = hipMalloc(&d_f, 8 * N1 * g->ny);
-    if (e == hipSuccess && sigma) e = hipMalloc(&d_s, 8 * N1);
-    if (e == hipSuccess) e = hipMalloc(&d_st, 4 * (size_t)P);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off, 4 * (size_t)(P + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_x0, x0, 8 * N, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && N) e = hipMemcpyAsync(d_x1, x1, 8 * N, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_predict_points: %s", hipGetErrorString(e));
-    }
-    int rc = gpc_sparse_predict_points_dev(g, (const int32_t*)d_off, (int)N, (const double*)d_x0, (const double*)d_x1, (double*)d_f,
-                                           (double*)d_s, conf, (int32_t*)d_st);
-    if (rc == GPC_OK && N) e = hipMemcpyAsync(f, d_f, 8 * N * g->ny, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess && sigma && N) e = hipMemcpyAsync(sigma, d_s, 8 * N, hipMemcpyDeviceToHost, s);
-    if (rc == GPC_OK && e == hipSuccess && status) e = hipMemcpyAsync(status, d_st, 4 * (size_t)P, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    cleanup();
-    if (rc != GPC_OK) return rc;
-    if (e != hipSuccess || e2 != hipSuccess)
-        return gpc_fail(ctx, GPC_EHIP, "gpc_sparse_predict_points: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return GPC_OK;
-}
-
-int gpc_sparse_sizes(gpc_sparse* g, int32_t* bv_count)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (!bv_count) return gpc_fail(ctx, GPC_EINVAL, "bv_count is NULL");
-    if (g->P == 0) return GPC_OK;
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = gpc_stream_of(ctx);
-    GPC_HIP(ctx, hipMemcpyAsync(bv_count, g->b, 4 * (size_t)g->P, hipMemcpyDeviceToHost, s));
-    GPC_HIP(ctx, hipStreamSynchronize(s));
-    return GPC_OK;
-}
-
-int gpc_sparse_get_state(gpc_sparse* g, double* alpha, double* C, double* Q, double* BV)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (g->P == 0) return GPC_OK;
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ld = (size_t)g->ld, P = (size_t)g->P;
-    hipStream_t s = gpc_stream_of(ctx);
-    if (alpha) GPC_HIP(ctx, hipMemcpyAsync(alpha, g->alpha, 8 * P * g->ny * ld, hipMemcpyDeviceToHost, s));
-    if (C) GPC_HIP(ctx, hipMemcpyAsync(C, g->C, 8 * P * ld * ld, hipMemcpyDeviceToHost, s));
-    if (Q) GPC_HIP(ctx, hipMemcpyAsync(Q, g->Q, 8 * P * ld * ld, hipMemcpyDeviceToHost, s));
-    if (BV) GPC_HIP(ctx, hipMemcpyAsync(BV, g->BV, 8 * P * ld * 2, hipMemcpyDeviceToHost, s));
-    GPC_HIP(ctx, hipStreamSynchronize(s));
-    return GPC_OK;
-}
-
-// Inverse of gpc_sparse_get_state: loads a stored model (the compressed representation of row f3).  alpha and BV are
-// required, C and Q may be NULL (zeroed: the mean prediction of the decompressor needs neither; sigma, likelihoods and
-// further online growth do).
-int gpc_sparse_set_state(gpc_sparse* g, const int32_t* bv_count, const double* alpha, const double* C, const double* Q,
-                         const double* BV)
-{
-    if (!g) return GPC_EINVAL;
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
-    if (g->P == 0) return GPC_OK;
-    if (!bv_count || !alpha || !BV) return gpc_fail(ctx, GPC_EINVAL, "bv_count/alpha/BV is NULL");
-    for (int i = 0; i < g->P; ++i)
-        if (bv_count[i] < 0 || bv_count[i] > g->ld) return gpc_fail(ctx, GPC_ERANGE, "bv_count[%d] = %d outside [0, %d]", i, bv_count[i], g->ld);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ld = (size_t)g->ld, P = (size_t)g->P;
-    hipStream_t s = ctx->stream;
-    GPC_HIP(ctx, hipMemcpyAsync(g->b, bv_count, 4 * P, hipMemcpyHostToDevice, s));
-    GPC_HIP(ctx, hipMemcpyAsync(g->count, bv_count, 4 * P, hipMemcpyHostToDevice, s));
-    GPC_HIP(ctx, hipMemsetAsync(g->stat, 0, 4 * P, s));
-    GPC_HIP(ctx, hipMemcpyAsync(g->alpha, alpha, 8 * P * g->ny * ld, hipMemcpyHostToDevice, s));
-    GPC_HIP(ctx, hipMemcpyAsync(g->BV, BV, 8 * P * ld * 2, hipMemcpyHostToDevice, s));
-    if (C) GPC_HIP(ctx, hipMemcpyAsync(g->C, C, 8 * P * ld * ld, hipMemcpyHostToDevice, s));
-    else GPC_HIP(ctx, hipMemsetAsync(g->C, 0, 8 * P * ld * ld, s));
-    if (Q) GPC_HIP(ctx, hipMemcpyAsync(g->Q, Q, 8 * P * ld * ld, hipMemcpyHostToDevice, s));
-    else GPC_HIP(ctx, hipMemsetAsync(g->Q, 0, 8 * P * ld * ld, s));
-    GPC_HIP(ctx, hipStreamSynchronize(s));
-    return GPC_OK;
-}
-
-}  // extern "C"

@@ -1,0 +1,397 @@
+// sparse_api.hip -- the gpc_sparse_* entry points of the C-ABI (include/gpc.h): the object, the _dev entries (argument checks,
+// locking, then the launcher beside the kernels: sparse.hip, sparse_predict.hip) and their host-pointer twins.
+#include <new>
+
+#include "sparse_internal.h"
+
+static void sp_free_all(gpc_sparse* g)
+{
+    for (void* p : {(void*)g->alpha, (void*)g->C, (void*)g->Q, (void*)g->BV, (void*)g->b, (void*)g->count, (void*)g->stat, (void*)g->done_it, (void*)g->list})
+        if (p) (void)hipFree(p);
+    delete g;
+}
+
+extern "C" {
+
+int gpc_sparse_create(gpc_ctx* ctx, const gpc_params* params, int P, int ny, gpc_sparse** out)
+{
+    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
+    if (!out) return gpc_fail(ctx, GPC_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!params) return gpc_fail(ctx, GPC_EINVAL, "params is NULL");
+    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative P");
+    if (ny != 1 && ny != 3) return gpc_fail(ctx, GPC_EINVAL, "ny must be 1 (sparse_gp) or 3 (sparse_gp_field), got %d", ny);
+    if (params->capacity == 0 || params->capacity < -1) return gpc_fail(ctx, GPC_EINVAL, "capacity must be > 0 or -1");
+    if (params->capacity > GPC_MAX_BV - 1) return gpc_fail(ctx, GPC_ERANGE, "capacity %d > %d", params->capacity, GPC_MAX_BV - 1);
+    if (params->noise_model < 0 || params->noise_model > 2) return gpc_fail(ctx, GPC_EINVAL, "noise_model must be 0, 1 or 2");
+    if (params->noise_model != 0 && ny != 1) return gpc_fail(ctx, GPC_EINVAL, "probit noise needs ny == 1");
+    if (!(params->l_sq > 0.0) || !(params->sigmaf_sq > 0.0)) return gpc_fail(ctx, GPC_EINVAL, "kernel parameters out of range");
+    gpc_sparse* g = new (std::nothrow) gpc_sparse();
+    if (!g) return GPC_ENOMEM;
+    g->ctx = ctx; g->prm = *params; g->P = P; g->ny = ny;
+    // capacity + 1 rows (a full update holds capacity + 1 basis vectors until the deletion that follows it), rounded up to 16
+    // doubles = 128 B: every column of C and Q then starts on a cache line, and a wave's 64-row segment is exactly 4 lines.
+    // With ld = 201 the segments straddled lines -- 5 fetched per 4 used, re-fetched from HBM by the next row trip -- and
+    // the add path, which is bound by exactly this stream, read 27 % more than it consumed (profiles/r02_summary.json).
+    g->ld = params->capacity == -1 ? GPC_MAX_BV : ((params->capacity + 1 + 15) & ~15);
+    g->alpha = g->C = g->Q = g->BV = nullptr;
+    g->b = g->count = g->stat = nullptr;
+    g->done_it = nullptr;
+    g->list = nullptr;
+    g->trace = nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t ld = (size_t)g->ld, Pn = (size_t)(P > 0 ? P : 1);
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = hipMalloc(&g->alpha, 8 * Pn * ny * ld);
+    if (e == hipSuccess) e = hipMalloc(&g->C, 8 * Pn * ld * ld);
+    if (e == hipSuccess) e = hipMalloc(&g->Q, 8 * Pn * ld * ld);
+    if (e == hipSuccess) e = hipMalloc(&g->BV, 8 * Pn * ld * 2);
+    if (e == hipSuccess) e = hipMalloc(&g->b, 4 * Pn);
+    if (e == hipSuccess) e = hipMalloc(&g->count, 4 * Pn);
+    if (e == hipSuccess) e = hipMalloc(&g->stat, 4 * Pn);
+    if (e == hipSuccess) e = hipMalloc(&g->done_it, 4 * Pn);
+    if (e == hipSuccess) e = hipMalloc(&g->list, 4 * (3 * Pn + 12));      // three work lists of P entries, then their 3 x 4 counters
+    if (e == hipSuccess) e = hipMemsetAsync(g->b, 0, 4 * Pn, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(g->count, 0, 4 * Pn, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(g->stat, 0, 4 * Pn, ctx->stream);
+    if (e != hipSuccess) {
+        int rc = gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_create: %s", hipGetErrorString(e));
+        sp_free_all(g);
+        return rc;
+    }
+    gpc_ctx_ref(ctx);
+    *out = g;
+    return GPC_OK;
+}
+
+// Safe in either order with gpc_ctx_destroy: a context destroyed first has synchronised its stream already and stays
+// allocated (dead) until its last child is gone.
+void gpc_sparse_destroy(gpc_sparse* g)
+{
+    if (!g) return;
+    gpc_ctx* ctx = g->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (!ctx->dead.load()) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (!ctx->dead.load()) (void)hipStreamSynchronize(ctx->stream);
+    }
+    sp_free_all(g);
+    gpc_ctx_unref(ctx);
+}
+
+int gpc_sparse_ld(const gpc_sparse* g) { return g ? g->ld : GPC_EINVAL; }
+
+int gpc_sparse_set_trace(gpc_sparse* g, uint8_t* trace_dev)
+{
+    if (!g) return GPC_EINVAL;
+    if (g->ctx->dead.load()) return GPC_EINVAL;
+    std::lock_guard<std::mutex> lk(g->ctx->mu);
+    g->trace = trace_dev;
+    return GPC_OK;
+}
+
+int gpc_sparse_reset(gpc_sparse* g)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t Pn = (size_t)(g->P > 0 ? g->P : 1);
+    GPC_HIP(ctx, hipMemsetAsync(g->b, 0, 4 * Pn, ctx->stream));
+    GPC_HIP(ctx, hipMemsetAsync(g->count, 0, 4 * Pn, ctx->stream));
+    GPC_HIP(ctx, hipMemsetAsync(g->stat, 0, 4 * Pn, ctx->stream));
+    return GPC_OK;
+}
+
+
+int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total, const double* x0, const double* x1,
+                       const double* y, const int32_t* perm, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total < 0 || n_max < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (g->P == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_add_launch(g, off, n_total, x0, x1, y, perm, status);
+}
+
+int gpc_sparse_predict_dev(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
+                           int conf, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (m < 0) return gpc_fail(ctx, GPC_EINVAL, "negative m");
+    if (m > 0 && (!xs0 || !xs1 || !f_star)) return gpc_fail(ctx, GPC_EINVAL, "xs0/xs1/f_star is NULL");
+    if (g->P == 0 || m == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    // (mean only: a patch is a few hundred kernel evaluations, more resident blocks hide their latency)
+    return sp_predict_launch(g, m, nullptr, 0, xs0, xs1, f_star, sigma, conf, status, sigma ? 4 : 8);
+}
+
+// predict_measurements on every patch's OWN point set (ragged, like the add call's batch): the reference's per-patch training-set
+// RMS block (/root/reference/src/gp_compressor.cpp:303-315) calls gps[i].predict_measurements(f, X_i, sigma) exactly so.
+int gpc_sparse_predict_points_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1,
+                                  double* f, double* sigma, int conf, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (n_total > 0 && (!x0 || !x1 || !f)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/f is NULL");
+    if (g->P == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_predict_launch(g, 0, off, n_total, x0, x1, f, sigma, conf, status, 4);
+}
+
+int gpc_sparse_likelihood_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1,
+                              const double* y, double* dX, double* l)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (g->prm.noise_model != 0) return gpc_fail(ctx, GPC_EINVAL, "likelihoods are defined for the Gaussian noise model");
+    if (g->P == 0 || n_total == 0 || (!dX && !l)) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_likelihood_launch(g, off, n_total, x0, x1, y, dX, l, nullptr);
+}
+
+#define GPC_TRAIN_MAX_COUNTER 10000
+
+int gpc_sparse_train_sigmaf_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
+                                double step, int max_counter, double* p0, int32_t* iters, double* ls, double* delta)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->ny != 1) return gpc_fail(ctx, GPC_EINVAL, "train_parameters exists for sparse_gp (ny == 1) only");
+    if (g->prm.noise_model != 0) return gpc_fail(ctx, GPC_EINVAL, "likelihoods are defined for the Gaussian noise model");
+    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (max_counter < 0 || max_counter > GPC_TRAIN_MAX_COUNTER) return gpc_fail(ctx, GPC_EINVAL, "max_counter must be in [0, %d]", GPC_TRAIN_MAX_COUNTER);
+    if (!(step == step)) return gpc_fail(ctx, GPC_EINVAL, "step is NaN");
+    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (g->P > 0 && (!p0 || !iters || !ls || !delta)) return gpc_fail(ctx, GPC_EINVAL, "p0/iters/ls/delta is NULL");
+    if (g->P == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    int rc = gpc_ws_reserve(ctx, sizeof(double) * 3 * (size_t)(n_total > 0 ? n_total : 1));
+    if (rc != GPC_OK) return rc;
+    double* raw = static_cast<double*>(ctx->ws);
+    if (n_total > 0) {
+        rc = sp_likelihood_launch(g, off, n_total, x0, x1, y, nullptr, nullptr, raw);
+        if (rc != GPC_OK) return rc;
+    }
+    return sp_train_launch(g, off, y, raw, step, max_counter, p0, iters, ls, delta);
+}
+
+// ---- host-pointer twins: validate, stage (GpcStaging, gpc_internal.h), the _dev entry, download
+
+int gpc_sparse_train_sigmaf(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y, double step,
+                            int max_counter, double* p0, int32_t* iters, double* ls, double* delta)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    const int P = g->P;
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (P == 0) return GPC_OK;
+    if (int rc = gpc_check_host_off(ctx, P, off, nullptr, nullptr)) return rc;
+    if (max_counter < 0 || max_counter > GPC_TRAIN_MAX_COUNTER) return gpc_fail(ctx, GPC_EINVAL, "max_counter must be in [0, %d]", GPC_TRAIN_MAX_COUNTER);
+    const size_t N = (size_t)off[P], Pz = (size_t)P, W = (size_t)max_counter + 2;
+    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (!p0 || !iters || !ls || !delta) return gpc_fail(ctx, GPC_EINVAL, "p0/iters/ls/delta is NULL");
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_train_sigmaf");
+    const int32_t* d_off = st.up(off, Pz + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
+    double *d_p0 = st.out<double>(Pz), *d_ls = st.out<double>(Pz * W, true), *d_de = st.out<double>(2 * Pz);
+    int32_t* d_it = st.out<int32_t>(Pz);
+    if (st.ok()) st.rc = gpc_sparse_train_sigmaf_dev(g, d_off, (int)N, d_x0, d_x1, d_y, step, max_counter, d_p0, d_it, d_ls, d_de);
+    st.down(p0, d_p0, Pz);
+    st.down(iters, d_it, Pz);
+    st.down(ls, d_ls, Pz * W);
+    st.down(delta, d_de, 2 * Pz);
+    return st.finish();
+}
+
+int gpc_sparse_likelihood(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y,
+                          double* dX, double* l)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    const int P = g->P;
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (P == 0) return GPC_OK;
+    if (int rc = gpc_check_host_off(ctx, P, off, nullptr, nullptr)) return rc;
+    const size_t N = (size_t)off[P], ny = (size_t)g->ny;
+    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (N == 0 || (!dX && !l)) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_likelihood");
+    const int32_t* d_off = st.up(off, (size_t)P + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N * ny);
+    double *d_dX = dX ? st.out<double>(N * 3) : nullptr, *d_l = l ? st.out<double>(N) : nullptr;
+    if (st.ok()) st.rc = gpc_sparse_likelihood_dev(g, d_off, (int)N, d_x0, d_x1, d_y, d_dX, d_l);
+    st.down(dX, d_dX, N * 3);
+    st.down(l, d_l, N);
+    return st.finish();
+}
+
+int gpc_sparse_add(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y,
+                   const int32_t* perm, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    const int P = g->P;
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (P == 0) return GPC_OK;
+    int n_max = 0;
+    if (int rc = gpc_check_host_off(ctx, P, off, &n_max, nullptr)) return rc;
+    const size_t N = (size_t)off[P], ny = (size_t)g->ny;
+    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (perm)
+        for (int i = 0; i < P; ++i)
+            for (int k = off[i]; k < off[i + 1]; ++k)
+                if (perm[k] < 0 || perm[k] >= off[i + 1] - off[i])
+                    return gpc_fail(ctx, GPC_EINVAL, "perm[%d] = %d outside patch %d", k, perm[k], i);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_add");
+    const int32_t* d_off = st.up(off, (size_t)P + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N * ny);
+    const int32_t* d_perm = perm ? st.up(perm, N) : nullptr;
+    int32_t* d_st = st.out<int32_t>((size_t)P);
+    if (st.ok()) st.rc = gpc_sparse_add_dev(g, d_off, n_max, (int)N, d_x0, d_x1, d_y, d_perm, d_st);
+    st.down(status, d_st, (size_t)P);
+    return st.finish();
+}
+
+int gpc_sparse_predict(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
+                       int conf, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (m < 0) return gpc_fail(ctx, GPC_EINVAL, "negative m");
+    if (m > 0 && (!xs0 || !xs1 || !f_star)) return gpc_fail(ctx, GPC_EINVAL, "xs0/xs1/f_star is NULL");
+    const int P = g->P;
+    if (P == 0 || m == 0) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t Pm = (size_t)P * (size_t)m, ny = (size_t)g->ny;
+    GpcStaging st(ctx, "gpc_sparse_predict");
+    const double *d_xs0 = st.up(xs0, (size_t)m), *d_xs1 = st.up(xs1, (size_t)m);
+    double *d_f = st.out<double>(Pm * ny), *d_s = sigma ? st.out<double>(Pm) : nullptr;
+    int32_t* d_st = st.out<int32_t>((size_t)P);
+    if (st.ok()) st.rc = gpc_sparse_predict_dev(g, m, d_xs0, d_xs1, d_f, d_s, conf, d_st);
+    st.down(f_star, d_f, Pm * ny);
+    st.down(sigma, d_s, Pm);
+    st.down(status, d_st, (size_t)P);
+    return st.finish();
+}
+
+int gpc_sparse_predict_points(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, double* f, double* sigma,
+                              int conf, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    const int P = g->P;
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (P == 0) return GPC_OK;
+    if (int rc = gpc_check_host_off(ctx, P, off, nullptr, nullptr)) return rc;
+    const size_t N = (size_t)off[P], ny = (size_t)g->ny;
+    if (N > 0 && (!x0 || !x1 || !f)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/f is NULL");
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_predict_points");
+    const int32_t* d_off = st.up(off, (size_t)P + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N);
+    double *d_f = st.out<double>(N * ny), *d_s = sigma ? st.out<double>(N) : nullptr;
+    int32_t* d_st = st.out<int32_t>((size_t)P);
+    if (st.ok()) st.rc = gpc_sparse_predict_points_dev(g, d_off, (int)N, d_x0, d_x1, d_f, d_s, conf, d_st);
+    st.down(f, d_f, N * ny);
+    st.down(sigma, d_s, N);
+    st.down(status, d_st, (size_t)P);
+    return st.finish();
+}
+
+int gpc_sparse_sizes(gpc_sparse* g, int32_t* bv_count)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (!bv_count) return gpc_fail(ctx, GPC_EINVAL, "bv_count is NULL");
+    if (g->P == 0) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = gpc_stream_of(ctx);
+    GPC_HIP(ctx, hipMemcpyAsync(bv_count, g->b, 4 * (size_t)g->P, hipMemcpyDeviceToHost, s));
+    GPC_HIP(ctx, hipStreamSynchronize(s));
+    return GPC_OK;
+}
+
+int gpc_sparse_get_state(gpc_sparse* g, double* alpha, double* C, double* Q, double* BV)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->P == 0) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ld = (size_t)g->ld, P = (size_t)g->P;
+    hipStream_t s = gpc_stream_of(ctx);
+    if (alpha) GPC_HIP(ctx, hipMemcpyAsync(alpha, g->alpha, 8 * P * g->ny * ld, hipMemcpyDeviceToHost, s));
+    if (C) GPC_HIP(ctx, hipMemcpyAsync(C, g->C, 8 * P * ld * ld, hipMemcpyDeviceToHost, s));
+    if (Q) GPC_HIP(ctx, hipMemcpyAsync(Q, g->Q, 8 * P * ld * ld, hipMemcpyDeviceToHost, s));
+    if (BV) GPC_HIP(ctx, hipMemcpyAsync(BV, g->BV, 8 * P * ld * 2, hipMemcpyDeviceToHost, s));
+    GPC_HIP(ctx, hipStreamSynchronize(s));
+    return GPC_OK;
+}
+
+// Inverse of gpc_sparse_get_state: loads a stored model (the compressed representation of row f3).  alpha and BV are
+// required, C and Q may be NULL (zeroed: the mean prediction of the decompressor needs neither; sigma, likelihoods and
+// further online growth do).
+int gpc_sparse_set_state(gpc_sparse* g, const int32_t* bv_count, const double* alpha, const double* C, const double* Q,
+                         const double* BV)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->P == 0) return GPC_OK;
+    if (!bv_count || !alpha || !BV) return gpc_fail(ctx, GPC_EINVAL, "bv_count/alpha/BV is NULL");
+    for (int i = 0; i < g->P; ++i)
+        if (bv_count[i] < 0 || bv_count[i] > g->ld) return gpc_fail(ctx, GPC_ERANGE, "bv_count[%d] = %d outside [0, %d]", i, bv_count[i], g->ld);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ld = (size_t)g->ld, P = (size_t)g->P;
+    hipStream_t s = ctx->stream;
+    GPC_HIP(ctx, hipMemcpyAsync(g->b, bv_count, 4 * P, hipMemcpyHostToDevice, s));
+    GPC_HIP(ctx, hipMemcpyAsync(g->count, bv_count, 4 * P, hipMemcpyHostToDevice, s));
+    GPC_HIP(ctx, hipMemsetAsync(g->stat, 0, 4 * P, s));
+    GPC_HIP(ctx, hipMemcpyAsync(g->alpha, alpha, 8 * P * g->ny * ld, hipMemcpyHostToDevice, s));
+    GPC_HIP(ctx, hipMemcpyAsync(g->BV, BV, 8 * P * ld * 2, hipMemcpyHostToDevice, s));
+    if (C) GPC_HIP(ctx, hipMemcpyAsync(g->C, C, 8 * P * ld * ld, hipMemcpyHostToDevice, s));
+    else GPC_HIP(ctx, hipMemsetAsync(g->C, 0, 8 * P * ld * ld, s));
+    if (Q) GPC_HIP(ctx, hipMemcpyAsync(g->Q, Q, 8 * P * ld * ld, hipMemcpyHostToDevice, s));
+    else GPC_HIP(ctx, hipMemsetAsync(g->Q, 0, 8 * P * ld * ld, s));
+    GPC_HIP(ctx, hipStreamSynchronize(s));
+    return GPC_OK;
+}
+
+}  // extern "C"

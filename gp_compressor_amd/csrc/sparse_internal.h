@@ -1,0 +1,40 @@
+// sparse_internal.h -- what the translation units of the sparse path share: sparse.hip (the add kernels), sparse_predict.hip (the
+// predict / likelihood / train kernels) and sparse_api.hip (the gpc_sparse_* C-ABI).
+#pragma once
+
+#include "gpc_device.h"
+#include "gpc_internal.h"
+
+#define SP_THREADS 256
+
+struct gpc_sparse {
+    gpc_ctx* ctx;
+    gpc_params prm;
+    int P, ny, ld;
+    double *alpha, *C, *Q, *BV;
+    int32_t *b, *count, *stat;
+    int32_t* done_it;   // P: hand-over between the phases of an add call (allocated with the object)
+    int32_t* list;      // P + 4: work list of the phases after the rows phase, then its length and three ticket counters
+    uint8_t* trace;     // diagnostic (gpc_sparse_set_trace): device buffer for the decision bytes of the next add calls, or nullptr
+};
+
+// kernel_function(X, X) = p(0) exp(-0.5/p(1) |X - X|^2) (src/sparse_gp.hpp:98, :316): p(0) for a finite X (X - X = +0, exp(-0) is exactly 1,
+// so finite data keeps its bits) and NaN when a coordinate is NaN or +-inf (X - X = NaN): no select, three operations.
+__device__ static __forceinline__ double sp_kstar(double sf, double x0, double x1) { return sf + ((x0 - x0) + (x1 - x1)); }
+
+// ---- launchers implemented beside their kernels.  The caller (sparse_api.hip) has checked the arguments, holds ctx->mu, has set the
+// device and made the poison call; all pointers are device pointers.
+
+// sparse.hip: the phases of one add call
+int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, const int32_t* perm,
+                  int32_t* status);
+// sparse_predict.hip.  off == nullptr: every patch at the shared grid xs0 / xs1 [m]; else patch i at its own points off[i] .. off[i+1]-1 of
+// xs0 / xs1 (m == 0, plane stride n_total).  max_blocks: cap on the resident workgroups per CU of the regular kernel.
+int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, const double* xs0, const double* xs1, double* f_star,
+                      double* sigma, int conf, int32_t* status, int max_blocks);
+// raw != nullptr: the train_sigmaf pass (sigma_f^2 = 1, per-point sums only)
+int sp_likelihood_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
+                         double* dX, double* l, double* raw);
+// the iterations of train_sigmaf on the per-point sums `raw` of sp_likelihood_launch
+int sp_train_launch(gpc_sparse* g, const int32_t* off, const double* y, const double* raw, double step, int max_counter, double* p0,
+                    int32_t* iters, double* ls, double* delta);

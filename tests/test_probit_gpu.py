@@ -303,6 +303,9 @@ def test_irls_edge_cases_and_errors(gp, oracle):
         assert np.all(st[1:-1] == want) and (max_iter == 20 or np.all(it[1:-1] == 2))
         assert np.max(np.abs(f - fo)) <= 1e-8 * np.max(np.abs(fo)) and np.max(np.abs(fh - fho)) <= 1e-8 * np.max(np.abs(fho))
     ir = capi.default_params_irls()
+    # a batch without a single point: every patch as the empty ones above
+    f, al, fh, it, st = ctx.dense_irls_fit_predict(p, ir, np.zeros(4, dtype=np.int32), np.zeros(0), np.zeros(0), np.zeros(0), res=res, sz=sz)
+    assert np.all(st == 0) and np.all(it == 0) and np.all(f == 0) and al.shape == (0,) and fh.shape == (0,)
     for bad_p, bad_ir in ((capi.default_params_dense(noise_model=0), ir), (capi.default_params_dense(noise_model=2, noise=0.0), ir),
                           (p, capi.default_params_irls(max_iter=0)), (p, capi.default_params_irls(tol=-1.0))):
         with pytest.raises(capi.GpcError) as e:

@@ -178,6 +178,11 @@ def test_sparse_known_answers_and_empty(gp):
     p = capi.default_params_sparse(1)
     off = np.array([0, 0, 1, 1], dtype=np.int32)
     g = capi.Sparse(ctx, p, 3, 1)
+    # a batch without a single point: nothing is added, nothing is predicted
+    off0, none = np.zeros(4, dtype=np.int32), np.zeros(0)
+    assert g.add(off0, none, none, np.zeros((1, 0))).tolist() == [0, 0, 0] and g.sizes().tolist() == [0, 0, 0]
+    f0, s0, st0 = g.predict_points(off0, none, none, want_sigma=True)
+    assert f0.shape == (1, 0) and s0.shape == (0,) and st0.tolist() == [0, 0, 0]
     st = g.add(off, np.array([0.01]), np.array([-0.02]), np.array([[0.7]]))
     alpha, C, Q, BV = g.state()
     s20 = float(np.float32(1e-1))
@@ -583,6 +588,9 @@ def test_sparse_train_sigmaf(gp, oracle, regime):
         assert io == iters[i]
         assert abs(p0[i] - po) <= 1e-4 * abs(po)
         assert np.max(np.abs(ls[i] - lo)) <= 1e-4 * np.max(np.abs(lo))
+    # a batch without a single point: what patch 4 showed above, for every trained patch
+    p0e, iters_e, _, _ = g.train_sigmaf(np.zeros(P + 1, dtype=np.int32), np.zeros(0), np.zeros(0), np.zeros(0), step=step, max_counter=maxc)
+    assert iters_e[2] == 0 and np.all(np.delete(iters_e, 2) == 1) and np.all(p0e == kw["sigmaf_sq"])
     # argument checks
     with pytest.raises(capi.GpcError) as e:
         g.train_sigmaf(qoff, q0, q1, yq, max_counter=-1)
