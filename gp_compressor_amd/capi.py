@@ -33,6 +33,12 @@ class IrlsParams(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double), ("f_init", C.c_double)]
 
 
+class RegistrationParams(C.Structure):
+    """struct gpc_registration_params (include/gpc.h)."""
+    _fields_ = [("step", C.c_double), ("tol", C.c_double), ("min_steps", C.c_int32), ("max_steps", C.c_int32),
+                ("ref_translation_sum", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PatchesView(C.Structure):
     """struct gpc_patches_view (include/gpc.h): sizes + device addresses of a patch batch."""
     _fields_ = [("P", C.c_int32), ("n_total", C.c_int32), ("n_max", C.c_int32), ("m", C.c_int32)] + \
@@ -99,6 +105,16 @@ PROTOTYPES = {
     "gpc_patches_view_dev": (C.c_int, [_vp, _vp]),
     "gpc_patches_fetch": (C.c_int, [_vp] * 11),
     "gpc_patches_destroy": (None, [_vp]),
+    "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
+    "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "gpc_registration_destroy": (None, [_vp]),
+    "gpc_registration_set_cloud": (C.c_int, [_vp, _vp, _i]),
+    "gpc_registration_set_cloud_dev": (C.c_int, [_vp, _vp, _i]),
+    "gpc_registration_step": (C.c_int, [_vp, C.POINTER(RegistrationParams), _vp]),
+    "gpc_registration_run": (C.c_int, [_vp, C.POINTER(RegistrationParams), _vp, _vp]),
+    "gpc_registration_get_transform": (C.c_int, [_vp, _vp, _vp]),
+    "gpc_registration_get_cloud": (C.c_int, [_vp, _vp]),
+    "gpc_registration_get_assignment": (C.c_int, [_vp, _vp, _vp]),
     "gpc_partition_patches": (C.c_int, [_i, _vp, _i, _i, _vp]),
     "gpc_comm_unique_id": (C.c_int, [_vp]),
     "gpc_comm_create": (C.c_int, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
@@ -178,6 +194,14 @@ def default_params_sparse(ny=1, **kw):
 def default_params_irls(**kw):
     p = IrlsParams()
     load().gpc_default_params_irls(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_params_registration(**kw):
+    p = RegistrationParams()
+    load().gpc_default_params_registration(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -545,6 +569,72 @@ def _sparse_set_state(self, bv_count, alpha, BV, C_=None, Q=None):
 
 
 Sparse.set_state = _sparse_set_state
+
+
+class Registration:
+    """gpc_registration: gp_registration (src/gp_registration.cpp) on a model that is already on the device -- a Patches batch and
+    the depth (ny=1) and colour (ny=3) Sparse objects trained on it.  Refers to the three, owns none: keep them open while this is."""
+
+    def __init__(self, ctx, patches, depth, rgb):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = _vp()
+        ctx._check(self.lib.gpc_registration_create(ctx.h, patches.h, depth.h, rgb.h, C.byref(h)))
+        self.h = h
+        self.n = 0
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gpc_registration_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_cloud(self, cloud, n=None):
+        """add_cloud: a host record array (Context.make_cloud) or a device buffer of n records; resets the pose and the step count"""
+        if isinstance(cloud, np.ndarray):
+            assert cloud.dtype == Context.POINT_DTYPE
+            cloud = np.ascontiguousarray(cloud)
+            self.ctx._check(self.lib.gpc_registration_set_cloud(self.h, _ptr(cloud) if len(cloud) else None, len(cloud)))
+            self.n = len(cloud)
+        else:
+            self.ctx._check(self.lib.gpc_registration_set_cloud_dev(self.h, _ptr(cloud), int(n)))
+            self.n = int(n)
+
+    def step(self, params=None):
+        """one registration_step: out (9,) = delta[6], ls, cls, n_used"""
+        out = np.full(9, np.nan)
+        prm = params if params is not None else default_params_registration()
+        self.ctx._check(self.lib.gpc_registration_step(self.h, C.byref(prm), _ptr(out)))
+        return out
+
+    def run(self, params=None):
+        """steps until registration_done(): returns trace (steps, 9), one row of step() output per step"""
+        prm = params if params is not None else default_params_registration()
+        trace = np.full((max(int(prm.max_steps), 1), 9), np.nan)
+        steps = np.zeros(1, dtype=np.int32)
+        self.ctx._check(self.lib.gpc_registration_run(self.h, C.byref(prm), _ptr(trace), _ptr(steps)))
+        return trace[:min(int(steps[0]), len(trace))]
+
+    def transform(self):
+        """get_cloud_transformation: R_cloud (3, 3), t_cloud (3,)"""
+        R = np.zeros(9)
+        t = np.zeros(3)
+        self.ctx._check(self.lib.gpc_registration_get_transform(self.h, _ptr(R), _ptr(t)))
+        return R.reshape(3, 3).T.copy(), t
+
+    def cloud(self):
+        """the working cloud as a record array"""
+        c = np.zeros(self.n, dtype=Context.POINT_DTYPE)
+        self.ctx._check(self.lib.gpc_registration_get_cloud(self.h, _ptr(c) if self.n else None))
+        return c
+
+    def assignment(self):
+        """what the last step assigned: owner (n,) int32 (-1 = unused), local (n, 3) = depth, x0, x1 in the owner's frame"""
+        owner = np.full(self.n, -1, dtype=np.int32)
+        local = np.zeros((self.n, 3))
+        self.ctx._check(self.lib.gpc_registration_get_assignment(self.h, _ptr(owner), _ptr(local)))
+        return owner, local
 
 
 class Comm:

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/gpc.h"
@@ -59,12 +60,37 @@ struct gpc_ctx {
     // child has been destroyed, so a child destroyed AFTER its context finds a `dead` context instead of freed memory.
     std::atomic<int> refs{1};
     std::atomic<bool> dead{false};
+    // the live gpc_patches / gpc_sparse objects of this context (address, serial number; under mu): an object that REFERS to others
+    // without owning them (gpc_registration) asks here whether they still exist before it touches them
+    std::vector<std::pair<const void*, uint64_t>> children;
+    uint64_t next_serial = 1;
 };
 
 static inline void gpc_ctx_ref(gpc_ctx* ctx) { ctx->refs.fetch_add(1, std::memory_order_relaxed); }
 static inline void gpc_ctx_unref(gpc_ctx* ctx)
 {
     if (ctx->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete ctx;
+}
+
+// Caller holds ctx->mu.  The serial number tells an object from a later one at the same address.
+static inline uint64_t gpc_child_register(gpc_ctx* ctx, const void* obj)
+{
+    ctx->children.emplace_back(obj, ctx->next_serial);
+    return ctx->next_serial++;
+}
+static inline void gpc_child_unregister(gpc_ctx* ctx, const void* obj)
+{
+    for (size_t i = 0; i < ctx->children.size(); ++i)
+        if (ctx->children[i].first == obj) {
+            ctx->children.erase(ctx->children.begin() + (long)i);
+            return;
+        }
+}
+static inline bool gpc_child_alive(const gpc_ctx* ctx, const void* obj, uint64_t serial)
+{
+    for (const auto& c : ctx->children)
+        if (c.first == obj) return c.second == serial;
+    return false;
 }
 
 static inline int gpc_fail(gpc_ctx* ctx, int code, const char* fmt, ...)

@@ -33,20 +33,10 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "gpc_internal.h"
-
-#pragma clang fp contract(off)
+#include "producer_internal.h"   // (switches floating-point contraction off)
 
 #define PC_THREADS 256
 #define PC_WAVES (PC_THREADS / 64)
-
-struct PcGrid {
-    double mn[3];       // minimum corner (the voxel grid's anchor)
-    double res, radius, half;
-    int kmax[3];        // largest voxel coordinate per axis
-    int bx, by, bz;     // key = kz << (bx + by) | ky << bx | kx
-    int sz;
-};
 
 struct PcPoint {        // sorted-order record
     float x, y, z;
@@ -108,28 +98,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_bounds_kernel(const gpc_point_x
 }
 
 // ---- 2: keys, leaf table -----------------------------------------------------------------------------------------------
-__device__ static inline void pc_voxel(const PcGrid& g, float x, float y, float z, int k[3])
-{
-    k[0] = (int)floor(((double)x - g.mn[0]) / g.res);
-    k[1] = (int)floor(((double)y - g.mn[1]) / g.res);
-    k[2] = (int)floor(((double)z - g.mn[2]) / g.res);
-}
-__device__ static inline uint64_t pc_pack(const PcGrid& g, int kx, int ky, int kz)
-{
-    return ((uint64_t)kz << (g.bx + g.by)) | ((uint64_t)ky << g.bx) | (uint64_t)kx;
-}
-__device__ static inline void pc_unpack(const PcGrid& g, uint64_t key, int k[3])
-{
-    k[0] = (int)(key & ((1ull << g.bx) - 1));
-    k[1] = (int)((key >> g.bx) & ((1ull << g.by) - 1));
-    k[2] = (int)(key >> (g.bx + g.by));
-}
-__device__ static inline void pc_center(const PcGrid& g, const int k[3], double c[3])
-{
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = g.mn[a] + ((double)k[a] + 0.5) * g.res;
-}
-
+// (PcGrid and the key arithmetic: producer_internal.h)
 __global__ __launch_bounds__(PC_THREADS) void pc_keys_kernel(PcGrid g, const gpc_point_xyzrgb* cloud, int n, uint64_t* keys, int32_t* vals)
 {
     const int i = blockIdx.x * PC_THREADS + threadIdx.x;
@@ -563,12 +532,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_emit_kernel(PcArgs A)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-struct gpc_patches {
-    gpc_ctx* ctx = nullptr;
-    gpc_patches_view v{};       // device pointers into `block`
-    void* block = nullptr;      // one allocation holds every array of the batch
-};
-
+// (struct gpc_patches: producer_internal.h)
 namespace {
 
 int bits_for(int kmax)
@@ -644,6 +608,7 @@ static void pc_patches_release(gpc_patches* o)
     gpc_ctx* ctx = o->ctx;
     if (ctx) (void)hipSetDevice(ctx->device);
     if (ctx && ctx->hint_off == o->v.off) ctx->hint_off = nullptr;
+    if (ctx) gpc_child_unregister(ctx, o);
     if (o->block) (void)hipFree(o->block);
     delete o;
     if (ctx) gpc_ctx_unref(ctx);
@@ -684,6 +649,7 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
         PC_HIP(hipMemsetAsync(o->block, 0, 256, st));
         PC_HIP(hipStreamSynchronize(st));
         o->v.off = static_cast<int32_t*>(o->block);
+        o->serial = gpc_child_register(ctx, o);
         *out = o;
         return GPC_OK;
     }
@@ -782,11 +748,14 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
         o->v.y = oc.take<double>(N);
         o->v.rgb = oc.take<double>(3 * N);
         o->v.src = oc.take<int32_t>(N);
+        o->leaf_key = oc.take<uint64_t>(Pz);            // (last: the batch's own arrays keep their places)
         if (!pass) PC_HIP(hipMalloc(&o->block, oc.used));
     }
     PcArgs A;
     memset(&A, 0, sizeof(A));
     A.g = g; A.n = n; A.P = P;
+    S.leaf_key = const_cast<uint64_t*>(o->leaf_key);    // the leaf table outlives the call: pc_leaves_kernel writes it into the result
+    o->grid = g;
     A.leaf_key = S.leaf_key; A.leaf_start = S.leaf_start; A.leaf_of = S.leaf_of; A.vals = S.vals; A.sp = S.sp;
     A.nbr = S.nbr; A.M = S.M; A.kcount = S.kcount; A.cen = S.cen; A.owner = S.owner; A.py = S.py; A.px0 = S.px0; A.px1 = S.px1;
     A.cnt = S.cnt; A.nmax = S.cnt + (P + 1);
@@ -821,6 +790,7 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
     o->v.P = P; o->v.n_total = total; o->v.n_max = nmax[0];
     // the size classes of this batch, for the dense dispatch (keyed by the batch's own `off` buffer, which lives as long as the object)
     ctx->hint_off = o->v.off; ctx->hint_P = P; ctx->hint_le256 = nmax[1]; ctx->hint_le272 = nmax[2];
+    o->serial = gpc_child_register(ctx, o);
     *out = o;
     return GPC_OK;
 }

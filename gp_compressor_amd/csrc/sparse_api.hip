@@ -60,6 +60,7 @@ int gpc_sparse_create(gpc_ctx* ctx, const gpc_params* params, int P, int ny, gpc
         return rc;
     }
     gpc_ctx_ref(ctx);
+    g->serial = gpc_child_register(ctx, g);
     *out = g;
     return GPC_OK;
 }
@@ -71,9 +72,10 @@ void gpc_sparse_destroy(gpc_sparse* g)
     if (!g) return;
     gpc_ctx* ctx = g->ctx;
     (void)hipSetDevice(ctx->device);
-    if (!ctx->dead.load()) {
+    {
         std::lock_guard<std::mutex> lk(ctx->mu);
         if (!ctx->dead.load()) (void)hipStreamSynchronize(ctx->stream);
+        gpc_child_unregister(ctx, g);
     }
     sp_free_all(g);
     gpc_ctx_unref(ctx);

@@ -16,6 +16,7 @@ struct gpc_sparse {
     int32_t* done_it;   // P: hand-over between the phases of an add call (allocated with the object)
     int32_t* list;      // P + 4: work list of the phases after the rows phase, then its length and three ticket counters
     uint8_t* trace;     // diagnostic (gpc_sparse_set_trace): device buffer for the decision bytes of the next add calls, or nullptr
+    uint64_t serial;    // gpc_child_register
 };
 
 // kernel_function(X, X) = p(0) exp(-0.5/p(1) |X - X|^2) (src/sparse_gp.hpp:98, :316): p(0) for a finite X (X - X = +0, exp(-0) is exactly 1,

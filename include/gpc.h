@@ -83,7 +83,7 @@ void gpc_default_params_sparse(gpc_params* p, int ny);
 int gpc_version(void);
 
 /* ---- context: one per process per GPU (owns the device workspace; thread-safe per context) ---------------- */
-/* Ownership: objects created from a context (gpc_sparse, gpc_patches) hold a reference on it and may be destroyed before
+/* Ownership: objects created from a context (gpc_sparse, gpc_patches, gpc_registration) hold a reference on it and may be destroyed before
  * OR after gpc_ctx_destroy, in any order -- neither order aborts or touches freed memory.  gpc_ctx_destroy synchronises
  * the stream and releases the device workspace at once; from then on every call that takes the context, or one of its
  * surviving children, returns GPC_EINVAL, except the children's own destroy functions, which release their device
@@ -309,6 +309,57 @@ int gpc_patches_view_dev(const gpc_patches* p, gpc_patches_view* view);
 int gpc_patches_fetch(const gpc_patches* p, int32_t* off, double* x0, double* x1, double* y, double* rgb, double* rotations,
                       double* means, double* rgb_means, uint8_t* W, int32_t* src);
 void gpc_patches_destroy(gpc_patches* p);
+
+/* ---- scan-to-model registration (SURVEY section 8, row f): gp_registration on the GPU ------------------------------------ */
+/* gp_registration (src/gp_registration.h, src/gp_registration.cpp) aligns a scan to a trained model by gradient ascent on the
+ * mean likelihood of the scan's points under the per-leaf depth and colour GPs.  One step (registration_step, :73-92) is
+ *     assign   every scan point to the first leaf, in leaf order, whose search sphere holds it and whose +-res/2 window accepts
+ *              it in that leaf's frame (compute_transformation's leaf walk :146-174 + get_local_points :94-113; leaves whose
+ *              depth GP is empty are skipped, :158);
+ *     evaluate compute_derivatives + compute_likelihoods of both GPs on every leaf's points (:175-195; the kernel behind
+ *              gpc_sparse_likelihood);
+ *     reduce   dX = l dCX + cl dX (:196), rotated to the global frame (:202-206), times the 3 x 6 Jacobian of :40-49, averaged
+ *              over the points used (:211-215, :245)  ->  delta[6], ls, cls;
+ *     update   R = Rx Ry Rz, t (gradient_step :51-58), R_cloud = R R_cloud, t_cloud (+)= t (:83-84), cloud <- R cloud + t as
+ *              float (transform_pointcloud :32-38),
+ * and here it is enqueued on the context's stream from end to end: no host pass over the points, one 72-byte read-back.
+ * The model is what the other entry points produced: a gpc_patches (its voxel table decides the candidate leaves the way the
+ * reference's octree does: the <= 27 voxels around the point's own, in ascending leaf order; a point may lie one voxel outside
+ * the model's grid and still be inside a leaf's sphere) and two gpc_sparse objects trained on it, depth (ny == 1) and colour
+ * (ny == 3), Gaussian noise.  The registration object REFERS to the three and owns none of them: they must belong to the same
+ * context and have the same P (else GPC_EINVAL), and once one of them has been destroyed every call on the registration object
+ * except its own destroy returns GPC_EINVAL.  It is a child of the context like the others (destroy order is free). */
+typedef struct gpc_registration gpc_registration;
+typedef struct gpc_registration_params {
+    double step;                    /* 1e-1f, src/gp_registration.cpp:10 */
+    double tol;                     /* 0.1 on both norms, :69 */
+    int32_t min_steps, max_steps;   /* 10, 300 (:69, :10) */
+    int32_t ref_translation_sum;    /* 1 = t_cloud += t as written (:84); 0 = t_cloud = R t_cloud + t */
+    int32_t reserved;
+} gpc_registration_params;
+/* step 1e-1f, tol 0.1, min_steps 10, max_steps 300, ref_translation_sum 1 (src/gp_registration.cpp:10, :69, :84) */
+void gpc_default_params_registration(gpc_registration_params* p);
+/* the constructor's tail (src/gp_registration.cpp:7-16) without the training, which the caller has done */
+int gpc_registration_create(gpc_ctx* ctx, const gpc_patches* patches, gpc_sparse* depth, gpc_sparse* rgb, gpc_registration** out);
+void gpc_registration_destroy(gpc_registration* r);
+/* add_cloud (:60-65): the scan, n records.  Resets R_cloud = I, t_cloud = 0 and the step count.  The object keeps its own
+ * working copy (the steps move it): set_cloud takes a HOST buffer, set_cloud_dev a DEVICE buffer that it copies on the stream. */
+int gpc_registration_set_cloud(gpc_registration* r, const gpc_point_xyzrgb* cloud, int n);
+int gpc_registration_set_cloud_dev(gpc_registration* r, const gpc_point_xyzrgb* cloud, int n);
+/* one registration_step (:73-92).  out (host): delta[6] (translation, rotation), ls, cls (get_likelihood, get_color_likelihood
+ * :248-256), n_used (points that found a leaf).  No point used: all zero.  The same state gives the same bits. */
+int gpc_registration_step(gpc_registration* r, const gpc_registration_params* params, double out[9]);
+/* steps until registration_done() (:67-70): after a step has raised the step count to s, stop when s > min_steps and either
+ * s >= max_steps or both |delta[0:3]| < tol and |delta[3:6]| < tol.  trace (host, [max_steps][9], may be NULL): row k = the out
+ * of the k-th step of this call (rows beyond max_steps, possible when min_steps >= max_steps, are not written); steps: how many. */
+int gpc_registration_run(gpc_registration* r, const gpc_registration_params* params, double* trace, int32_t* steps);
+/* get_cloud_transformation (:18-22): the accumulated R_cloud [9] column-major and t_cloud [3] (host) */
+int gpc_registration_get_transform(gpc_registration* r, double R[9], double t[3]);
+/* the working cloud, n records (host) */
+int gpc_registration_get_cloud(gpc_registration* r, gpc_point_xyzrgb* cloud);
+/* Diagnostic, like gpc_sparse_set_trace: what the LAST step assigned.  owner [n]: the leaf of every scan point, -1 = unused;
+ * local [n][3]: its coordinates in that leaf's frame (depth, x0, x1).  Host pointers, each may be NULL. */
+int gpc_registration_get_assignment(gpc_registration* r, int32_t* owner, double* local);
 
 /* ---- patch -> rank partition for one process per GPU (src/gp_compressor.cpp:146-163: patches are independent) ----- */
 /* Longest-processing-time assignment of P patches with per-patch cost n_i^3 (dense) or n_i*cap^2 (sparse) onto
