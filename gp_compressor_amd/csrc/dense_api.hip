@@ -1,0 +1,311 @@
+// dense_api.hip -- the dense path on device pointers: argument checks, the dispatcher that chooses the kernels of a batch, the
+// dense and IRLS _dev entries and the host-pointer IRLS entry.  The pipelined host-pointer dense entries are in dense_host.hip.
+#include <cstdlib>
+
+#include "dense_internal.h"
+
+int dense_check(gpc_ctx* ctx, const gpc_params* prm, int P, const void* off, int n_max, int n_total,
+                const void* x0, const void* x1, const void* y, int ny, int m, const void* f_star)
+{
+    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
+    if (!prm) return gpc_fail(ctx, GPC_EINVAL, "params is NULL");
+    if (P < 0 || m < 0 || n_total < 0 || n_max < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (ny != 1 && ny != 3) return gpc_fail(ctx, GPC_EINVAL, "ny must be 1 (depth) or 3 (RGB), got %d", ny);
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (P > 0 && m > 0 && !f_star) return gpc_fail(ctx, GPC_EINVAL, "f_star is NULL");
+    if (n_max > GPC_MAX_POINTS) return gpc_fail(ctx, GPC_ERANGE, "n_max %d > GPC_MAX_POINTS %d", n_max, GPC_MAX_POINTS);
+    if (!(prm->l_sq > 0.0) || !(prm->sigmaf_sq >= 0.0) || !(prm->noise >= 0.0))
+        return gpc_fail(ctx, GPC_EINVAL, "kernel/noise parameters out of range");
+    return GPC_OK;
+}
+
+DenseArgs dense_args(const gpc_params* prm, int P, const int32_t* off, int n_max, int n_total, const double* x0, const double* x1,
+                     const double* y, int ny, int m, double* f_star, double* alpha_out, int32_t* status)
+{
+    DenseArgs a{};
+    a.prm = *prm;
+    a.P = P; a.n_max = n_max; a.n_total = n_total; a.ny = ny; a.m = m;
+    a.off = off; a.x0 = x0; a.x1 = x1; a.y = y;
+    a.f_star = f_star; a.alpha_out = alpha_out; a.status = status;
+    return a;
+}
+
+// Ragged batches whose largest patch exceeds the register-resident kernel's 256 points: patches are sorted into size classes on
+// the device (no host round trip: `off` lives there) -- n <= 256 -> the register-resident kernel, 256 < n <= 272 -> its NT = 17
+// shape (depth plane only: the octree leaves of a cloud cut for 256-point patches scatter around that size, median 258, and
+// would otherwise pay the tiled kernel's 4x cost per patch), the rest -> the tiled kernel.  Patches are independent, so the
+// order inside a class does not matter.
+extern "C" __global__ void dense_classify_kernel(int P, const int32_t* off, int bound0, int bound1, int32_t* sel0, int32_t* sel1, int32_t* sel2,
+                                                 int32_t* counts)
+{
+    // one atomic per wave and class (a counter takes ~11 ns per atomic device-wide: with one per patch the 8192 patches of a
+    // single-class batch spent 95 us here, 0.8 % of a C3 launch and 5 % of a C2-sized one)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int n = i < P ? off[i + 1] - off[i] : 0;
+    const int cls = i >= P ? -1 : n <= bound0 ? 0 : n <= bound1 ? 1 : 2;
+    int32_t* const sel[3] = {sel0, sel1, sel2};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(cls == c);
+        if (m == 0) continue;
+        int base = 0;
+        if (lane == __builtin_ctzll(m)) base = atomicAdd(&counts[c], __builtin_popcountll(m));
+        base = __builtin_amdgcn_readlane(base, __builtin_ctzll(m));
+        if (cls == c) sel[c][base + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = i;
+    }
+}
+
+bool dense_w1_takes(const gpc_ctx* ctx, const DenseArgs& a)
+{
+    const char* mp = getenv("GPC_W1_MIN_P");
+    const int min_p = mp ? atoi(mp) : 4 * ctx->num_cus;
+    const bool force = getenv("GPC_FORCE_GENERIC") || getenv("GPC_FORCE_BIG");
+    // (round 4: the kernel's 512-point instance takes the depth plane of batches whose largest patch has 257 .. 512 points -- C3, and the
+    // ragged batches of a cloud cut for 256-point patches, which the size-class split used to deal to three kernels; GPC_NO_W1_512=1: as before)
+    if (a.n_max > 256 && getenv("GPC_NO_W1_512")) return false;
+    return !force && a.n_max <= 512 && a.P >= min_p && a.P > 1 && (a.n_max > 192 || !a.v_star) && dense_w1_supported(a) && !getenv("GPC_NO_W1");
+}
+
+// the tiled kernel's workspace for `a`, reserved at the site; its grid comes back in *grid
+static int dense_big_reserve(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int* grid)
+{
+    return gpc_ws_reserve(ctx, site, (dense_big_ws_bytes(ctx, a, grid) + 255) & ~(size_t)255);
+}
+
+// Caller holds ctx->mu.
+int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* seen_gen)
+{
+    if (a.P == 0 || (a.m == 0 && !a.alpha_out)) return GPC_OK;
+    if (a.n_max < 1) a.n_max = 1;
+    if (seen_gen)      // a chunk of the two-stream host pipeline
+        if (int rco = gpc_pipe_chunk_order(ctx, site.stream, seen_gen)) return rco;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (!a.prm.want_variance) a.v_star = nullptr;
+    if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
+    const bool force_generic = getenv("GPC_FORCE_GENERIC") != nullptr, force_big = getenv("GPC_FORCE_BIG") != nullptr;
+    const bool ny_ok = a.ny == 1 || a.ny == 3;
+    if (!force_generic && !force_big && ny_ok) {
+        const bool no_split = a.P == 1 || getenv("GPC_NO_SPLIT");
+        // Depth plane, n <= 256, a batch large enough to fill the chip: ONE wave per patch, eight patches per CU (dense_mfma_w1.hip) --
+        // no hand-over between waves at all.  Measured against the register-resident kernel at 8192 patches: 256 points 1.72 against
+        // 2.57 ms, 192: 0.98 / 1.70, 128: 0.48 / 1.06, 64: 0.20 / 0.62; at 512 patches the two are level, below that the register kernel's
+        // eight waves per patch win on latency (64 patches x 192 points: 0.066 against 0.134 ms) -- hence the batch-size rule
+        // (GPC_W1_MIN_P overrides it; the variance goes this way for 193 .. 256 points, where its solve kernel is the <16> shape).
+        if (dense_w1_takes(ctx, a)) {
+            // One factor slot (304 KB) per patch of a launch.  If the device cannot serve that, the batch goes
+            // through in smaller launches that reuse fewer slots, and below two launches' worth of resident patches it takes the
+            // register-resident kernel, which needs no workspace at all.
+            int grid_w1 = 0, rcw = GPC_ENOMEM;
+            DenseArgs aw = a;
+            for (int cap_w1 = 0;;) {
+                const size_t w1_bytes = (dense_w1_ws_bytes(ctx, aw, &grid_w1, cap_w1) + 255) & ~(size_t)255;
+                rcw = gpc_ws_reserve(ctx, site, w1_bytes);
+                if (rcw != GPC_ENOMEM) break;
+                cap_w1 = grid_w1 / 2;
+                if (cap_w1 < 4 * ctx->num_cus) break;             // (below the batch-size rule of this kernel)
+            }
+            if (rcw == GPC_OK) return dense_w1_launch(ctx, site, a, grid_w1);
+            if (rcw != GPC_ENOMEM || a.v_star) return rcw;
+            (void)hipGetLastError();
+        }
+        // (GPC_W2=1: the two-wave shape of the tiled kernel, round 3's first headline kernel, kept as a cross-check)
+        if (a.n_max > 192 && a.n_max <= 256 && a.ny == 1 && !a.v_star && a.P > 1 && getenv("GPC_W2")) {
+            int grid_w2 = 0;
+            if (int rcw = dense_big_reserve(ctx, site, a, &grid_w2)) return rcw;
+            return dense_big_launch(ctx, site, a, grid_w2);
+        }
+        if (a.n_max <= 256 || (no_split && dense_mfma_supported(a) && !getenv("GPC_NO_NT17")))
+            return dense_mfma_launch(ctx, site, a);                                                         // one shape for the whole batch
+        // (a batch whose patches all have n_max points -- P n_max == n_total: every n_i <= n_max and they add up to n_total -- has one
+        // size class and the host knows it: no classification, no empty class launches waiting for a CU beside the tiled kernel)
+        const bool uniform = (long long)a.P * a.n_max == (long long)a.n_total;
+        if (!a.v_star && a.n_max <= GPC_MAX_POINTS && !no_split && !(uniform && a.n_max > 17 * 16)) {
+            const bool nt17 = a.ny == 1 && !getenv("GPC_NO_NT17");
+            const bool need_big = !(nt17 && a.n_max <= 17 * 16);
+            int grid_b = 0;
+            const size_t big_bytes = need_big ? (dense_big_ws_bytes(ctx, a, &grid_b) + 255) & ~(size_t)255 : 0;
+            // Class sizes known on the host (the batch came from gpc_project_cloud on this context): the class launches get exactly that
+            // many workgroups.  The hint is matched by pointer and P only -- a caller that rewrites `off` IN PLACE keeps both -- so every
+            // hinted launch is followed by an OVERFLOW launch of the generic kernel (a few workgroups that stride over
+            // sel[hint .. count), count on the device: no patch when the hint was right, every patch the hint missed otherwise).
+            const bool hinted = ctx->hint_off == a.off && ctx->hint_P == a.P && !getenv("GPC_NO_HINT");
+            constexpr int OVF_GRID = 8;
+            const size_t ovf_slot = sizeof(double) * (size_t)(17 * 16 + a.ny) * (size_t)(17 * 16 + a.ny);
+            const size_t ovf_bytes = hinted ? (2 * OVF_GRID * ovf_slot + 255) & ~(size_t)255 : 0;
+            int rc = gpc_ws_reserve(ctx, site, big_bytes + ovf_bytes + sizeof(int32_t) * (3 * (size_t)a.P + 64));
+            if (rc != GPC_OK) return rc;
+            double* ovf_ws = reinterpret_cast<double*>(dense_ws(ctx, site) + big_bytes);
+            int32_t* counts = reinterpret_cast<int32_t*>(dense_ws(ctx, site) + big_bytes + ovf_bytes);
+            int32_t* sel0 = counts + 64;
+            int32_t* sel1 = sel0 + a.P;
+            int32_t* sel2 = sel1 + a.P;
+            GPC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), site.stream));
+            hipLaunchKernelGGL(dense_classify_kernel, dim3((a.P + 255) / 256), dim3(256), 0, site.stream, a.P, a.off, 256, nt17 ? 17 * 16 : 256,
+                               sel0, sel1, sel2, counts);
+            GPC_HIP(ctx, hipGetLastError());
+            // The classes are independent: they run on three streams (forked from and joined to the site's), so that
+            // the tail of one kernel -- its last workgroups running on a mostly idle chip -- fills with the next one's work.
+            const hipStream_t main_s = site.stream;
+            const DenseSite on_in{ctx->s_in, site.ws_off, site.ws_len}, on_out{ctx->s_out, site.ws_off, site.ws_len};
+            // an error after the fork must not leave work (or the caller's buffers) in flight on the side streams
+            auto bail = [&](int code) {
+                (void)hipStreamSynchronize(ctx->s_in);
+                (void)hipStreamSynchronize(ctx->s_out);
+                return code;
+            };
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[0][GPC_EV_CLASS_FORK], main_s));
+            GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_in, ctx->ev[0][GPC_EV_CLASS_FORK], 0));
+            GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_out, ctx->ev[0][GPC_EV_CLASS_FORK], 0));
+            // largest patches first: the tiled kernel's workgroups are the long ones
+            if (need_big) {
+                DenseArgs b = a;
+                b.sel = sel2; b.sel_count = counts + 2;
+                rc = dense_big_launch(ctx, on_out, b, grid_b);
+                if (rc != GPC_OK) return bail(rc);
+            }
+            // Class `which` (0: n <= 256, 1: the NT = 17 shape) on the register kernel, `cnt` workgroups at `at`.  Without a hint cnt is P: the
+            // workgroups beyond the class count leave at once, but each still waits for a CU with 158 KB of LDS free.  With one, the overflow
+            // launch follows on the same stream; a class the hint calls empty is its overflow launch alone, on the main stream.
+            auto run_class = [&](int which, int cnt, const DenseSite& at) -> int {
+                DenseArgs s = a;
+                s.n_max = which ? 17 * 16 : 256;
+                s.sel = which ? sel1 : sel0; s.sel_count = counts + which;
+                s.P = cnt;
+                const int rcl = cnt > 0 ? dense_mfma_launch(ctx, at, s) : GPC_OK;
+                if (rcl != GPC_OK || !hinted || cnt >= a.P) return rcl;
+                s.sel_base = cnt;
+                s.P = a.P;
+                return dense_generic_launch(ctx, cnt > 0 ? at : site, s, OVF_GRID, ovf_ws + (size_t)which * OVF_GRID * (ovf_slot / sizeof(double)));
+            };
+            const int c0 = hinted ? ctx->hint_le256 : a.P;
+            const int c1 = hinted ? ctx->hint_le272 - ctx->hint_le256 : a.P;
+            if (nt17 && (rc = run_class(1, c1, on_in)) != GPC_OK) return bail(rc);
+            if ((rc = run_class(0, c0, site)) != GPC_OK) return bail(rc);
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[1][GPC_EV_CLASS_FORK], ctx->s_in));
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[2][GPC_EV_CLASS_FORK], ctx->s_out));
+            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][GPC_EV_CLASS_FORK], 0));
+            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][GPC_EV_CLASS_FORK], 0));
+            ctx->last_dense_kernel = !need_big ? "dense_mfma_nt16 + dense_mfma_nt17" : nt17 ? "dense_mfma_nt16 + dense_mfma_nt17 + dense_mfma_big"
+                                                                                             : "dense_mfma_nt16 + dense_mfma_big";
+            return rc;
+        }
+    }
+    if ((dense_big_supported(a) || (force_big && a.n_max <= 1024 && !a.v_star)) && !force_generic) {   // GPC_FORCE_BIG: diagnostic
+        int grid_b = 0;
+        if (int rcb = dense_big_reserve(ctx, site, a, &grid_b)) return rcb;
+        return dense_big_launch(ctx, site, a, grid_b);
+    }
+    int grid = 0;
+    size_t bytes = dense_generic_ws_bytes(ctx, a, &grid);
+    int rc = gpc_ws_reserve(ctx, site, bytes);
+    if (rc != GPC_OK) return rc;
+    return dense_generic_launch(ctx, site, a, grid);
+}
+
+extern "C" {
+
+int gpc_dense_fit_predict_dev(gpc_ctx* ctx, const gpc_params* params, int P, const int32_t* off, int n_max, int n_total,
+                              const double* x0, const double* x1, const double* y, int ny,
+                              int m, const double* xs0, const double* xs1,
+                              double* f_star, double* v_star, double* alpha_out, int32_t* status)
+{
+    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, ny, m, f_star);
+    if (rc != GPC_OK) return rc;
+    if (m > 0 && (!xs0 || !xs1)) return gpc_fail(ctx, GPC_EINVAL, "xs0/xs1 is NULL");
+    DenseArgs a = dense_args(params, P, off, n_max, n_total, x0, x1, y, ny, m, f_star, alpha_out, status);
+    a.xs0 = xs0; a.xs1 = xs1;
+    a.v_star = v_star;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return dense_dispatch(ctx, a, dense_site_of(ctx));
+}
+
+int gpc_dense_fit_predict_grid_dev(gpc_ctx* ctx, const gpc_params* params, int P, const int32_t* off, int n_max,
+                                   int n_total, const double* x0, const double* x1, const double* y, int ny,
+                                   double res, int sz, double* f_star, double* alpha_out, int32_t* status)
+{
+    if (ctx && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
+    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, ny, sz * sz, f_star);
+    if (rc != GPC_OK) return rc;
+    DenseArgs a = dense_args(params, P, off, n_max, n_total, x0, x1, y, ny, sz * sz, f_star, alpha_out, status);
+    a.prm.want_variance = 0;
+    a.grid_res = res; a.grid_sz = sz;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return dense_dispatch(ctx, a, dense_site_of(ctx));
+}
+
+// ------------------------------------------------------------------------------------------------ probit / IRLS (config 5)
+
+int gpc_dense_irls_fit_predict_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                   int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
+                                   const double* xs0, const double* xs1, double res, int sz, double* f_star, double* alpha_out,
+                                   double* fhat_out, int32_t* iters, int32_t* status)
+{
+    const bool grid = (xs0 == nullptr);
+    if (ctx && grid && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
+    if (grid) m = sz * sz;
+    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
+    if (rc != GPC_OK) return rc;
+    if (!irls) return gpc_fail(ctx, GPC_EINVAL, "irls is NULL");
+    if (params->noise_model != 1 && params->noise_model != 2)
+        return gpc_fail(ctx, GPC_EINVAL, "the IRLS loop needs a probit noise_model (1 or 2), got %d", params->noise_model);
+    if (irls->max_iter < 1 || !(irls->tol >= 0.0) || !(irls->f_init == irls->f_init))
+        return gpc_fail(ctx, GPC_EINVAL, "irls parameters out of range");
+    if (!(params->noise > 0.0)) return gpc_fail(ctx, GPC_EINVAL, "s20 (params->noise) must be positive");
+    if (!grid && m > 0 && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
+    if (P == 0) return GPC_OK;
+    DenseArgs a = dense_args(params, P, off, n_max < 1 ? 1 : n_max, n_total, x0, x1, y, 1, m, f_star, alpha_out, status);
+    a.prm.want_variance = 0;
+    a.xs0 = xs0; a.xs1 = xs1;
+    a.grid_res = grid ? res : 0.0; a.grid_sz = grid ? sz : 0;
+    IrlsArgs ir{irls->max_iter, irls->tol, irls->f_init, iters, fhat_out};
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const DenseSite site = dense_site_of(ctx);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
+    int grid_b = 0;
+    if ((rc = dense_big_reserve(ctx, site, a, &grid_b))) return rc;
+    return dense_irls_launch(ctx, site, a, ir, grid_b);
+}
+
+int gpc_dense_irls_fit_predict(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                               const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
+                               double res, int sz, double* f_star, double* alpha_out, double* fhat_out, int32_t* iters,
+                               int32_t* status)
+{
+    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
+    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    const bool grid = (xs0 == nullptr);
+    if (grid) {
+        if (sz < 0 || sz > 1024) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
+        m = sz * sz;
+    }
+    int n_max = 0, n_total = 0;
+    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
+    if (rc != GPC_OK) return rc;
+    rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
+    if (rc != GPC_OK) return rc;
+    if (P == 0) return GPC_OK;
+    if (!grid && m && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)n_total, Pz = (size_t)P, Pm = Pz * (size_t)m;
+    GpcStaging st(ctx, "gpc_dense_irls_fit_predict");
+    const int32_t* d_off = st.up(off, Pz + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
+    const double *d_xs0 = grid ? nullptr : st.up(xs0, (size_t)m), *d_xs1 = grid ? nullptr : st.up(xs1, (size_t)m);
+    double *d_f = st.out<double>(Pm), *d_al = st.out<double>(N), *d_fh = st.out<double>(N);
+    int32_t *d_it = st.out<int32_t>(Pz), *d_st = st.out<int32_t>(Pz);
+    if (st.ok())
+        st.rc = gpc_dense_irls_fit_predict_dev(ctx, params, irls, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res, sz, d_f, d_al,
+                                               d_fh, d_it, d_st);
+    st.down(f_star, d_f, Pm);
+    st.down(alpha_out, d_al, N);
+    st.down(fhat_out, d_fh, N);
+    st.down(iters, d_it, Pz);
+    st.down(status, d_st, Pz);
+    return st.finish();
+}
+
+}  // extern "C"

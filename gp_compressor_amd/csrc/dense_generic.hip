@@ -14,7 +14,7 @@
 // falls out of the panel TRSM.  This kernel is the correctness anchor and the path for n > 256; the n <= 256
 // bench path is dense_mfma.hip.
 #include "gpc_device.h"
-#include "gpc_internal.h"
+#include "dense_internal.h"
 
 #define GEN_THREADS 256
 #define GEN_NB 16
@@ -358,13 +358,13 @@ size_t dense_generic_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_
     return (size_t)grid * slot * sizeof(double);
 }
 
-int dense_generic_launch(gpc_ctx* ctx, const DenseArgs& a, int grid, double* ws_override)
+int dense_generic_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid, double* ws_override)
 {
     GenParams g;
     g.a = a;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.pivot_tol = GPC_PIVOT_RTOL * (a.prm.sigmaf_sq + a.prm.noise);
-    g.ws = ws_override ? ws_override : static_cast<double*>(ctx->ws);
+    g.ws = ws_override ? ws_override : reinterpret_cast<double*>(dense_ws(ctx, site));
     g.ld = a.n_max + a.ny;
     g.mpad = (a.m + 63) & ~63;
     g.slot = (size_t)g.ld * g.ld + (a.v_star ? (size_t)a.n_max * g.mpad : 0);
@@ -372,7 +372,7 @@ int dense_generic_launch(gpc_ctx* ctx, const DenseArgs& a, int grid, double* ws_
     // per call: the attribute is per device, and a process may hold contexts on several GPUs (idempotent, host-side only)
     GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_generic_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(dense_generic_kernel, dim3(grid), dim3(GEN_THREADS), lds, ctx->stream, g);
+    hipLaunchKernelGGL(dense_generic_kernel, dim3(grid), dim3(GEN_THREADS), lds, site.stream, g);
     GPC_HIP(ctx, hipGetLastError());
     ctx->last_dense_kernel = "dense_generic";
     return GPC_OK;

@@ -1,0 +1,97 @@
+// dense_internal.h -- host-side definitions of the dense path: the arguments of a batch, where a call runs, the dispatcher and the
+// launchers of the kernel translation units (not part of the C-ABI).
+#pragma once
+
+#include "gpc_internal.h"
+
+struct DenseArgs {
+    gpc_params prm;
+    int P, n_max, n_total, ny, m;
+    const int32_t* off;
+    const double *x0, *x1, *y;
+    const double *xs0, *xs1;   // point-wise X* (m entries) or nullptr when the grid form is used
+    double grid_res;           // grid form: res, sz (m = sz*sz)
+    int grid_sz;
+    double *f_star, *v_star, *alpha_out;
+    int32_t* status;
+    // size-class dispatch of a ragged batch (dense_api.hip): when sel != nullptr a kernel works on the patches sel[0 .. *sel_count)
+    // (both on the device) instead of 0 .. P-1
+    const int32_t* sel;
+    const int32_t* sel_count;
+    int sel_base;              // generic kernel only: it works on sel[sel_base .. *sel_count) -- the overflow launch behind a class launch that
+                               // was sized from a host-side hint (dense_api.hip)
+};
+
+// Where a dense call runs.  A host-side value handed from the dispatcher to the launchers, never part of a kernel-parameter struct.
+struct DenseSite {
+    hipStream_t stream;     // every launch, memset and event record of the call in hand
+    size_t ws_off, ws_len;  // the region of ctx->ws it may use; ws_len == 0: the whole workspace, not a chunk of the host-pointer pipeline
+};
+
+// a call on the context's stream that may use the whole workspace (caller holds ctx->mu)
+static inline DenseSite dense_site_of(const gpc_ctx* ctx) { return DenseSite{ctx->stream, 0, 0}; }
+// the site's region of the workspace; ask AFTER the reserve, which may move ctx->ws
+static inline char* dense_ws(const gpc_ctx* ctx, const DenseSite& site) { return static_cast<char*>(ctx->ws) + site.ws_off; }
+// ... and how much of it the workspace holds as it stands
+static inline size_t dense_ws_len(const gpc_ctx* ctx, const DenseSite& site)
+{
+    const size_t rest = ctx->ws_bytes > site.ws_off ? ctx->ws_bytes - site.ws_off : 0;
+    return site.ws_len && site.ws_len < rest ? site.ws_len : rest;
+}
+// `bytes` within the site's region
+static inline int gpc_ws_reserve(gpc_ctx* ctx, const DenseSite& site, size_t bytes)
+{
+    return gpc_ws_reserve(ctx, site.stream, site.ws_len != 0, site.ws_off + bytes);
+}
+// GPC_POISON_LDS for a dense call: launched on the site's stream, and only the site's region of the workspace is filled
+int gpc_debug_poison_lds(gpc_ctx* ctx, const DenseSite& site);
+
+// ---- dispatcher (dense_api.hip), also used by the host-pointer pipeline (dense_host.hip) ----------------------
+
+int dense_check(gpc_ctx* ctx, const gpc_params* prm, int P, const void* off, int n_max, int n_total,
+                const void* x0, const void* x1, const void* y, int ny, int m, const void* f_star);
+// the device-pointer arguments shared by the dense and IRLS entries; the rest of DenseArgs stays zero
+DenseArgs dense_args(const gpc_params* prm, int P, const int32_t* off, int n_max, int n_total, const double* x0, const double* x1,
+                     const double* y, int ny, int m, double* f_star, double* alpha_out, int32_t* status);
+// the one-wave kernel takes this batch (the rule of dense_dispatch, also asked by dense_host before it splits a batch over two streams)
+bool dense_w1_takes(const gpc_ctx* ctx, const DenseArgs& a);
+// Chooses the kernels of a batch and launches them at `site`; caller holds ctx->mu.  `seen_gen`: a chunk of the two-stream host-pointer
+// pipeline hands in gpc_ctx::foreign_gen as its compute stream last saw it (gpc_pipe_chunk_order); nullptr everywhere else.
+int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* seen_gen = nullptr);
+
+// ---- launchers implemented in the kernel translation units -------------------------------------------------
+
+// generic kernel: any n <= GPC_MAX_POINTS, K/L in a global-memory workspace slot per workgroup
+size_t dense_generic_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out);
+int dense_generic_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid, double* ws_override = nullptr);
+
+// register-tile MFMA kernel: n <= 256, trailing matrix resident in VGPRs (see dense_mfma.hip)
+bool dense_mfma_supported(const DenseArgs& a);
+int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a);
+
+// predictive variance from the exported factor of the register-tile kernel (dense_variance.hip): V* [P][m]
+int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int nt_max, const double* factor, const double* alpha,
+                          double* v_star);
+
+// ... and from the tiled kernel's per-patch factor slots (n <= 1024); scratch: V blocks of the waves in flight
+size_t big_slot_doubles(int ntw);
+size_t dense_variance_big_scratch_doubles(const gpc_ctx* ctx, int ntw);
+int dense_variance_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
+                              const double* alpha, double* scratch, double* v_star);
+
+// tiled left-looking MFMA kernel: 256 < n <= 1024, factor in a global-memory workspace slot per workgroup (see dense_mfma_big.hip)
+bool dense_big_supported(const DenseArgs& a);
+size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out);
+int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid);
+// one wave per patch, eight patches per CU: n <= 256, depth plane, mean only (see dense_mfma_w1.hip) -- the C2 headline kernel
+bool dense_w1_supported(const DenseArgs& a);
+size_t dense_w1_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out, int cap = 0);
+int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid);
+// the same kernel inside the Newton / IRLS loop of the probit variant (BASELINE config 5; any n <= 1024, ny == 1)
+struct IrlsArgs {
+    int max_iter;
+    double tol, f_init;
+    int32_t* iters;   // [P] or nullptr
+    double* fhat;     // [n_total] or nullptr
+};
+int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const IrlsArgs& ir, int grid);

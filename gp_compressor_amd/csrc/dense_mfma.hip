@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "gpc_device.h"
-#include "gpc_internal.h"
+#include "dense_internal.h"
 #include "mfma_tile.h"
 
 
@@ -881,13 +881,13 @@ bool dense_mfma_supported(const DenseArgs& a)
 }
 
 template <int NT, bool EXPORT = false>
-static int launch_nt(gpc_ctx* ctx, const MfmaParams& g, int grid, const char* name)
+static int launch_nt(gpc_ctx* ctx, hipStream_t stream, const MfmaParams& g, int grid, const char* name)
 {
     const size_t lds = sizeof(double) * (size_t)mf_l_total(NT);
     // per call: the attribute is per device, and a process may hold contexts on several GPUs (idempotent, host-side only)
     GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_mfma_kernel<NT, EXPORT>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((dense_mfma_kernel<NT, EXPORT>), dim3(grid), dim3(MF_THREADS), lds, ctx->stream, g);
+    hipLaunchKernelGGL((dense_mfma_kernel<NT, EXPORT>), dim3(grid), dim3(MF_THREADS), lds, stream, g);
     GPC_HIP(ctx, hipGetLastError());
     ctx->last_dense_kernel = name;
     return GPC_OK;
@@ -896,7 +896,7 @@ static int launch_nt(gpc_ctx* ctx, const MfmaParams& g, int grid, const char* na
 // Predictive variance (gaussian_process::predict_measurements, /root/reference/src/gaussian_process.cpp:35-43): the fit runs as
 // usual and additionally writes its factor (operand images of every L_ik and of the L_ii^-1) into the context's workspace,
 // 272 KB per patch at NT = 16; dense_variance.hip then evaluates V* = k** - ||L^-1 k*||^2 from there.
-int dense_mfma_launch(gpc_ctx* ctx, const DenseArgs& a_in)
+int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
@@ -906,28 +906,28 @@ int dense_mfma_launch(gpc_ctx* ctx, const DenseArgs& a_in)
     if (v_star) {
         if (a.sel) return gpc_fail(ctx, GPC_EINVAL, "variance + size-class dispatch is not supported");
         fbytes = sizeof(double) * (size_t)a.P * (nt_max * (nt_max + 1) / 2) * MF_IMG;
-        const int rc = gpc_ws_reserve(ctx, fbytes + sizeof(double) * (size_t)a.n_total * a.ny);
+        const int rc = gpc_ws_reserve(ctx, site, fbytes + sizeof(double) * (size_t)a.n_total * a.ny);
         if (rc != GPC_OK) return rc;
         // the variance kernel evaluates K* anyway: it forms the mean from the same tiles, so the fit predicts nothing
         a.m = 0;
-        if (!a.alpha_out) a.alpha_out = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + fbytes);
+        if (!a.alpha_out) a.alpha_out = reinterpret_cast<double*>(dense_ws(ctx, site) + fbytes);
     }
     MfmaParams g;
     g.a = a;
-    g.export_L = v_star ? static_cast<double*>(ctx->ws) : nullptr;
+    g.export_L = v_star ? reinterpret_cast<double*>(dense_ws(ctx, site)) : nullptr;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.pivot_tol = GPC_PIVOT_RTOL * (a.prm.sigmaf_sq + a.prm.noise);
     g.stamps = nullptr;
     const int grid = a.P;         // one workgroup per patch
 #ifdef MF_STAMPS
     GPC_HIP(ctx, hipMalloc(&g.stamps, sizeof(unsigned long long) * (size_t)grid * MF_WAVES * MF_NPH));
-    GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * (size_t)grid * MF_WAVES * MF_NPH, ctx->stream));
+    GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * (size_t)grid * MF_WAVES * MF_NPH, site.stream));
     struct StampDump {
-        gpc_ctx* ctx; unsigned long long* d; int grid;
+        hipStream_t stream; unsigned long long* d; int grid;
         ~StampDump()
         {
             std::vector<unsigned long long> h((size_t)grid * MF_WAVES * MF_NPH);
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(stream);
             (void)hipMemcpy(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
             (void)hipFree(d);
             static const char* names[MF_NPH] = {"load+gram", "wait ready | B2 (factor)", "trsm | z+publish (factor)", "wait B2 | y_j (factor)",
@@ -954,17 +954,17 @@ int dense_mfma_launch(gpc_ctx* ctx, const DenseArgs& a_in)
             }
             fprintf(stderr, "\n");
         }
-    } dump{ctx, g.stamps, grid};
+    } dump{site.stream, g.stamps, grid};
 #endif
 #ifdef MF_TRACE
     GPC_HIP(ctx, hipMalloc(&g.stamps, sizeof(unsigned long long) * (size_t)grid * MF_WAVES * MF_NTR));
-    GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * (size_t)grid * MF_WAVES * MF_NTR, ctx->stream));
+    GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * (size_t)grid * MF_WAVES * MF_NTR, site.stream));
     struct TraceDump {
-        gpc_ctx* ctx; unsigned long long* d; int grid;
+        hipStream_t stream; unsigned long long* d; int grid;
         ~TraceDump()
         {
             std::vector<unsigned long long> h((size_t)grid * MF_WAVES * MF_NTR);
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(stream);
             (void)hipMemcpy(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
             (void)hipFree(d);
             std::vector<double> sum((size_t)MF_WAVES * MF_NTR, 0.0), cnt((size_t)MF_WAVES * MF_NTR, 0.0);
@@ -998,22 +998,22 @@ int dense_mfma_launch(gpc_ctx* ctx, const DenseArgs& a_in)
                 fprintf(stderr, "\n");
             }
         }
-    } tdump{ctx, g.stamps, grid};
+    } tdump{site.stream, g.stamps, grid};
 #endif
     if (v_star) {
         int rc;
-        if (nt_max == 4) rc = launch_nt<4, true>(ctx, g, grid, "dense_mfma_nt4 + dense_variance");
-        else if (nt_max == 8) rc = launch_nt<8, true>(ctx, g, grid, "dense_mfma_nt8 + dense_variance");
-        else if (nt_max == 12) rc = launch_nt<12, true>(ctx, g, grid, "dense_mfma_nt12 + dense_variance");
-        else rc = launch_nt<16, true>(ctx, g, grid, "dense_mfma_nt16 + dense_variance");
+        if (nt_max == 4) rc = launch_nt<4, true>(ctx, site.stream, g, grid, "dense_mfma_nt4 + dense_variance");
+        else if (nt_max == 8) rc = launch_nt<8, true>(ctx, site.stream, g, grid, "dense_mfma_nt8 + dense_variance");
+        else if (nt_max == 12) rc = launch_nt<12, true>(ctx, site.stream, g, grid, "dense_mfma_nt12 + dense_variance");
+        else rc = launch_nt<16, true>(ctx, site.stream, g, grid, "dense_mfma_nt16 + dense_variance");
         if (rc != GPC_OK) return rc;
         DenseArgs av = a;
         av.m = a_in.m;
-        return dense_variance_launch(ctx, av, nt_max, g.export_L, a.alpha_out, v_star);
+        return dense_variance_launch(ctx, site, av, nt_max, g.export_L, a.alpha_out, v_star);
     }
-    if (a.n_max <= 64) return launch_nt<4>(ctx, g, grid, "dense_mfma_nt4");
-    if (a.n_max <= 128) return launch_nt<8>(ctx, g, grid, "dense_mfma_nt8");
-    if (a.n_max <= 192) return launch_nt<12>(ctx, g, grid, "dense_mfma_nt12");
-    if (a.n_max <= 256) return launch_nt<16>(ctx, g, grid, "dense_mfma_nt16");
-    return launch_nt<17>(ctx, g, grid, "dense_mfma_nt17");
+    if (a.n_max <= 64) return launch_nt<4>(ctx, site.stream, g, grid, "dense_mfma_nt4");
+    if (a.n_max <= 128) return launch_nt<8>(ctx, site.stream, g, grid, "dense_mfma_nt8");
+    if (a.n_max <= 192) return launch_nt<12>(ctx, site.stream, g, grid, "dense_mfma_nt12");
+    if (a.n_max <= 256) return launch_nt<16>(ctx, site.stream, g, grid, "dense_mfma_nt16");
+    return launch_nt<17>(ctx, site.stream, g, grid, "dense_mfma_nt17");
 }

@@ -32,7 +32,7 @@
 #include <cstdlib>
 
 #include "gpc_device.h"
-#include "gpc_internal.h"
+#include "dense_internal.h"
 #include "mfma_tile.h"
 
 
@@ -993,25 +993,25 @@ size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out)
 }
 
 template <int W, int NP, int RM, int OC, bool IRLS = false, int NYP = 3>
-static int big_launch_t(gpc_ctx* ctx, const BigParams& g, int grid)
+static int big_launch_t(gpc_ctx* ctx, hipStream_t stream, const BigParams& g, int grid)
 {
     const size_t lds = sizeof(double) * (size_t)bg_lds_doubles(NP, 4, NYP, W == 2);
     // per call: the attribute is per device, and a process may hold contexts on several GPUs (idempotent, host-side only)
     GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_big_kernel<W, NP, RM, OC, IRLS, 4, NYP>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((dense_big_kernel<W, NP, RM, OC, IRLS, 4, NYP>), dim3(grid), dim3(W * 64), lds, ctx->stream, g);
+    hipLaunchKernelGGL((dense_big_kernel<W, NP, RM, OC, IRLS, 4, NYP>), dim3(grid), dim3(W * 64), lds, stream, g);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }
 
 // BASELINE config 5: the Newton / IRLS loop around the tiled factorisation (any n <= 1024; the 4-wave shape for n <= 256)
-int dense_irls_launch(gpc_ctx* ctx, const DenseArgs& a, const IrlsArgs& ir, int grid)
+int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const IrlsArgs& ir, int grid)
 {
     BigParams g;
     g.a = a;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.pivot_tol = GPC_PIVOT_RTOL;                        // B = I + W^1/2 K W^1/2: every pivot is >= 1 in exact arithmetic
-    g.ws = static_cast<double*>(ctx->ws);
+    g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
     g.ntw = (a.n_max + MF_TS - 1) / MF_TS;
     g.slot = big_slot_doubles(g.ntw);
     g.stamps = nullptr;
@@ -1023,19 +1023,19 @@ int dense_irls_launch(gpc_ctx* ctx, const DenseArgs& a, const IrlsArgs& ir, int 
     g.irls_iters = ir.iters;
     g.irls_fhat = ir.fhat;
     if (!ctx->tickets) GPC_HIP(ctx, hipMalloc(&ctx->tickets, 64 * sizeof(int32_t)));
-    GPC_HIP(ctx, hipMemsetAsync(ctx->tickets, 0, sizeof(int32_t), ctx->stream));
+    GPC_HIP(ctx, hipMemsetAsync(ctx->tickets, 0, sizeof(int32_t), site.stream));
     g.ticket = ctx->tickets;
     int waves, npad, per_cu;
     big_shape(a, true, &waves, &npad, &per_cu);
     if (waves == 4) {
         ctx->last_dense_kernel = "dense_mfma_big_w4_irls";
-        return big_launch_t<4, 256, 2, 2, true>(ctx, g, grid);
+        return big_launch_t<4, 256, 2, 2, true>(ctx, site.stream, g, grid);
     }
     ctx->last_dense_kernel = "dense_mfma_big_irls";
-    return big_launch_t<8, 1024, 2, 2, true>(ctx, g, grid);
+    return big_launch_t<8, 1024, 2, 2, true>(ctx, site.stream, g, grid);
 }
 
-int dense_big_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
+int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, int grid)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
@@ -1043,7 +1043,7 @@ int dense_big_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
     double* ws_alpha = nullptr;
     if (v_star) {
         // the variance kernel forms the mean from the same K* tiles: the fit predicts nothing, and leaves alpha behind
-        ws_alpha = static_cast<double*>(ctx->ws) + big_slot_doubles(ntw_) * (size_t)a.P;
+        ws_alpha = reinterpret_cast<double*>(dense_ws(ctx, site)) + big_slot_doubles(ntw_) * (size_t)a.P;
         a.v_star = nullptr;
         a.m = 0;
         if (!a.alpha_out) a.alpha_out = ws_alpha;
@@ -1053,7 +1053,7 @@ int dense_big_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
     g.export_factor = v_star ? 1 : 0;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.pivot_tol = GPC_PIVOT_RTOL * (a.prm.sigmaf_sq + a.prm.noise);
-    g.ws = static_cast<double*>(ctx->ws);
+    g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
     g.ntw = (a.n_max + MF_TS - 1) / MF_TS;
     g.slot = big_slot_doubles(g.ntw);
     int waves, npad, per_cu;
@@ -1062,12 +1062,12 @@ int dense_big_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
     g.irls_model = 0; g.irls_max_iter = 0; g.irls_tol = 0.0; g.irls_f_init = 0.0; g.irls_iters = nullptr; g.irls_fhat = nullptr;
     g.ticket = nullptr;
     struct StampDump {
-        gpc_ctx* ctx; unsigned long long* d; int P, waves;
+        hipStream_t stream; unsigned long long* d; int P, waves;
         ~StampDump()
         {
             if (!d) return;
             unsigned long long h[BG_NPH * 8];
-            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipStreamSynchronize(stream);
             (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
             (void)hipFree(d);
             static const char* names[BG_NPH] = {"load", "factorisation", "z gather", "backward", "predict", "- diag tiles", "- update",
@@ -1079,31 +1079,31 @@ int dense_big_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
                 fprintf(stderr, "\n");
             }
         }
-    } dump{ctx, nullptr, a.P, waves};
+    } dump{site.stream, nullptr, a.P, waves};
     if (getenv("GPC_BIG_STAMPS")) {
         GPC_HIP(ctx, hipMalloc(&g.stamps, sizeof(unsigned long long) * BG_NPH * 8));
-        GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * BG_NPH * 8, ctx->stream));
+        GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * BG_NPH * 8, site.stream));
         dump.d = g.stamps;
     }
     if (waves == 2) {
         ctx->last_dense_kernel = "dense_mfma_big_w2";
-        return big_launch_t<2, 256, 2, 2, false, 1>(ctx, g, grid);
+        return big_launch_t<2, 256, 2, 2, false, 1>(ctx, site.stream, g, grid);
     }
     if (waves == 4 && npad == 256) {
         ctx->last_dense_kernel = "dense_mfma_big_w4";
-        return big_launch_t<4, 256, 2, 2>(ctx, g, grid);
+        return big_launch_t<4, 256, 2, 2>(ctx, site.stream, g, grid);
     }
     int rc;
     if (waves == 4) {
         ctx->last_dense_kernel = v_star ? "dense_mfma_big + dense_variance_big" : "dense_mfma_big";      // (the shape is not part of the name)
-        rc = big_launch_t<4, 512, 2, 2, false, 1>(ctx, g, grid);
+        rc = big_launch_t<4, 512, 2, 2, false, 1>(ctx, site.stream, g, grid);
     } else {
         ctx->last_dense_kernel = v_star ? "dense_mfma_big + dense_variance_big" : "dense_mfma_big";
-        rc = big_launch_t<8, 1024, 2, 2>(ctx, g, grid);
+        rc = big_launch_t<8, 1024, 2, 2>(ctx, site.stream, g, grid);
     }
     if (rc != GPC_OK || !v_star) return rc;
     DenseArgs av = a;
     av.m = a_in.m;
-    return dense_variance_big_launch(ctx, av, g.ntw, g.ws, g.slot, a.alpha_out,
+    return dense_variance_big_launch(ctx, site, av, g.ntw, g.ws, g.slot, a.alpha_out,
                                      ws_alpha + (size_t)a.n_total * a.ny, v_star);
 }

@@ -24,7 +24,7 @@
 #include <type_traits>
 
 #include "gpc_device.h"
-#include "gpc_internal.h"
+#include "dense_internal.h"
 #include "mfma_tile.h"
 
 #define W1_NPAD_MAX 512   // the kernel is instantiated for 256 (eight patches per CU) and 512 points (seven: 21 KB of LDS each)
@@ -770,14 +770,14 @@ size_t dense_w1_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out, 
     return sizeof(double) * ((size_t)(W1_TRI_OF(npad) + W1_NT_OF(npad)) * MF_IMG * (size_t)grid + (a.v_star ? (size_t)a.n_total : 0));
 }
 
-int dense_w1_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
+int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, int grid)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
     a.v_star = nullptr;
     W1Params g;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
-    g.ws = reinterpret_cast<double*>(static_cast<char*>(ctx->ws) + ctx->ws_off);
+    g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
     const int npad = w1_npad(a);
     g.linvt = g.ws + (size_t)W1_TRI_OF(npad) * MF_IMG * (size_t)grid;
     g.export_factor = v_star ? 1 : 0;
@@ -799,7 +799,7 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
 #ifdef W1_STAMPS
     if (getenv("GPC_W1_STAMPS")) {
         GPC_HIP(ctx, hipMalloc(&g.stamps, sizeof(unsigned long long) * W1_NPH));
-        GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * W1_NPH, ctx->stream));
+        GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * W1_NPH, site.stream));
     }
 #endif
     for (int base = 0; base < a.P; base += grid) {
@@ -811,20 +811,20 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseArgs& a_in, int grid)
         g.a.off = a.off + base;
         g.a.f_star = a.f_star ? a.f_star + (size_t)base * a.ny * a_in.m : nullptr;
         g.a.status = a.status ? a.status + base : nullptr;
-        if (npad == 256) hipLaunchKernelGGL((dense_w1_kernel<256>), dim3(cnt), dim3(64), 0, ctx->stream, g);
-        else hipLaunchKernelGGL((dense_w1_kernel<W1_NPAD_MAX>), dim3(cnt), dim3(64), 0, ctx->stream, g);
+        if (npad == 256) hipLaunchKernelGGL((dense_w1_kernel<256>), dim3(cnt), dim3(64), 0, site.stream, g);
+        else hipLaunchKernelGGL((dense_w1_kernel<W1_NPAD_MAX>), dim3(cnt), dim3(64), 0, site.stream, g);
         GPC_HIP(ctx, hipGetLastError());
         if (v_star) {
             DenseArgs av = g.a;
             av.m = a_in.m;
-            const int rc = dense_variance_launch(ctx, av, W1_NT_OF(256), g.ws, a.alpha_out, v_star + (size_t)base * a_in.m);
+            const int rc = dense_variance_launch(ctx, site, av, W1_NT_OF(256), g.ws, a.alpha_out, v_star + (size_t)base * a_in.m);
             if (rc != GPC_OK) return rc;
         }
     }
 #ifdef W1_STAMPS
     if (g.stamps) {
         unsigned long long h[W1_NPH];
-        GPC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GPC_HIP(ctx, hipStreamSynchronize(site.stream));
         GPC_HIP(ctx, hipMemcpy(h, g.stamps, sizeof(h), hipMemcpyDeviceToHost));
         (void)hipFree(g.stamps);
         static const char* names[W1_NPH] = {"load", "sweep gram", "sweep loop", "chain", "forward", "pass gram", "pass loop", "pass trsm",

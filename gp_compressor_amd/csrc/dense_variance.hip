@@ -25,7 +25,7 @@
 #include <cstdlib>
 
 #include "gpc_device.h"
-#include "gpc_internal.h"
+#include "dense_internal.h"
 #include "mfma_tile.h"
 
 #define DV_THREADS 512
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(64 * WV, 2) void dense_variance_kernel(VarParams g)
 }
 
 template <int NT>
-static int var_launch_t(gpc_ctx* ctx, const VarParams& g, int grid)
+static int var_launch_t(gpc_ctx* ctx, hipStream_t stream, const VarParams& g, int grid)
 {
     // four waves per workgroup (two workgroups per CU) when that fills the rounds markedly better: m = 400 is 25 blocks -- 0.78 of
     // the wave slots in rounds of eight, 0.89 in rounds of four (C2 + variance 8.22 -> 8.06 ms; the factor is streamed 7 times
@@ -237,13 +237,14 @@ static int var_launch_t(gpc_ctx* ctx, const VarParams& g, int grid)
     const int nblk = (g.a.m + MF_TS - 1) / MF_TS;
     const double eff8 = (double)nblk / (8 * ((nblk + 7) / 8)), eff4 = (double)nblk / (4 * ((nblk + 3) / 4));
     const bool w4 = getenv("GPC_VAR_W4") ? atoi(getenv("GPC_VAR_W4")) != 0 : eff4 > eff8 + 0.08;
-    if (w4) hipLaunchKernelGGL((dense_variance_kernel<NT, 4>), dim3(grid), dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL((dense_variance_kernel<NT, 8>), dim3(grid), dim3(DV_THREADS), 0, ctx->stream, g);
+    if (w4) hipLaunchKernelGGL((dense_variance_kernel<NT, 4>), dim3(grid), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((dense_variance_kernel<NT, 8>), dim3(grid), dim3(DV_THREADS), 0, stream, g);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }
 
-int dense_variance_launch(gpc_ctx* ctx, const DenseArgs& a, int nt_max, const double* factor, const double* alpha, double* v_star)
+int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int nt_max, const double* factor, const double* alpha,
+                          double* v_star)
 {
     if (a.P == 0 || a.m == 0) return GPC_OK;
     if (!a.xs0 || !a.xs1) return gpc_fail(ctx, GPC_EINVAL, "the predictive variance needs point-wise X*");
@@ -254,10 +255,10 @@ int dense_variance_launch(gpc_ctx* ctx, const DenseArgs& a, int nt_max, const do
     g.alpha = alpha;
     g.v_star = v_star;
     switch (nt_max) {
-        case 4: return var_launch_t<4>(ctx, g, a.P);
-        case 8: return var_launch_t<8>(ctx, g, a.P);
-        case 12: return var_launch_t<12>(ctx, g, a.P);
-        default: return var_launch_t<16>(ctx, g, a.P);
+        case 4: return var_launch_t<4>(ctx, site.stream, g, a.P);
+        case 8: return var_launch_t<8>(ctx, site.stream, g, a.P);
+        case 12: return var_launch_t<12>(ctx, site.stream, g, a.P);
+        default: return var_launch_t<16>(ctx, site.stream, g, a.P);
     }
 }
 
@@ -495,8 +496,8 @@ size_t dense_variance_big_scratch_doubles(const gpc_ctx* ctx, int ntw)
     return (size_t)ctx->num_cus * DV_WAVES * (size_t)ntw * MF_IMG;
 }
 
-int dense_variance_big_launch(gpc_ctx* ctx, const DenseArgs& a, int ntw, const double* ws, size_t slot, const double* alpha,
-                              double* scratch, double* v_star)
+int dense_variance_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
+                              const double* alpha, double* scratch, double* v_star)
 {
     if (a.P == 0 || a.m == 0) return GPC_OK;
     if (!a.xs0 || !a.xs1) return gpc_fail(ctx, GPC_EINVAL, "the predictive variance needs point-wise X*");
@@ -507,7 +508,7 @@ int dense_variance_big_launch(gpc_ctx* ctx, const DenseArgs& a, int ntw, const d
     const size_t lds = sizeof(double) * (size_t)(64 + 5 * DVB_NPAD + 2 * DV_CH * MF_IMG);
     GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_variance_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      160 * 1024));
-    hipLaunchKernelGGL(dense_variance_big_kernel, dim3(dvb_grid(ctx, a.P)), dim3(DV_THREADS), lds, ctx->stream, g);
+    hipLaunchKernelGGL(dense_variance_big_kernel, dim3(dvb_grid(ctx, a.P)), dim3(DV_THREADS), lds, site.stream, g);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }

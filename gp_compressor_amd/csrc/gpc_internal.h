@@ -30,11 +30,8 @@ struct gpc_ctx {
     // grow-only device workspace (K / L factors of the generic dense kernel, variance scratch, grid tables)
     void* ws = nullptr;
     size_t ws_bytes = 0;
-    size_t ws_len = 0;                 // ... and its length (0: to the end of the workspace); GPC_POISON_LDS poisons only this region
-    size_t ws_off = 0;                 // offset of the region the launch in hand may use (the host-pointer pipeline runs the kernels of
-                                       // consecutive chunks on two streams, each in its own half; 0 everywhere else)
     int32_t* tickets = nullptr;        // 64 counters (allocated on first use): patches handed out one at a time where their cost varies (dense_mfma_big.hip)
-    // host-pointer entries (gpc_api.hip, dense_host): a grow-only device arena for the batch, pinned staging buffers for
+    // host-pointer entries (dense_host.hip, dense_host): a grow-only device arena for the batch, pinned staging buffers for
     // pageable caller memory, and two copy streams so that the upload of chunk c+1 and the download of chunk c-1 run on the
     // SDMA engines while the kernel works on chunk c
     void* io = nullptr;
@@ -46,7 +43,7 @@ struct gpc_ctx {
     hipStream_t s_in = nullptr, s_out = nullptr, s_c2 = nullptr;   // copy-in, copy-out, second compute stream
     bool pipe_active = false;          // a two-stream host-pointer call is in flight on own_stream / s_c2 (under mu): see gpc_ws_reserve
     unsigned foreign_gen = 0;          // ... and the number of calls of other threads that touched the workspace meanwhile
-    hipEvent_t ev[3][16] = {};       // [.][0 .. 7] the chunks of the host-pointer pipeline, [.][10] the pipeline against other threads' calls, [.][13] the class fork, [0][15] the arena
+    hipEvent_t ev[3][16] = {};         // [.][slot]: slots 0 .. 7 are the chunks of the host-pointer pipeline, the others are named in GpcEvSlot
     std::mutex host_mu;                // one host-pointer call at a time per context (they share the arena)
     // size classes of the last batch gpc_project_cloud produced on this context (its `off` buffer, how many of its P patches have
     // <= 256 / <= 272 points): lets the dense dispatch size its class launches exactly instead of P workgroups each
@@ -64,6 +61,15 @@ struct gpc_ctx {
     // without owning them (gpc_registration) asks here whether they still exist before it touches them
     std::vector<std::pair<const void*, uint64_t>> children;
     uint64_t next_serial = 1;
+};
+
+// gpc_ctx::ev[.][slot] above the eight chunk slots
+enum GpcEvSlot {
+    GPC_EV_PIPE_ORDER = 10,     // the host-pointer pipeline against other threads' calls (gpc_ws_reserve, gpc_pipe_chunk_order)
+    GPC_EV_SPARSE_OWN = 12,     // [1]: the sparse predict fork's launch on own_stream joins the caller's stream
+    GPC_EV_CLASS_FORK = 13,     // fork and join of the dense size-class launches
+    GPC_EV_SPARSE_FORK = 14,    // fork and join of the sparse predict launches
+    GPC_EV_ARENA = 15,          // the host-pointer arena against the caller's stream, and the pipeline's compute streams joining it
 };
 
 static inline void gpc_ctx_ref(gpc_ctx* ctx) { ctx->refs.fetch_add(1, std::memory_order_relaxed); }
@@ -112,9 +118,8 @@ static inline int gpc_fail(gpc_ctx* ctx, int code, const char* fmt, ...)
                             #call, hipGetErrorString(e_));                                              \
     } while (0)
 
-// The context's stream as the caller configured it, for code that does NOT hold ctx->mu: the dispatchers swap ctx->stream for the length of
-// a fork (class streams, the host pipeline's compute streams) and put it back before they unlock, so a read under the lock never sees a
-// fork's stream while a bare read from another thread can.
+// The context's stream as the caller configured it, for code that does NOT hold ctx->mu: gpc_ctx_set_stream on another thread writes
+// ctx->stream under the lock, so a bare read may race with it.
 static inline hipStream_t gpc_stream_of(gpc_ctx* ctx)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -204,19 +209,20 @@ struct GpcStaging {
     }
 };
 
-// grow-only workspace; returns nullptr + sets error on failure.  Caller holds ctx->mu.
-static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)
+// grow-only workspace; sets the error on failure.  Caller holds ctx->mu.  `stream` is the stream of the call in hand: a grow synchronises
+// it before the old block goes and clears the new one on it.  `pipe_chunk`: the caller is a chunk of the two-stream host-pointer pipeline.
+static inline int gpc_ws_reserve(gpc_ctx* ctx, hipStream_t stream, bool pipe_chunk, size_t bytes)
 {
     // "Thread-safe per context" (include/gpc.h) while a two-stream host-pointer call is in flight: its chunk kernels use the workspace from
-    // the context's two compute streams, which the stream of ANOTHER thread's call (ws_len == 0: not a chunk of the pipeline) is not
+    // the context's two compute streams, which the stream of ANOTHER thread's call (not a chunk of the pipeline) is not
     // ordered against.  Every user of the workspace comes through here first: that call goes behind the chunks already enqueued; the
-    // chunks enqueued after it go behind the context's stream in turn (dense_dispatch).
-    if (ctx->pipe_active && ctx->ws_len == 0 && !getenv("GPC_NO_PIPE_ORDER")) {   // (the switch: what the test of this looks like without it)
+    // chunks enqueued after it go behind the context's stream in turn (gpc_pipe_chunk_order).
+    if (ctx->pipe_active && !pipe_chunk && !getenv("GPC_NO_PIPE_ORDER")) {   // (the switch: what the test of this looks like without it)
         ++ctx->foreign_gen;
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[0][10], ctx->own_stream));
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[1][10], ctx->s_c2));
-        GPC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev[0][10], 0));
-        GPC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev[1][10], 0));
+        GPC_HIP(ctx, hipEventRecord(ctx->ev[0][GPC_EV_PIPE_ORDER], ctx->own_stream));
+        GPC_HIP(ctx, hipEventRecord(ctx->ev[1][GPC_EV_PIPE_ORDER], ctx->s_c2));
+        GPC_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev[0][GPC_EV_PIPE_ORDER], 0));
+        GPC_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev[1][GPC_EV_PIPE_ORDER], 0));
     }
     if (bytes <= ctx->ws_bytes) return GPC_OK;
     // The new block is allocated BEFORE the old one is released: a request the device cannot serve leaves the context with the
@@ -229,7 +235,7 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)
     if (e != hipSuccess) {
         (void)hipGetLastError();
         if (!ctx->ws) return gpc_fail(ctx, GPC_ENOMEM, "workspace allocation failed");
-        GPC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GPC_HIP(ctx, hipStreamSynchronize(stream));
         const size_t old_bytes = ctx->ws_bytes;
         GPC_HIP(ctx, hipFree(ctx->ws));
         ctx->ws = nullptr;
@@ -240,7 +246,7 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)
             // put back what was there, so that later (smaller) calls find the context as it was
             if (hipMalloc(&ctx->ws, old_bytes) == hipSuccess) {
                 ctx->ws_bytes = old_bytes;
-                (void)hipMemsetAsync(ctx->ws, getenv("GPC_POISON_LDS") ? 0xFF : 0, old_bytes, ctx->stream);
+                (void)hipMemsetAsync(ctx->ws, getenv("GPC_POISON_LDS") ? 0xFF : 0, old_bytes, stream);
             } else {
                 (void)hipGetLastError();
                 ctx->ws = nullptr;
@@ -249,7 +255,7 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)
         }
     } else if (ctx->ws) {
         // the previous workspace may still be in use by work enqueued on the stream
-        GPC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GPC_HIP(ctx, hipStreamSynchronize(stream));
         GPC_HIP(ctx, hipFree(ctx->ws));
     }
     ctx->ws = nw;
@@ -257,7 +263,22 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)
     // recycled device memory holds arbitrary bit patterns; the kernels write every workspace element before they use it,
     // but their (clamped, unconditional) prefetches may touch elements they never consume: keep those reads free of
     // signalling patterns and the results independent of what ran before
-    GPC_HIP(ctx, hipMemsetAsync(ctx->ws, getenv("GPC_POISON_LDS") ? 0xFF : 0, bytes, ctx->stream));   // diagnostic runs: NaN instead of zero
+    GPC_HIP(ctx, hipMemsetAsync(ctx->ws, getenv("GPC_POISON_LDS") ? 0xFF : 0, bytes, stream));   // diagnostic runs: NaN instead of zero
+    return GPC_OK;
+}
+// ... for a call on the context's own stream that uses the whole workspace (every caller outside the dense path)
+static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes) { return gpc_ws_reserve(ctx, ctx->stream, false, bytes); }
+// The other half of that ordering, for a chunk of the pipeline about to launch on `stream` (in the ctx->mu critical section of its launches:
+// no foreign call can slip in between).  If a call of another thread touched the workspace since this compute stream's last chunk
+// (*seen_gen: gpc_ctx::foreign_gen as the stream last saw it), the chunk goes behind the context's stream as it stands now: that call may
+// use -- or re-grow and clear -- the region this chunk is about to write.
+static inline int gpc_pipe_chunk_order(gpc_ctx* ctx, hipStream_t stream, unsigned* seen_gen)
+{
+    if (*seen_gen == ctx->foreign_gen) return GPC_OK;
+    *seen_gen = ctx->foreign_gen;
+    if (ctx->stream == stream) return GPC_OK;
+    GPC_HIP(ctx, hipEventRecord(ctx->ev[2][GPC_EV_PIPE_ORDER], ctx->stream));
+    GPC_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev[2][GPC_EV_PIPE_ORDER], 0));
     return GPC_OK;
 }
 
@@ -265,57 +286,3 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, size_t bytes)
 // previous kernel left there, so a read of a word the current kernel never wrote is otherwise a coin toss; with the poison it
 // is a NaN in the output and a failing test.  Enqueued on the context's stream; a no-op unless the variable is set.
 extern "C" int gpc_debug_poison_lds(gpc_ctx* ctx);
-
-// ---- launchers implemented in the kernel translation units -------------------------------------------------
-
-struct DenseArgs {
-    gpc_params prm;
-    int P, n_max, n_total, ny, m;
-    const int32_t* off;
-    const double *x0, *x1, *y;
-    const double *xs0, *xs1;   // point-wise X* (m entries) or nullptr when the grid form is used
-    double grid_res;           // grid form: res, sz (m = sz*sz)
-    int grid_sz;
-    double *f_star, *v_star, *alpha_out;
-    int32_t* status;
-    // size-class dispatch of a ragged batch (gpc_api.hip): when sel != nullptr a kernel works on the patches sel[0 .. *sel_count)
-    // (both on the device) instead of 0 .. P-1
-    const int32_t* sel;
-    const int32_t* sel_count;
-    int sel_base;              // generic kernel only: it works on sel[sel_base .. *sel_count) -- the overflow launch behind a class launch that
-                               // was sized from a host-side hint (gpc_api.hip)
-};
-
-// generic kernel: any n <= GPC_MAX_POINTS, K/L in a global-memory workspace slot per workgroup
-size_t dense_generic_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out);
-int dense_generic_launch(gpc_ctx* ctx, const DenseArgs& a, int grid, double* ws_override = nullptr);
-
-// register-tile MFMA kernel: n <= 256, trailing matrix resident in VGPRs (see dense_mfma.hip)
-bool dense_mfma_supported(const DenseArgs& a);
-int dense_mfma_launch(gpc_ctx* ctx, const DenseArgs& a);
-
-// predictive variance from the exported factor of the register-tile kernel (dense_variance.hip): V* [P][m]
-int dense_variance_launch(gpc_ctx* ctx, const DenseArgs& a, int nt_max, const double* factor, const double* alpha, double* v_star);
-
-// ... and from the tiled kernel's per-patch factor slots (n <= 1024); scratch: V blocks of the waves in flight
-size_t big_slot_doubles(int ntw);
-size_t dense_variance_big_scratch_doubles(const gpc_ctx* ctx, int ntw);
-int dense_variance_big_launch(gpc_ctx* ctx, const DenseArgs& a, int ntw, const double* ws, size_t slot, const double* alpha,
-                              double* scratch, double* v_star);
-
-// tiled left-looking MFMA kernel: 256 < n <= 1024, factor in a global-memory workspace slot per workgroup (see dense_mfma_big.hip)
-bool dense_big_supported(const DenseArgs& a);
-size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out);
-int dense_big_launch(gpc_ctx* ctx, const DenseArgs& a, int grid);
-// one wave per patch, eight patches per CU: n <= 256, depth plane, mean only (see dense_mfma_w1.hip) -- the C2 headline kernel
-bool dense_w1_supported(const DenseArgs& a);
-size_t dense_w1_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out, int cap = 0);
-int dense_w1_launch(gpc_ctx* ctx, const DenseArgs& a, int grid);
-// the same kernel inside the Newton / IRLS loop of the probit variant (BASELINE config 5; any n <= 1024, ny == 1)
-struct IrlsArgs {
-    int max_iter;
-    double tol, f_init;
-    int32_t* iters;   // [P] or nullptr
-    double* fhat;     // [n_total] or nullptr
-};
-int dense_irls_launch(gpc_ctx* ctx, const DenseArgs& a, const IrlsArgs& ir, int grid);

@@ -424,7 +424,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_claim_kernel(PcArgs A)
 }
 
 // nmax[0] = largest patch; nmax[1], nmax[2] = patches of <= 256 / <= 272 points: the size classes of the dense dispatch
-// (gpc_api.hip), which the host reads together with n_max and hands to it so that the class launches are sized exactly
+// (dense_api.hip), which the host reads together with n_max and hands to it so that the class launches are sized exactly
 __global__ __launch_bounds__(PC_THREADS) void pc_nmax_kernel(const int32_t* cnt, int P, int32_t* nmax)
 {
     int m = 0, c0 = 0, c1 = 0;

@@ -553,13 +553,13 @@ int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, con
     const bool fork = ctx->s_in && ctx->s_out && A.sigma != nullptr;
     hipStream_t s32 = fork ? ctx->s_in : main_s, sreg = fork ? ctx->s_out : main_s;
     // (the third launch goes to the context's OWN stream: the legacy default stream does not overlap its kernels with another stream's, and
-    // a caller's stream may share a hardware queue with s_in or s_out -- gpc_api.hip, dense_host; own_stream, s_in and s_out never do)
+    // a caller's stream may share a hardware queue with s_in or s_out -- dense_host.hip, dense_host; own_stream, s_in and s_out never do)
     hipStream_t s16 = (fork && ctx->own_stream) ? ctx->own_stream : main_s;
     if (fork) {
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[0][14], main_s));
-        GPC_HIP(ctx, hipStreamWaitEvent(s32, ctx->ev[0][14], 0));
-        GPC_HIP(ctx, hipStreamWaitEvent(sreg, ctx->ev[0][14], 0));
-        if (s16 != main_s) GPC_HIP(ctx, hipStreamWaitEvent(s16, ctx->ev[0][14], 0));
+        GPC_HIP(ctx, hipEventRecord(ctx->ev[0][GPC_EV_SPARSE_FORK], main_s));
+        GPC_HIP(ctx, hipStreamWaitEvent(s32, ctx->ev[0][GPC_EV_SPARSE_FORK], 0));
+        GPC_HIP(ctx, hipStreamWaitEvent(sreg, ctx->ev[0][GPC_EV_SPARSE_FORK], 0));
+        if (s16 != main_s) GPC_HIP(ctx, hipStreamWaitEvent(s16, ctx->ev[0][GPC_EV_SPARSE_FORK], 0));
     }
     const int waves = std::min(A.P, ctx->num_cus * 16);
     const size_t l16 = sizeof(double) * (size_t)(64 + 16 * 16 + 5 * 16), l32 = sizeof(double) * (size_t)(64 + 32 * 32 + 5 * 32);
@@ -572,13 +572,13 @@ int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, con
     hipLaunchKernelGGL((sparse_predict_small_kernel<16>), dim3(waves), dim3(64), l16, s16, A, 0);
     GPC_HIP(ctx, hipGetLastError());
     if (fork) {
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[1][14], s32));
-        GPC_HIP(ctx, hipEventRecord(ctx->ev[2][14], sreg));
-        GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][14], 0));
-        GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][14], 0));
+        GPC_HIP(ctx, hipEventRecord(ctx->ev[1][GPC_EV_SPARSE_FORK], s32));
+        GPC_HIP(ctx, hipEventRecord(ctx->ev[2][GPC_EV_SPARSE_FORK], sreg));
+        GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][GPC_EV_SPARSE_FORK], 0));
+        GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][GPC_EV_SPARSE_FORK], 0));
         if (s16 != main_s) {
-            GPC_HIP(ctx, hipEventRecord(ctx->ev[1][12], s16));
-            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][12], 0));
+            GPC_HIP(ctx, hipEventRecord(ctx->ev[1][GPC_EV_SPARSE_OWN], s16));
+            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][GPC_EV_SPARSE_OWN], 0));
         }
     }
     return GPC_OK;

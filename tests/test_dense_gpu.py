@@ -670,7 +670,7 @@ def test_dense_does_not_read_stale_lds(gp, oracle, monkeypatch):
 
 def test_host_pointer_entry_pipeline_and_pinned_buffers(gp, oracle, monkeypatch):
     """The host-pointer entries cut a batch of >= 2048 patches into four chunks and overlap upload, kernel and download
-    (csrc/gpc_api.hip, dense_host): a ragged 3-channel batch through the pipeline, through the single-chunk form
+    (csrc/dense_host.hip, dense_host): a ragged 3-channel batch through the pipeline, through the single-chunk form
     (GPC_HOST_NO_PIPELINE) and from page-locked caller buffers (gpc_host_alloc) gives the same grids, alpha and status; the
     oracle on a sample.  Point-wise X* with the variance goes through the same chunking."""
     capi, ctx = gp
@@ -718,7 +718,7 @@ def test_host_pointer_entry_pipeline_and_pinned_buffers(gp, oracle, monkeypatch)
 @pytest.mark.gpu
 def test_host_pointer_two_stream_mode_with_a_chunk_of_small_patches(gp, oracle, monkeypatch):
     """The two-stream form of the host-pointer pipeline (eight chunks, kernels of consecutive chunks on two streams, each in its own half of
-    the workspace: csrc/gpc_api.hip, dense_host) is for batches whose EVERY chunk goes to the one-wave kernel.  With the variance wanted a
+    the workspace: csrc/dense_host.hip, dense_host) is for batches whose EVERY chunk goes to the one-wave kernel.  With the variance wanted a
     chunk of patches of <= 192 points goes to the register kernel, whose factor export starts at the base of the workspace -- under the
     other stream's live factor slots if the pipeline forked anyway (round 4 did, up to this test).  Batch: 8192 patches of 250 points with
     patches 1024 .. 2047 (chunk 1) cut to 150; the call must equal the one-stream form and the oracle on patches of both kinds."""
