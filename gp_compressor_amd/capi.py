@@ -98,6 +98,7 @@ PROTOTYPES = {
     "gpc_sparse_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_ld": (C.c_int, [_vp]),
     "gpc_sparse_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_sparse_remap": (C.c_int, [_vp, _i, _vp, C.POINTER(_vp)]),
     "gpc_reproject": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_reproject_dev": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_project_cloud": (C.c_int, [_vp, _vp, _i, _d, _i, C.POINTER(_vp)]),
@@ -105,6 +106,8 @@ PROTOTYPES = {
     "gpc_patches_view_dev": (C.c_int, [_vp, _vp]),
     "gpc_patches_fetch": (C.c_int, [_vp] * 11),
     "gpc_patches_destroy": (None, [_vp]),
+    "gpc_patches_insert_cloud": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp), _vp]),
+    "gpc_patches_insert_cloud_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp), _vp]),
     "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
     "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "gpc_registration_destroy": (None, [_vp]),
@@ -114,6 +117,7 @@ PROTOTYPES = {
     "gpc_registration_run": (C.c_int, [_vp, C.POINTER(RegistrationParams), _vp, _vp]),
     "gpc_registration_get_transform": (C.c_int, [_vp, _vp, _vp]),
     "gpc_registration_get_cloud": (C.c_int, [_vp, _vp]),
+    "gpc_registration_cloud_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
     "gpc_registration_get_assignment": (C.c_int, [_vp, _vp, _vp]),
     "gpc_partition_patches": (C.c_int, [_i, _vp, _i, _i, _vp]),
     "gpc_comm_unique_id": (C.c_int, [_vp]),
@@ -420,6 +424,23 @@ class Patches:
         o["R"] = o["R"].reshape(P, 3, 3).transpose(0, 2, 1).copy()
         return o
 
+    def insert_cloud(self, cloud, min_nbr=100, depth=None, n=None):
+        """gpc_patches_insert_cloud[_dev]: a registered scan -- host record array (Context.make_cloud) or device buffer of n records -- cut
+        against this model.  depth: the model's depth Sparse (None: every leaf counts as trained).  Returns the new Patches (this
+        one is untouched) and old_to_new (P,) int32."""
+        h = _vp()
+        o2n = np.full(max(self.view.P, 1), -1, dtype=np.int32)
+        dh = depth.h if depth is not None else None
+        if isinstance(cloud, np.ndarray):
+            assert cloud.dtype == Context.POINT_DTYPE
+            cloud = np.ascontiguousarray(cloud)
+            rc = self.lib.gpc_patches_insert_cloud(self.ctx.h, self.h, dh, _ptr(cloud) if len(cloud) else None, len(cloud), int(min_nbr),
+                                                   C.byref(h), _ptr(o2n))
+        else:
+            rc = self.lib.gpc_patches_insert_cloud_dev(self.ctx.h, self.h, dh, _ptr(cloud), int(n), int(min_nbr), C.byref(h), _ptr(o2n))
+        self.ctx._check(rc)
+        return Patches(self.ctx, h), o2n[:self.view.P]
+
 
 class Sparse:
     """gpc_sparse: P independent sparse_gp (ny=1) / sparse_gp_field (ny=3) states resident on the device."""
@@ -440,6 +461,17 @@ class Sparse:
 
     def reset(self):
         self.ctx._check(self.lib.gpc_sparse_reset(self.h))
+
+    def remap(self, P_new, old_to_new):
+        """gpc_sparse_remap: a new Sparse of P_new patches, patch old_to_new[i] holding this object's patch i, the others empty"""
+        o2n = np.ascontiguousarray(old_to_new, dtype=np.int32)
+        assert o2n.shape == (self.P,)
+        h = _vp()
+        self.ctx._check(self.lib.gpc_sparse_remap(self.h, int(P_new), _ptr(o2n) if self.P else None, C.byref(h)))
+        g = Sparse.__new__(Sparse)
+        g.ctx, g.lib, g.P, g.ny, g.h = self.ctx, self.lib, int(P_new), self.ny, h
+        self.ctx._children.add(g)
+        return g
 
     def add(self, off, x0, x1, y, perm=None, trace=False):
         """trace=True: also returns the decision bytes of the call (gpc_sparse_set_trace), (N,) uint8 in insertion order"""
@@ -629,12 +661,58 @@ class Registration:
         self.ctx._check(self.lib.gpc_registration_get_cloud(self.h, _ptr(c) if self.n else None))
         return c
 
+    def cloud_dev(self):
+        """the working cloud where it is: (device address, n); valid until the next set_cloud or close"""
+        p, n = _vp(), C.c_int(0)
+        self.ctx._check(self.lib.gpc_registration_cloud_dev(self.h, C.byref(p), C.byref(n)))
+        return (p.value or 0), int(n.value)
+
     def assignment(self):
         """what the last step assigned: owner (n,) int32 (-1 = unused), local (n, 3) = depth, x0, x1 in the owner's frame"""
         owner = np.full(self.n, -1, dtype=np.int32)
         local = np.zeros((self.n, 3))
         self.ctx._check(self.lib.gpc_registration_get_assignment(self.h, _ptr(owner), _ptr(local)))
         return owner, local
+
+
+class Mapping:
+    """gp_mapping (src/gp_mapping.cpp): a map -- a Patches batch with the depth (ny=1) and colour (ny=3) Sparse objects trained on it --
+    that grows scan by scan.  Takes the three over: add_cloud replaces them by new objects and closes the old ones."""
+
+    def __init__(self, ctx, patches, depth, rgb, params=None, min_nbr=100):
+        self.ctx, self.patches, self.depth, self.rgb = ctx, patches, depth, rgb
+        self.params = params if params is not None else default_params_registration()
+        self.min_nbr = int(min_nbr)
+        self.reg = Registration(ctx, patches, depth, rgb)
+
+    def close(self):
+        for o in (getattr(self, "reg", None), getattr(self, "depth", None), getattr(self, "rgb", None), getattr(self, "patches", None)):
+            if o is not None:
+                o.close()
+        self.reg = self.depth = self.rgb = self.patches = None
+
+    def add_cloud(self, cloud, n=None, perm_depth=None, perm_rgb=None):
+        """gp_mapping::add_cloud (:12-28): register the scan (host record array or device buffer of n records) against the map; if the
+        loop stopped before max_steps (:22) insert it (insert_into_map) and train the leaf GPs on what was inserted (train_processes),
+        else drop it (:26).  perm_depth / perm_rgb: optional insertion orders for the new batch (device, as Sparse.add_dev takes them).
+        Returns (steps, inserted)."""
+        self.reg.set_cloud(cloud, n)
+        steps = len(self.reg.run(self.params))             # = step_nbr: set_cloud restarted the count
+        if steps >= self.params.max_steps:
+            self.reg.set_cloud(np.zeros(0, dtype=Context.POINT_DTYPE))
+            return steps, False
+        d_cloud, m = self.reg.cloud_dev()
+        pt, o2n = self.patches.insert_cloud(d_cloud, self.min_nbr, self.depth, n=m)
+        v = pt.view
+        gd, gc = self.depth.remap(v.P, o2n), self.rgb.remap(v.P, o2n)
+        gd.add_dev(v.off, v.n_max, v.n_total, v.x0, v.x1, v.y, perm_depth)
+        gc.add_dev(v.off, v.n_max, v.n_total, v.x0, v.x1, v.rgb, perm_rgb)
+        self.ctx.synchronize()
+        reg = Registration(self.ctx, pt, gd, gc)
+        for o in (self.reg, self.depth, self.rgb, self.patches):
+            o.close()
+        self.reg, self.patches, self.depth, self.rgb = reg, pt, gd, gc
+        return steps, True
 
 
 class Comm:

@@ -35,212 +35,11 @@
 
 #include "producer_internal.h"   // (switches floating-point contraction off)
 
-#define PC_THREADS 256
-#define PC_WAVES (PC_THREADS / 64)
-
-struct PcPoint {        // sorted-order record
-    float x, y, z;
-    uint32_t rgb;       // r | g << 8 | b << 16
-};
-
 // ---- 1: bounds -------------------------------------------------------------------------------------------------------
-__device__ static inline uint32_t pc_ordered(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ static inline float pc_unordered(uint32_t o)
-{
-    const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// out[0..2] = ordered min, out[3..5] = ordered max, out[6] = 1 if a coordinate is not finite
-__global__ __launch_bounds__(PC_THREADS) void pc_bounds_kernel(const gpc_point_xyzrgb* cloud, int n, uint32_t* out)
-{
-    __shared__ uint32_t red[PC_WAVES][8];
-    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0, 0, 0};
-    int bad = 0;
-    for (int i = blockIdx.x * PC_THREADS + threadIdx.x; i < n; i += gridDim.x * PC_THREADS) {
-        const float4 p = *reinterpret_cast<const float4*>(&cloud[i]);
-        const float c[3] = {p.x, p.y, p.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            bad |= !(fabsf(c[a]) <= 3.4028234e38f);
-            const uint32_t o = pc_ordered(c[a]);
-            lo[a] = min(lo[a], o);
-            hi[a] = max(hi[a], o);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], o));
-            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], o));
-        }
-    }
-    bad = __any(bad);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[w][a] = lo[a]; red[w][3 + a] = hi[a]; }
-        red[w][6] = (uint32_t)bad;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const int a = threadIdx.x;
-        uint32_t v = red[0][a];
-        for (int q = 1; q < PC_WAVES; ++q) v = a < 3 ? min(v, red[q][a]) : max(v, red[q][a]);   // [6]: 0 / 1, max == or
-        if (a < 3) atomicMin(&out[a], v); else if (a < 6) atomicMax(&out[a], v); else if (v) atomicOr(&out[6], 1u);
-    }
-}
-
 // ---- 2: keys, leaf table -----------------------------------------------------------------------------------------------
 // (PcGrid and the key arithmetic: producer_internal.h)
-__global__ __launch_bounds__(PC_THREADS) void pc_keys_kernel(PcGrid g, const gpc_point_xyzrgb* cloud, int n, uint64_t* keys, int32_t* vals)
-{
-    const int i = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = *reinterpret_cast<const float4*>(&cloud[i]);
-    int k[3];
-    pc_voxel(g, p.x, p.y, p.z, k);
-    keys[i] = pc_pack(g, k[0], k[1], k[2]);
-    vals[i] = i;
-}
-
-__global__ __launch_bounds__(PC_THREADS) void pc_heads_kernel(const uint64_t* keys, int n, int32_t* head)
-{
-    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (s < n) head[s] = (s == 0 || keys[s] != keys[s - 1]) ? 1 : 0;
-}
-
-// leaf_of[s] holds the inclusive scan of head[] on entry (leaf id + 1) and the leaf id on exit
-__global__ __launch_bounds__(PC_THREADS) void pc_leaves_kernel(const uint64_t* keys, int n, int P, int32_t* leaf_of, uint64_t* leaf_key,
-                                                               int32_t* leaf_start)
-{
-    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (s >= n) return;
-    const int id = leaf_of[s] - 1;
-    leaf_of[s] = id;
-    if (s == 0 || keys[s] != keys[s - 1]) {
-        leaf_key[id] = keys[s];
-        leaf_start[id] = s;
-    }
-    if (s == n - 1) leaf_start[P] = n;
-}
-
 // ---- 3: sorted-order copy ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PC_THREADS) void pc_gather_kernel(const gpc_point_xyzrgb* cloud, const int32_t* vals, int n, PcPoint* sp)
-{
-    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (s >= n) return;
-    const gpc_point_xyzrgb* q = &cloud[vals[s]];
-    const float4 p = *reinterpret_cast<const float4*>(q);
-    const uint32_t c = *reinterpret_cast<const uint32_t*>(&q->b);     // b | g << 8 | r << 16 | a << 24
-    PcPoint o;
-    o.x = p.x; o.y = p.y; o.z = p.z;
-    o.rgb = ((c >> 16) & 0xffu) | (c & 0xff00u) | ((c & 0xffu) << 16);
-    *reinterpret_cast<float4*>(&sp[s]) = *reinterpret_cast<const float4*>(&o);
-}
-
 // ---- 4: frames -------------------------------------------------------------------------------------------------------------
-__device__ static inline int pc_find_leaf(const uint64_t* leaf_key, int P, uint64_t key)
-{
-    int lo = 0, hi = P;                       // first element >= key
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (leaf_key[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < P && leaf_key[lo] == key) ? lo : -1;
-}
-
-__device__ static inline float pc_readlane_f(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-__device__ static inline double pc_readlane_d(double v, int lane)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// eigenvector of the smallest eigenvalue of the symmetric 4x4 matrix A: the cyclic Jacobi of orc_smallest_eigvec4
-__device__ static inline void pc_smallest_eigvec4(double A[4][4], double v[4])
-{
-    double V[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        double offd = 0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) offd += A[p][q] * A[p][q];
-        if (offd == 0.0) break;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double g = 100.0 * fabs(A[p][q]);       // negligible against both diagonal entries: drop it
-                const bool drop = fabs(A[p][p]) + g == fabs(A[p][p]) && fabs(A[q][q]) + g == fabs(A[q][q]);
-                if (A[p][q] != 0.0 && drop) A[p][q] = A[q][p] = 0.0;
-                if (A[p][q] != 0.0) {
-                    const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = c * akp - s * akq;
-                        A[k][q] = s * akp + c * akq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const double apk = A[p][k], aqk = A[q][k];
-                        A[p][k] = c * apk - s * aqk;
-                        A[q][k] = s * apk + c * aqk;
-                    }
-                    A[p][q] = A[q][p] = 0.0;                  // the rotation annihilates this pair: make it exact
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const double vkp = V[k][p], vkq = V[k][q];
-                        V[k][p] = c * vkp - s * vkq;
-                        V[k][q] = s * vkp + c * vkq;
-                    }
-                }
-            }
-        }
-    }
-    double best = A[0][0];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = V[k][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (A[i][i] < best) {
-            best = A[i][i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = V[k][i];
-        }
-}
-
-__device__ static inline void pc_cross(const double a[3], const double b[3], double o[3])
-{
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ static inline void pc_normalize(double a[3])
-{
-    const double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    if (n > 0) { a[0] /= n; a[1] /= n; a[2] /= n; }
-}
-
 struct PcArgs {
     PcGrid g;
     int n, P;
@@ -263,8 +62,6 @@ struct PcArgs {
     double *x0, *x1, *y, *rgb;
     int32_t* src;
 };
-
-#define PC_LROW 66         // LDS row pitch (doubles) of the product table: 64 hits + padding against bank conflicts
 
 __global__ __launch_bounds__(PC_THREADS) void pc_moment_kernel(PcArgs A)
 {
@@ -290,41 +87,9 @@ __global__ __launch_bounds__(PC_THREADS) void pc_moment_kernel(PcArgs A)
         if (nb >= 0) { seg0 = A.leaf_start[nb]; seg1 = A.leaf_start[nb + 1]; }
     }
     if (lane < 3) A.cen[(size_t)leaf * 3 + lane] = lane == 0 ? center[0] : (lane == 1 ? center[1] : center[2]);
-    pr[9 * PC_LROW + lane] = 1.0;                             // the homogeneous coordinate's products
-    const double r2 = g.radius * g.radius;
-    // lanes 0..15: entry (ea, eb) of the moment matrix = product row of (min, max)
-    const int ea = (lane >> 2) & 3, eb = lane & 3, lo = min(ea, eb), hi = max(ea, eb);
-    const int row = (lo == 0 ? 0 : (lo == 1 ? 3 : (lo == 2 ? 5 : 6))) + hi;      // 0:0-3, 1:4-6, 2:7-8, 3:9
-    const double* mine = pr + row * PC_LROW;
-    double M = 0.0;
-    int k = 0;
-    for (int j = 0; j < 27; ++j) {
-        const int s0 = __builtin_amdgcn_readlane(seg0, j), s1 = __builtin_amdgcn_readlane(seg1, j);
-        for (int base = s0; base < s1; base += 64) {
-            const int s = base + lane;
-            double q0 = 0, q1 = 0, q2 = 0;
-            bool in = false;
-            if (s < s1) {
-                const float4 p = *reinterpret_cast<const float4*>(&A.sp[s]);
-                q0 = (double)p.x; q1 = (double)p.y; q2 = (double)p.z;
-                const double ex = q0 - center[0], ey = q1 - center[1], ez = q2 - center[2];
-                in = ex * ex + ey * ey + ez * ez <= r2;
-            }
-            const unsigned long long mask = __ballot(in);
-            const int hits = __popcll(mask);
-            if (in) {                                         // radiusSearch hit order = the oracle's accumulation order
-                const int r = __popcll(mask & ((1ull << lane) - 1));
-                pr[0 * PC_LROW + r] = q0 * q0; pr[1 * PC_LROW + r] = q0 * q1; pr[2 * PC_LROW + r] = q0 * q2; pr[3 * PC_LROW + r] = q0;
-                pr[4 * PC_LROW + r] = q1 * q1; pr[5 * PC_LROW + r] = q1 * q2; pr[6 * PC_LROW + r] = q1;
-                pr[7 * PC_LROW + r] = q2 * q2; pr[8 * PC_LROW + r] = q2;
-            }
-            __builtin_amdgcn_wave_barrier();                  // LDS is in order within a wave; keep the compiler in order too
-#pragma unroll 8
-            for (int r = 0; r < hits; ++r) M += mine[r];
-            __builtin_amdgcn_wave_barrier();
-            k += hits;
-        }
-    }
+    double M;
+    int k;
+    pc_sphere_moments(g, center, seg0, seg1, A.sp, pr, lane, M, k);
     if (lane < 16) A.M[(size_t)leaf * 16 + lane] = M;
     if (lane == 0) A.kcount[leaf] = k;
 }
@@ -335,34 +100,8 @@ __global__ __launch_bounds__(PC_FRAME_THREADS) void pc_frame_kernel(PcArgs A)
 {
     const int leaf = blockIdx.x * PC_FRAME_THREADS + threadIdx.x;
     if (leaf >= A.P) return;
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (A.kcount[leaf] >= 4) {                                // :31-34
-        double Mm[4][4], v[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) Mm[a][b] = A.M[(size_t)leaf * 16 + 4 * a + b];
-        pc_smallest_eigvec4(Mm, v);
-        double normal[3] = {v[0], v[1], v[2]};
-        pc_normalize(normal);
-        const double x[3] = {1, 0, 0}, y[3] = {0, 1, 0}, z[3] = {0, 0, 1};
-        double c1[3], c2[3];
-        const double ax = fabs(normal[0]), ay = fabs(normal[1]), az = fabs(normal[2]);
-        if (ax > ay && ax > az) {
-            if (normal[0] < 0) { normal[0] = -normal[0]; normal[1] = -normal[1]; normal[2] = -normal[2]; }
-            pc_cross(z, normal, c1);
-        } else if (ay > ax && ay > az) {
-            if (normal[1] < 0) { normal[0] = -normal[0]; normal[1] = -normal[1]; normal[2] = -normal[2]; }
-            pc_cross(x, normal, c1);
-        } else {
-            if (normal[2] < 0) { normal[0] = -normal[0]; normal[1] = -normal[1]; normal[2] = -normal[2]; }
-            pc_cross(y, normal, c1);
-        }
-        pc_normalize(c1);
-        pc_cross(normal, c1, c2);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { R[a] = normal[a]; R[3 + a] = c1[a]; R[6 + a] = c2[a]; }
-    }
+    double R[9];
+    pc_frame_of_moments(A.M + (size_t)leaf * 16, A.kcount[leaf], R);
 #pragma unroll
     for (int i = 0; i < 9; ++i) A.R[(size_t)leaf * 9 + i] = R[i];
 }
@@ -535,26 +274,6 @@ __global__ __launch_bounds__(PC_THREADS) void pc_emit_kernel(PcArgs A)
 // (struct gpc_patches: producer_internal.h)
 namespace {
 
-int bits_for(int kmax)
-{
-    int b = 1;
-    while ((1ll << b) <= (long long)kmax) ++b;
-    return b;
-}
-
-// carves 256-byte aligned pieces out of one buffer; with base == nullptr it only measures
-struct Carver {
-    char* base;
-    size_t used = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    template <class T> T* take(size_t count)
-    {
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
 struct Scratch {                // per call, in the context's workspace
     uint32_t* bounds;
     uint64_t *k0, *k1, *leaf_key;
@@ -565,7 +284,7 @@ struct Scratch {                // per call, in the context's workspace
     size_t prim_bytes;
 };
 
-size_t carve_scratch(Carver& c, Scratch& s, size_t n, size_t pb, size_t prim_bytes)
+size_t carve_scratch(PcCarver& c, Scratch& s, size_t n, size_t pb, size_t prim_bytes)
 {
     s.bounds = c.take<uint32_t>(8);
     s.k0 = c.take<uint64_t>(n); s.k1 = c.take<uint64_t>(n);
@@ -602,7 +321,7 @@ extern "C" {
 
 // Safe in either order with gpc_ctx_destroy (the batch holds a reference on its context; hipFree synchronises the device).
 // the caller holds ctx->mu (or the object was never published): the error paths of gpc_project_cloud_dev end here
-static void pc_patches_release(gpc_patches* o)
+void pc_patches_release(gpc_patches* o)
 {
     if (!o) return;
     gpc_ctx* ctx = o->ctx;
@@ -678,6 +397,7 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
     g.radius = std::sqrt(3.0f) / 2.0f * res;            // :194
     g.half = res / 2.0f;
     g.sz = sz;
+    g.koff[0] = g.koff[1] = g.koff[2] = 0;
     double cells = 1.0;
     for (int a = 0; a < 3; ++a) {
         g.mn[a] = (double)pc_unordered(hb[a]);
@@ -689,7 +409,7 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
         g.kmax[a] = (int)ext;
         cells *= ext + 1.0;
     }
-    g.bx = bits_for(g.kmax[0]); g.by = bits_for(g.kmax[1]); g.bz = bits_for(g.kmax[2]);
+    g.bx = pc_bits_for(g.kmax[0]); g.by = pc_bits_for(g.kmax[1]); g.bz = pc_bits_for(g.kmax[2]);
     const int key_bits = g.bx + g.by + g.bz;           // <= 63
     const size_t pb = cells < (double)n ? (size_t)cells : N;   // bound on the number of leaves
 
@@ -702,10 +422,10 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
     const size_t prim_bytes = std::max(sort_bytes, std::max(scan_bytes, scan2_bytes));
     Scratch S;
     {
-        Carver measure(nullptr);
+        PcCarver measure(nullptr);
         const int rc = gpc_ws_reserve(ctx, carve_scratch(measure, S, N, pb, prim_bytes));
         if (rc != GPC_OK) { pc_patches_release(o); return rc; }
-        Carver c(ctx->ws);
+        PcCarver c(ctx->ws);
         carve_scratch(c, S, N, pb, prim_bytes);
     }
 
@@ -735,9 +455,9 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
 
     // the result: one block; per-point arrays are sized by n (an upper bound of the points owned)
     const size_t Pz = (size_t)P, m = (size_t)(sz * sz);
-    Carver oc(nullptr);
+    PcCarver oc(nullptr);
     for (int pass = 0; pass < 2; ++pass) {
-        oc = Carver(pass ? o->block : nullptr);
+        oc = PcCarver(pass ? o->block : nullptr);
         o->v.off = oc.take<int32_t>(Pz + 1);
         o->v.rotations = oc.take<double>(9 * Pz);
         o->v.means = oc.take<double>(3 * Pz);

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(RG_THREADS) void rg_assign_kernel(RgArgs A)
     bool near = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        kd[a] = floor((p[a] - g.mn[a]) / g.res);
+        kd[a] = floor((p[a] - g.mn[a]) / g.res) + (double)g.koff[a];       // (koff: producer_internal.h; 0 unless the map grew downwards)
         near = near && kd[a] >= -1.0 && kd[a] <= (double)g.kmax[a] + 1.0;
     }
     int owner = -1;
@@ -595,6 +595,19 @@ int gpc_registration_get_cloud(gpc_registration* r, gpc_point_xyzrgb* cloud)
     GPC_HIP(ctx, hipSetDevice(ctx->device));
     GPC_HIP(ctx, hipMemcpyAsync(cloud, r->cloud, sizeof(gpc_point_xyzrgb) * (size_t)r->n, hipMemcpyDeviceToHost, ctx->stream));
     GPC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GPC_OK;
+}
+
+int gpc_registration_cloud_dev(gpc_registration* r, const gpc_point_xyzrgb** cloud, int* n)
+{
+    if (!r) return GPC_EINVAL;
+    gpc_ctx* ctx = r->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!rg_usable(r)) return GPC_EINVAL;
+    if (!cloud || !n) return gpc_fail(ctx, GPC_EINVAL, "cloud/n is NULL");
+    *cloud = r->n > 0 ? r->cloud : nullptr;
+    *n = r->n;
     return GPC_OK;
 }
 

@@ -11,6 +11,27 @@ static void sp_free_all(gpc_sparse* g)
     delete g;
 }
 
+// gpc_sparse_remap: the state of patch i of `src` goes to patch map[i] of `dst` (same ld, same ny); one workgroup per source patch
+__global__ __launch_bounds__(256) void sp_remap_kernel(const double* alpha, const double* C, const double* Q, const double* BV, const int32_t* b,
+                                                       const int32_t* count, const int32_t* stat, const int32_t* map, int ny, int ld,
+                                                       double* alpha_o, double* C_o, double* Q_o, double* BV_o, int32_t* b_o, int32_t* count_o,
+                                                       int32_t* stat_o)
+{
+    const size_t i = blockIdx.x, j = (size_t)map[i];
+    const size_t na = (size_t)ny * ld, nc = (size_t)ld * ld, nb = (size_t)ld * 2;
+    for (size_t e = threadIdx.x; e < nc; e += 256) {
+        C_o[j * nc + e] = C[i * nc + e];
+        Q_o[j * nc + e] = Q[i * nc + e];
+    }
+    for (size_t e = threadIdx.x; e < na; e += 256) alpha_o[j * na + e] = alpha[i * na + e];
+    for (size_t e = threadIdx.x; e < nb; e += 256) BV_o[j * nb + e] = BV[i * nb + e];
+    if (threadIdx.x == 0) {
+        b_o[j] = b[i];
+        count_o[j] = count[i];
+        stat_o[j] = stat[i];
+    }
+}
+
 extern "C" {
 
 int gpc_sparse_create(gpc_ctx* ctx, const gpc_params* params, int P, int ny, gpc_sparse** out)
@@ -82,6 +103,48 @@ void gpc_sparse_destroy(gpc_sparse* g)
 }
 
 int gpc_sparse_ld(const gpc_sparse* g) { return g ? g->ld : GPC_EINVAL; }
+
+int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_sparse** out)
+{
+    if (!old) return GPC_EINVAL;
+    gpc_ctx* ctx = old->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (!out) return gpc_fail(ctx, GPC_EINVAL, "out is NULL");
+    *out = nullptr;
+    const int P = old->P;
+    if (P_new < P) return gpc_fail(ctx, GPC_EINVAL, "P_new %d is smaller than the object's P %d", P_new, P);
+    if (P > 0 && !old_to_new) return gpc_fail(ctx, GPC_EINVAL, "old_to_new is NULL");
+    for (int i = 0; i < P; ++i)
+        if (old_to_new[i] < 0 || old_to_new[i] >= P_new || (i > 0 && old_to_new[i] <= old_to_new[i - 1]))
+            return gpc_fail(ctx, GPC_EINVAL, "old_to_new[%d] = %d: the table must be strictly increasing within [0, %d)", i, old_to_new[i], P_new);
+    gpc_sparse* g = nullptr;
+    if (int rc = gpc_sparse_create(ctx, &old->prm, P_new, old->ny, &g)) return rc;      // every patch empty, as after gpc_sparse_reset
+    if (P == 0) { *out = g; return GPC_OK; }
+    hipError_t e;
+    void* d_map = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        hipStream_t st = ctx->stream;
+        e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = hipMalloc(&d_map, 4 * (size_t)P);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_map, old_to_new, 4 * (size_t)P, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(sp_remap_kernel, dim3(P), dim3(256), 0, st, old->alpha, old->C, old->Q, old->BV, old->b, old->count, old->stat,
+                               (const int32_t*)d_map, old->ny, old->ld, g->alpha, g->C, g->Q, g->BV, g->b, g->count, g->stat);
+            e = hipGetLastError();
+        }
+        const hipError_t es = hipStreamSynchronize(st);                                  // the table is the caller's again; d_map goes
+        if (e == hipSuccess) e = es;
+        if (d_map) (void)hipFree(d_map);
+    }
+    if (e != hipSuccess) {
+        const int rc = gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_remap: %s", hipGetErrorString(e));
+        gpc_sparse_destroy(g);
+        return rc;
+    }
+    *out = g;
+    return GPC_OK;
+}
 
 int gpc_sparse_set_trace(gpc_sparse* g, uint8_t* trace_dev)
 {

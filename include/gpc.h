@@ -239,6 +239,11 @@ int gpc_sparse_ld(const gpc_sparse* g);
  * src/gp_compressor.cpp:21-27): same layouts, host pointers; C and Q may be NULL (zeroed -- enough for the mean prediction) */
 int gpc_sparse_set_state(gpc_sparse* g, const int32_t* bv_count, const double* alpha, const double* C, const double* Q,
                          const double* BV);
+/* The map grew (gpc_patches_insert_cloud): a NEW object of P_new patches with old's parameters, ny and leading dimension, in which
+ * patch old_to_new[i] holds the state of old's patch i -- alpha, C, Q, BV, basis count and the per-patch counters, copied exactly
+ * on the device -- and every other patch is empty, as after gpc_sparse_reset.  old_to_new: host, old's P entries, strictly
+ * increasing, < P_new (else GPC_EINVAL).  old is untouched; the two objects are destroyed independently. */
+int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_sparse** out);
 
 /* ---- hyper-parameter training: the live part of sparse_gp::train_parameters ---------------- */
 /* src/sparse_gp.hpp:586-640 up to the exit(0) at :640 (the call site is commented out upstream, src/gp_compressor.cpp:161):
@@ -310,6 +315,35 @@ int gpc_patches_fetch(const gpc_patches* p, int32_t* off, double* x0, double* x1
                       double* means, double* rgb_means, uint8_t* W, int32_t* src);
 void gpc_patches_destroy(gpc_patches* p);
 
+/* ---- mapping (gp_mapping::insert_into_map, src/gp_mapping.cpp:37-152): a registered scan goes into the map ---------------------
+ * Cuts `cloud` (n records; _dev: device pointer) against the leaf table of `model` and returns a NEW batch; `model` is untouched
+ * and both are destroyed independently.  Synchronous, like gpc_project_cloud (sizes depend on the data).
+ *   leaves   every leaf of the model, plus every voxel new to it whose search sphere holds >= min_nbr scan points (:126; upstream
+ *            min_nbr = 100).  The leaf table is the merge of the two sorted key lists, leaf id = position in it (the reference
+ *            appends instead, :88-95); old_to_new (host, the model's P entries) is the resulting monotone renumbering.
+ *   grid     res, sz and the anchor are the model's; the grid grows by whole voxels to cover the scan, below the anchor too.
+ *            Non-finite coordinate: GPC_EINVAL; more than 2^21 voxels along an axis: GPC_ERANGE.
+ *   frames   kept  = old leaf whose depth GP (`depth`, ny == 1, the model's P; NULL: every leaf counts as trained) is not empty
+ *                    (:115): keeps R_i, mean_i, rgb_mean_i (transform_to_old, :213-243);
+ *            fresh = new leaf, or old leaf with an empty depth GP and >= min_nbr scan points in its sphere (:121-137): the
+ *                    producer's treatment on the scan's points (frame of the sphere's moment matrix, origin at the voxel centre,
+ *                    depth-mean shift and colour mean over what it owns, transform_to_new :245-291);
+ *            an old untrained leaf below min_nbr keeps its frame and gets no points.
+ *   points   every scan point goes to the first kept or fresh leaf in leaf order, out of the <= 27 around its voxel, whose search
+ *            sphere (around the voxel centre, :96) holds it and whose +-res/2 window -- around the stored mean for a kept leaf
+ *            (:227-228), around the voxel centre for a fresh one (:266-267) -- accepts it.
+ *   batch    off / x0 / x1 / y / rgb / src hold the SCAN's points only (what S[i] holds when train_processes runs), ascending scan
+ *            index inside a leaf, src = scan index.  Kept leaf: depth as is, colours minus the stored rgb_mean (:237); fresh leaf:
+ *            mean-removed depth and colours.  W: old mask | cells hit now (kept, :242), cells hit now (fresh, :290), old mask (other).
+ * Deviations: upstream lets to_be_added of a leaf below min_nbr pile up across scans and pairs it with a mis-indexed last_inds
+ * (:261); here the threshold looks at the current scan only -- the reference's behaviour for a leaf's first scan.
+ * train_classification (the ray-cast free mask, :154-211) is not part of this: its only reader never uses it.
+ * The same inputs give the same bits.  Follow with gpc_sparse_remap on both GPs and gpc_sparse_add_dev on the new batch. */
+int gpc_patches_insert_cloud(gpc_ctx* ctx, const gpc_patches* model, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud, int n,
+                             int min_nbr, gpc_patches** out, int32_t* old_to_new);
+int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud,
+                                 int n, int min_nbr, gpc_patches** out, int32_t* old_to_new);
+
 /* ---- scan-to-model registration (SURVEY section 8, row f): gp_registration on the GPU ------------------------------------ */
 /* gp_registration (src/gp_registration.h, src/gp_registration.cpp) aligns a scan to a trained model by gradient ascent on the
  * mean likelihood of the scan's points under the per-leaf depth and colour GPs.  One step (registration_step, :73-92) is
@@ -357,6 +391,9 @@ int gpc_registration_run(gpc_registration* r, const gpc_registration_params* par
 int gpc_registration_get_transform(gpc_registration* r, double R[9], double t[3]);
 /* the working cloud, n records (host) */
 int gpc_registration_get_cloud(gpc_registration* r, gpc_point_xyzrgb* cloud);
+/* ... as a DEVICE pointer (read-only for the caller; valid until the next set_cloud or destroy): the registered scan goes into
+ * gpc_patches_insert_cloud_dev without a host round trip */
+int gpc_registration_cloud_dev(gpc_registration* r, const gpc_point_xyzrgb** cloud, int* n);
 /* Diagnostic, like gpc_sparse_set_trace: what the LAST step assigned.  owner [n]: the leaf of every scan point, -1 = unused;
  * local [n][3]: its coordinates in that leaf's frame (depth, x0, x1).  Host pointers, each may be NULL. */
 int gpc_registration_get_assignment(gpc_registration* r, int32_t* owner, double* local);
