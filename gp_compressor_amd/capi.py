@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPC_LIB_PATH", os.path.join(HERE, "libgpc_hip.so"))   # override: diagnostic builds only
 
 GPC_OK, GPC_EINVAL, GPC_ENOMEM, GPC_ENODEV, GPC_EHIP, GPC_ERANGE = 0, -22, -12, -19, -5, -34
+CELL_UNOBSERVED, CELL_OCCUPIED, CELL_FREE = 0, 1, 2
 STATUS_OK, STATUS_NOT_SPD, STATUS_NAN, STATUS_SIGMA_CLAMPED, STATUS_OVERFLOW, STATUS_NOT_CONVERGED = 0, 1, 2, 3, 4, 5
 MAX_POINTS, MAX_BV = 1024, 256
 
@@ -108,6 +109,9 @@ PROTOTYPES = {
     "gpc_patches_destroy": (None, [_vp]),
     "gpc_patches_insert_cloud": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp), _vp]),
     "gpc_patches_insert_cloud_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(_vp), _vp]),
+    "gpc_patches_raycast": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "gpc_patches_raycast_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "gpc_occupancy_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
     "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "gpc_registration_destroy": (None, [_vp]),
@@ -376,7 +380,7 @@ class Context:
                                                    C.byref(h)))
         else:
             self._check(self.lib.gpc_project_cloud_dev(self.h, _ptr(cloud), int(n), float(res), int(sz), C.byref(h)))
-        return Patches(self, h)
+        return Patches(self, h, float(res))
 
     def reproject_dev(self, P, m, bv_count, xs0, xs1, f_star, c_star, rotations, means, rgb_means, cloud, n_points):
         self._check(self.lib.gpc_reproject_dev(self.h, P, m, _ptr(bv_count), _ptr(xs0), _ptr(xs1), _ptr(f_star), _ptr(c_star),
@@ -399,8 +403,9 @@ class Context:
 class Patches:
     """gpc_patches: the batch gp_compressor::project_cloud produces, resident on the device."""
 
-    def __init__(self, ctx, h):
+    def __init__(self, ctx, h, res=None):
         self.ctx, self.lib, self.h = ctx, ctx.lib, h
+        self.res = res                                     # the voxel side the batch was cut with (None: the creator did not say)
         self.view = PatchesView()
         ctx._check(self.lib.gpc_patches_view_dev(h, C.byref(self.view)))
         ctx._children.add(self)
@@ -439,7 +444,45 @@ class Patches:
         else:
             rc = self.lib.gpc_patches_insert_cloud_dev(self.ctx.h, self.h, dh, _ptr(cloud), int(n), int(min_nbr), C.byref(h), _ptr(o2n))
         self.ctx._check(rc)
-        return Patches(self.ctx, h), o2n[:self.view.P]
+        return Patches(self.ctx, h, self.res), o2n[:self.view.P]
+
+    def raycast(self, cloud, origin, cells, depth=None, n=None):
+        """gpc_patches_raycast[_dev] (train_classification): the rays from the sensor `origin` (3,) to the points of `cloud` -- the cloud
+        this batch was cut from, a host record array or a device buffer of n records -- label `cells` (P, m) uint8, in place: a numpy
+        array with a host cloud, a device tensor with a device cloud.  depth: the map's depth Sparse as it is BEFORE the scan is
+        trained (None: every leaf counts as trained).  Returns counts (4,) int32: rays, rays that did nothing, occupied writes, free
+        writes."""
+        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        counts = np.zeros(4, dtype=np.int32)
+        dh = depth.h if depth is not None else None
+        v = self.view
+        if isinstance(cloud, np.ndarray):
+            assert cloud.dtype == Context.POINT_DTYPE
+            cloud = np.ascontiguousarray(cloud)
+            assert isinstance(cells, np.ndarray) and cells.dtype == np.uint8 and cells.size == v.P * v.m
+            rc = self.lib.gpc_patches_raycast(self.ctx.h, self.h, dh, _ptr(cloud) if len(cloud) else None, len(cloud), _ptr(org),
+                                              _ptr(cells), _ptr(counts))
+        else:
+            assert cells.numel() == v.P * v.m and cells.element_size() == 1
+            rc = self.lib.gpc_patches_raycast_dev(self.ctx.h, self.h, dh, _ptr(cloud), int(n), _ptr(org), _ptr(cells), _ptr(counts))
+        self.ctx._check(rc)
+        return counts
+
+    def occupancy_batch(self, cells):
+        """gpc_occupancy_batch_dev: the labelled cells (device tensor (P, m) uint8) as the ragged batch the probit GP reads -- per leaf the
+        observed cells in ascending cell index at their centres, y = +1 occupied / -1 free.  Returns device tensors off (P + 1,) int32,
+        x0, x1, y (n_total,) float64 (views of P * m entries) and the host sizes n_total, n_max."""
+        import torch
+        v = self.view
+        assert cells.numel() == v.P * v.m and cells.element_size() == 1
+        off = torch.zeros(v.P + 1, dtype=torch.int32, device=cells.device)
+        x0, x1, y = (torch.zeros(max(v.P * v.m, 1), dtype=torch.float64, device=cells.device) for _ in range(3))
+        nt, nm = C.c_int32(0), C.c_int32(0)
+        torch.cuda.synchronize(cells.device)               # the buffers above were filled on torch's stream
+        self.ctx._check(self.lib.gpc_occupancy_batch_dev(self.ctx.h, self.h, _ptr(cells), _ptr(off), _ptr(x0), _ptr(x1), _ptr(y),
+                                                         C.addressof(nt), C.addressof(nm)))
+        N = int(nt.value)
+        return off, x0[:N], x1[:N], y[:N], N, int(nm.value)
 
 
 class Sparse:
@@ -684,12 +727,16 @@ class Mapping:
         self.params = params if params is not None else default_params_registration()
         self.min_nbr = int(min_nbr)
         self.reg = Registration(ctx, patches, depth, rgb)
+        # the occupancy labels of every leaf's cells (train_classification's `free`, with a third state): CELL_UNOBSERVED until a ray
+        # of an inserted scan meets the cell
+        import torch
+        self.cells = torch.zeros((patches.view.P, patches.view.m), dtype=torch.uint8, device="cuda")
 
     def close(self):
         for o in (getattr(self, "reg", None), getattr(self, "depth", None), getattr(self, "rgb", None), getattr(self, "patches", None)):
             if o is not None:
                 o.close()
-        self.reg = self.depth = self.rgb = self.patches = None
+        self.reg = self.depth = self.rgb = self.patches = self.cells = None
 
     def add_cloud(self, cloud, n=None, perm_depth=None, perm_rgb=None):
         """gp_mapping::add_cloud (:12-28): register the scan (host record array or device buffer of n records) against the map; if the
@@ -705,6 +752,13 @@ class Mapping:
         pt, o2n = self.patches.insert_cloud(d_cloud, self.min_nbr, self.depth, n=m)
         v = pt.view
         gd, gc = self.depth.remap(v.P, o2n), self.rgb.remap(v.P, o2n)
+        # train_classification (:148, before train_processes): the leaves the scan trains below do not count as trained yet
+        import torch
+        cells = torch.zeros((v.P, v.m), dtype=torch.uint8, device=self.cells.device)
+        cells[torch.from_numpy(o2n.astype(np.int64)).to(cells.device)] = self.cells
+        torch.cuda.synchronize(cells.device)
+        pt.raycast(d_cloud, self.reg.transform()[1], cells, depth=gd, n=m)
+        self.cells = cells
         gd.add_dev(v.off, v.n_max, v.n_total, v.x0, v.x1, v.y, perm_depth)
         gc.add_dev(v.off, v.n_max, v.n_total, v.x0, v.x1, v.rgb, perm_rgb)
         self.ctx.synchronize()
@@ -713,6 +767,25 @@ class Mapping:
             o.close()
         self.reg, self.patches, self.depth, self.rgb = reg, pt, gd, gc
         return steps, True
+
+    def occupancy(self, params, irls=None):
+        """The occupancy layer of the map: the probit GP (dense_irls_fit_predict_dev; params: noise_model 1 or 2) trained per leaf on the
+        labelled cells, evaluated on the leaf's sz x sz grid.  Returns device tensors f_star (P, m) float64 -- the latent mean, > 0
+        towards occupied, 0 for a leaf without an observed cell -- and status (P,) int32."""
+        import torch
+        pt = self.patches
+        if pt.res is None:
+            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
+        P, msz = pt.view.P, pt.view.m
+        sz = int(round(msz ** 0.5))
+        off, x0, x1, y, n_total, n_max = pt.occupancy_batch(self.cells)
+        f = torch.zeros((P, msz), dtype=torch.float64, device=self.cells.device)
+        st = torch.full((P,), -1, dtype=torch.int32, device=self.cells.device)
+        torch.cuda.synchronize(self.cells.device)
+        self.ctx.dense_irls_fit_predict_dev(params, irls if irls is not None else default_params_irls(), P, off, n_max, n_total, x0, x1, y,
+                                            msz, None, None, pt.res, sz, f, status=st)
+        self.ctx.synchronize()
+        return f, st
 
 
 class Comm:

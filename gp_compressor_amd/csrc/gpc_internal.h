@@ -92,6 +92,13 @@ static inline void gpc_child_unregister(gpc_ctx* ctx, const void* obj)
             return;
         }
 }
+// Is obj a live object of THIS context?  (An object of another context is not in the list: found out without touching it.)
+static inline bool gpc_child_listed(const gpc_ctx* ctx, const void* obj)
+{
+    for (const auto& c : ctx->children)
+        if (c.first == obj) return true;
+    return false;
+}
 static inline bool gpc_child_alive(const gpc_ctx* ctx, const void* obj, uint64_t serial)
 {
     for (const auto& c : ctx->children)

@@ -16,7 +16,7 @@
 // reference appends, :88-95); old_to_new is that monotone renumbering.
 // Deviations from upstream: its to_be_added of a leaf below the threshold piles up across scans and is then paired with a mis-indexed
 // last_inds (:261); here the threshold looks at the current scan only, which is the reference's behaviour for a leaf's first scan.
-// train_classification (the ray-cast free mask, :154-211) is not built: its only reader never uses it (src/gp_compressor.cpp:329).
+// train_classification (the ray-cast free mask, :154-211), which upstream runs between this and train_processes, is raycast.hip.
 //
 // The grid keeps the model's anchor mn and resolution; its whole-voxel origin shift koff and its extent kmax grow to cover the scan
 // (producer_internal.h), so no old voxel centre moves.  Pipeline (integer / gather work, one stream, three reads of a few bytes):
@@ -372,13 +372,6 @@ __global__ __launch_bounds__(PC_THREADS) void mp_emit_kernel(MpArgs A)
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
-bool mp_listed(const gpc_ctx* ctx, const void* obj)
-{
-    for (const auto& c : ctx->children)
-        if (c.first == obj) return true;
-    return false;
-}
-
 struct MpScratch {
     uint32_t* bounds;
     uint64_t *k0, *k1, *okey, *ukey;
@@ -440,7 +433,7 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
     if (min_nbr < 1) return gpc_fail(ctx, GPC_EINVAL, "min_nbr must be >= 1");
     std::lock_guard<std::mutex> lk(ctx->mu);
     // (an object of another context is not in this context's list: found out without touching it)
-    if (!mp_listed(ctx, model) || (depth && !mp_listed(ctx, depth)))
+    if (!gpc_child_listed(ctx, model) || (depth && !gpc_child_listed(ctx, depth)))
         return gpc_fail(ctx, GPC_EINVAL, "model and depth must be live objects of this context");
     const int P0 = model->v.P;
     if (depth && (depth->ny != 1 || depth->P != P0))

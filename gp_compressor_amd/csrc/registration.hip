@@ -327,13 +327,6 @@ bool rg_usable(const gpc_registration* r)
            gpc_child_alive(ctx, r->gc, r->gc_serial);
 }
 
-bool rg_listed(const gpc_ctx* ctx, const void* obj)
-{
-    for (const auto& c : ctx->children)
-        if (c.first == obj) return true;
-    return false;
-}
-
 int rg_check_params(gpc_ctx* ctx, const gpc_registration_params* p)
 {
     if (!p) return gpc_fail(ctx, GPC_EINVAL, "params is NULL");
@@ -465,7 +458,7 @@ int gpc_registration_create(gpc_ctx* ctx, const gpc_patches* patches, gpc_sparse
     if (!patches || !depth || !rgb) return gpc_fail(ctx, GPC_EINVAL, "patches/depth/rgb is NULL");
     std::lock_guard<std::mutex> lk(ctx->mu);
     // (an object of another context is not in this context's list: found out without touching it)
-    if (!rg_listed(ctx, patches) || !rg_listed(ctx, depth) || !rg_listed(ctx, rgb))
+    if (!gpc_child_listed(ctx, patches) || !gpc_child_listed(ctx, depth) || !gpc_child_listed(ctx, rgb))
         return gpc_fail(ctx, GPC_EINVAL, "patches, depth and rgb must be live objects of this context");
     if (depth->ny != 1 || rgb->ny != 3) return gpc_fail(ctx, GPC_EINVAL, "depth must have ny == 1 and rgb ny == 3");
     if (depth->P != patches->v.P || rgb->P != patches->v.P)

@@ -145,7 +145,7 @@ int gpc_dense_fit_predict_grid_dev(gpc_ctx* ctx, const gpc_params* params, int P
 
 /* ---- dense GP with the probit functor: Newton / IRLS loop on the GPU (BASELINE config 5) ---------------------------- */
 /* The reference never instantiates probit_noise and holds no IRLS loop (its occupancy map is a ray-cast boolean mask,
- * src/gp_mapping.cpp:154-211): what it fixes is the Noise contract, q = dx_ln(y, x, sigma_x), r = dx2_ln(y, x, sigma_x)
+ * src/gp_mapping.cpp:154-211 -- gpc_patches_raycast + gpc_occupancy_batch_dev below turn it into this entry's labels): what it fixes is the Noise contract, q = dx_ln(y, x, sigma_x), r = dx2_ln(y, x, sigma_x)
  * (src/probit_noise.cpp:11-31), and the kernel.  This entry runs the textbook loop those plug into -- Newton's method for
  * the mode of p(f | y) with labels y = +-1 (Rasmussen & Williams 2006, Alg. 3.1) in IRLS form: with W = -r, g = q at
  * sigma_x = 0, every step is one gaussian_process::add_measurements-style fit (src/gaussian_process.cpp:15-26) with
@@ -337,12 +337,58 @@ void gpc_patches_destroy(gpc_patches* p);
  *            mean-removed depth and colours.  W: old mask | cells hit now (kept, :242), cells hit now (fresh, :290), old mask (other).
  * Deviations: upstream lets to_be_added of a leaf below min_nbr pile up across scans and pairs it with a mis-indexed last_inds
  * (:261); here the threshold looks at the current scan only -- the reference's behaviour for a leaf's first scan.
- * train_classification (the ray-cast free mask, :154-211) is not part of this: its only reader never uses it.
+ * train_classification (the ray-cast free mask, :154-211) is its own entry: gpc_patches_raycast below.
  * The same inputs give the same bits.  Follow with gpc_sparse_remap on both GPs and gpc_sparse_add_dev on the new batch. */
 int gpc_patches_insert_cloud(gpc_ctx* ctx, const gpc_patches* model, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud, int n,
                              int min_nbr, gpc_patches** out, int32_t* old_to_new);
 int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud,
                                  int n, int min_nbr, gpc_patches** out, int32_t* old_to_new);
+
+/* ---- mapping (gp_mapping::train_classification, src/gp_mapping.cpp:154-211): the scan's rays label the cells of the leaves ------
+ * Every scan ray, from the sensor `origin` to its point, is cast through the leaf table of `map`; on the plane of every trained
+ * leaf it crosses between the sensor and the leaf that owns the point, the cell it meets is recorded as seen through (free), on the
+ * owner's plane as hit (occupied).  Upstream keeps one boolean per cell (`free`, :203-208), which cannot tell "never seen" from
+ * "occupied"; here a cell has three states: */
+#define GPC_CELL_UNOBSERVED 0   /* no ray of any scan met the cell: the initial value of a cell buffer */
+#define GPC_CELL_OCCUPIED 1     /* free(ind, m) = false, :204: the last ray that met the cell ended in this leaf */
+#define GPC_CELL_FREE 2         /* free(ind, m) = true, :207: the last ray that met the cell went on to another leaf */
+/* `map` is the batch gpc_patches_insert_cloud (or gpc_project_cloud) cut from THIS cloud: the owner of scan point i is the leaf whose
+ * bucket holds it (gp_indices, :66-69, :233, :273), taken from the batch's off / src.  A batch that holds more points than n, or
+ * a src entry >= n, is another cloud's: GPC_EINVAL.
+ *   trained  a leaf whose depth GP (`depth`, ny == 1, the map's P) has a basis vector (gps[m].size() > 0, :180) at the time of the
+ *            call -- upstream that is before train_processes, so pass the remapped object before gpc_sparse_add_dev.  NULL: every leaf.
+ *   rays     o32 = float(origin), delta = p - o32 in float (:169), both widened to double for the walk.  A ray does nothing when its
+ *            point is unowned (:176), its owner is untrained (:180) or it does not meet the owner's voxel (slab test; :183-190).
+ *   walk     from the owner's voxel back towards the sensor, one face at a time: at voxel k the entry parameters
+ *            n_a = (face_a - o_a) / delta_a (low face if delta_a > 0, else high; -inf if delta_a == 0) are recomputed from the
+ *            integer coordinate; max n_a <= 0: the sensor is in or behind the voxel, stop; else step across the first axis that
+ *            attains the maximum; stop on leaving the grid.  This is the reference's j loop (:175) from the far end once reached_gp
+ *            is set (:183-190), without the list.
+ *   planes   every visited voxel that is a trained leaf m, the owner included (:191-202): normal = column 0 of R_m,
+ *            d = normal . (mean_m - origin) / normal . delta with the DOUBLE origin (:194-195), loc = R_m^T (origin + d delta - mean_m),
+ *            the +-res/2 window on loc(1), loc(2) (:197), cell = sz * gx + gy with the clipped cell function of W.  A non-finite d or
+ *            loc skips the leaf (upstream: undefined behaviour in int(nan)).  As upstream, d is NOT range-checked: a plane that the
+ *            ray meets outside the voxel, or behind the sensor, but inside the window, is labelled all the same.
+ *   write    upstream's loop is sequential, so the last scan index wins a cell; here integer atomicMax of (i + 1) << 1 | is_free
+ *            per (leaf, cell), then touched cells of `cells` become GPC_CELL_OCCUPIED / GPC_CELL_FREE and the others keep what they
+ *            held.  The same inputs give the same bits.  n > 2^30: GPC_ERANGE.
+ * cells: P x m uint8 in the layout of W, in/out (DEVICE in _dev, HOST otherwise).  origin: host, 3 doubles.  counts: host int32[4] or
+ * NULL: rays cast, rays that did nothing, occupied writes, free writes (per ray and leaf, before the tie rule).
+ * gpc_patches_raycast_dev enqueues on the context's stream; it synchronises -- and reports what only the device can find: a
+ * non-finite coordinate, a src entry >= n -- only when counts != NULL.  In those two cases `cells` is left untouched either way.
+ * GPC_EINVAL: a non-finite origin or coordinate, objects of different contexts, a depth with another P or ny != 1, a cloud that is
+ * not the batch's.  n == 0: GPC_OK, cells as they were. */
+int gpc_patches_raycast(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud, int n,
+                        const double origin[3], uint8_t* cells, int32_t* counts);
+int gpc_patches_raycast_dev(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud, int n,
+                            const double origin[3], uint8_t* cells, int32_t* counts);
+/* The labelled batch the occupancy GP (gpc_dense_irls_fit_predict_dev) trains on, from a cell buffer: per leaf the observed cells in
+ * ascending cell index, at the cell centres of the decompression grid (src/gp_compressor.cpp:326-327),
+ * x0 = res*((gx+.5)/sz-.5), x1 = res*((gy+.5)/sz-.5), cell = sz*gx + gy, y = +1 (occupied) / -1 (free).  A leaf without an observed cell
+ * is an empty patch.  All buffers on the DEVICE: cells P x m, off P + 1, x0 / x1 / y of capacity P * m.  n_total = off[P] and n_max (the
+ * largest patch) are written to the host: the call synchronises, like the cutters. */
+int gpc_occupancy_batch_dev(gpc_ctx* ctx, const gpc_patches* map, const uint8_t* cells, int32_t* off, double* x0, double* x1, double* y,
+                            int32_t* n_total, int32_t* n_max);
 
 /* ---- scan-to-model registration (SURVEY section 8, row f): gp_registration on the GPU ------------------------------------ */
 /* gp_registration (src/gp_registration.h, src/gp_registration.cpp) aligns a scan to a trained model by gradient ascent on the
