@@ -40,6 +40,11 @@ class RegistrationParams(C.Structure):
                 ("ref_translation_sum", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RenderParams(C.Structure):
+    """struct gpc_render_params (include/gpc.h)."""
+    _fields_ = [("newton_iters", C.c_int32), ("use_w", C.c_int32), ("eps_rel", C.c_double), ("t_max", C.c_double)]
+
+
 class PatchesView(C.Structure):
     """struct gpc_patches_view (include/gpc.h): sizes + device addresses of a patch batch."""
     _fields_ = [("P", C.c_int32), ("n_total", C.c_int32), ("n_max", C.c_int32), ("m", C.c_int32)] + \
@@ -112,6 +117,10 @@ PROTOTYPES = {
     "gpc_patches_raycast": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "gpc_patches_raycast_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "gpc_occupancy_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_default_params_render": (None, [C.POINTER(RenderParams)]),
+    "gpc_patches_render": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RenderParams), _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_patches_render_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RenderParams), _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_camera_rays_dev": (C.c_int, [_vp, _vp, _d, _d, _d, _d, _i, _i, _vp]),
     "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
     "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "gpc_registration_destroy": (None, [_vp]),
@@ -210,6 +219,14 @@ def default_params_irls(**kw):
 def default_params_registration(**kw):
     p = RegistrationParams()
     load().gpc_default_params_registration(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_params_render(**kw):
+    p = RenderParams()
+    load().gpc_default_params_render(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -386,6 +403,18 @@ class Context:
         self._check(self.lib.gpc_reproject_dev(self.h, P, m, _ptr(bv_count), _ptr(xs0), _ptr(xs1), _ptr(f_star), _ptr(c_star),
                                                _ptr(rotations), _ptr(means), _ptr(rgb_means), _ptr(cloud), _ptr(n_points)))
 
+    def camera_rays(self, R, fx, fy, cx, cy, width, height):
+        """gpc_camera_rays_dev: the pinhole rays of a width x height image, pixel v * width + u -> R ((u - cx) / fx, (v - cy) / fy, 1), as a
+        device tensor (width * height, 3) float64 for Patches.render.  R (3, 3): the camera's axes in the world.  Not normalised."""
+        import torch
+        Rc = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(3, 3).T)      # column-major
+        dirs = torch.empty((int(width) * int(height), 3), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize(dirs.device)
+        self._check(self.lib.gpc_camera_rays_dev(self.h, _ptr(Rc), float(fx), float(fy), float(cx), float(cy), int(width), int(height),
+                                                 _ptr(dirs) if dirs.numel() else None))
+        self.synchronize()
+        return dirs
+
     # ---- dense, device buffers (torch tensors or raw addresses), asynchronous on the context's stream ---------
     def dense_fit_predict_dev(self, params, P, off, n_max, n_total, x0, x1, y, ny, m, xs0, xs1, f_star,
                               v_star=None, alpha_out=None, status=None):
@@ -467,6 +496,48 @@ class Patches:
             rc = self.lib.gpc_patches_raycast_dev(self.ctx.h, self.h, dh, _ptr(cloud), int(n), _ptr(org), _ptr(cells), _ptr(counts))
         self.ctx._check(rc)
         return counts
+
+    def render(self, origin, dirs, depth, rgb=None, cells=None, params=None, want=("leaf", "range", "local")):
+        """gpc_patches_render[_dev]: the map seen along the rays origin (3,) + t dirs[i] -- dirs (n, 3) float64, a numpy array (then cells
+        is a numpy array or None, and numpy arrays come back) or a device tensor (cells a device tensor or None, device tensors come
+        back, complete on return).  depth / rgb: the map's Sparse objects (rgb None: colours 0); cells (P, m) uint8: occupancy labels,
+        CELL_FREE cells let a ray through.  Returns a dict: cloud (n,) POINT_DTYPE records (device: (n, 32) uint8), counts (5,) int32 =
+        rays, hits, rays that never met the grid, surface tests, tests rejected on the residual, and the outputs named in `want`:
+        leaf (n,) int32 (-1 = miss), range (n,), local (n, 3) = (f, q1, q2)."""
+        org = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        prm = params if params is not None else default_params_render()
+        counts = np.zeros(5, dtype=np.int32)
+        v = self.view
+        rh = rgb.h if rgb is not None else None
+        shapes = dict(leaf=((), np.int32), range=((), np.float64), local=((3,), np.float64))
+        assert set(want) <= set(shapes)
+        out = {}
+        if isinstance(dirs, np.ndarray):
+            dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+            n = len(dirs)
+            if cells is not None:
+                assert isinstance(cells, np.ndarray) and cells.dtype == np.uint8 and cells.size == v.P * v.m
+                cells = np.ascontiguousarray(cells)
+            out["cloud"] = np.zeros(n, dtype=Context.POINT_DTYPE)
+            for k in want:
+                out[k] = np.zeros((n,) + shapes[k][0], dtype=shapes[k][1])
+            entry = self.lib.gpc_patches_render
+        else:
+            import torch
+            assert dirs.dtype == torch.float64 and dirs.numel() % 3 == 0
+            n = dirs.numel() // 3
+            if cells is not None:
+                assert cells.numel() == v.P * v.m and cells.element_size() == 1
+            out["cloud"] = torch.zeros((n, 32), dtype=torch.uint8, device=dirs.device)
+            for k in want:
+                out[k] = torch.zeros((n,) + shapes[k][0], dtype=torch.int32 if k == "leaf" else torch.float64, device=dirs.device)
+            torch.cuda.synchronize(dirs.device)             # the buffers above were filled on torch's stream
+            entry = self.lib.gpc_patches_render_dev
+        arg = lambda a: _ptr(a) if (a is not None and n) else None
+        self.ctx._check(entry(self.ctx.h, self.h, depth.h, rh, arg(cells), C.byref(prm), _ptr(org), arg(dirs), n, arg(out["cloud"]),
+                              arg(out.get("leaf")), arg(out.get("range")), arg(out.get("local")), _ptr(counts)))
+        out["counts"] = counts
+        return out
 
     def occupancy_batch(self, cells):
         """gpc_occupancy_batch_dev: the labelled cells (device tensor (P, m) uint8) as the ragged batch the probit GP reads -- per leaf the
@@ -767,6 +838,11 @@ class Mapping:
             o.close()
         self.reg, self.patches, self.depth, self.rgb = reg, pt, gd, gc
         return steps, True
+
+    def render(self, origin, dirs, params=None, use_cells=True, want=("leaf", "range", "local")):
+        """The map as a sensor at `origin` sees it along `dirs` (Context.camera_rays, or any (n, 3) float64 device tensor): Patches.render
+        on the map's current batch, depth and colour GPs; use_cells: cells a scan saw through (CELL_FREE) do not stop a ray."""
+        return self.patches.render(origin, dirs, self.depth, self.rgb, self.cells if use_cells else None, params, want)
 
     def occupancy(self, params, irls=None):
         """The occupancy layer of the map: the probit GP (dense_irls_fit_predict_dev; params: noise_model 1 or 2) trained per leaf on the

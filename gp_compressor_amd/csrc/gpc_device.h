@@ -140,6 +140,18 @@ __device__ static inline double gpc_rbf_small(double sf, double c, double xi0, d
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// flatten_colors (src/gp_compressor.cpp:251-265) of one value, shared by reproject.hip and render.hip:
+// x.cast<short>() as the x86-64 reference binary evaluates it (cvttsd2si, then truncation to 16 bits), then the clamp
+// ---------------------------------------------------------------------------------------------------------
+__device__ static inline uint8_t rp_flatten(double x)
+{
+    if (x != x || __builtin_isinf(x)) return 255;
+    const int w = (x >= 2147483648.0 || x < -2147483648.0) ? (int)0x80000000 : (int)x;     // (int)x truncates toward zero
+    const int v = (int)(short)(unsigned short)(unsigned)w;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // wave / block reductions
 // ---------------------------------------------------------------------------------------------------------
 __device__ static inline double gpc_wave_sum(double v)

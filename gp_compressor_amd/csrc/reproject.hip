@@ -38,15 +38,6 @@ __global__ __launch_bounds__(RP_SCAN_THREADS) void reproject_scan_kernel(int P, 
     if (tid == RP_SCAN_THREADS - 1) total[0] = part[tid] * m;
 }
 
-// x.cast<short>() as the x86-64 reference binary evaluates it (cvttsd2si, then truncation to 16 bits), then the clamp
-__device__ static inline uint8_t rp_flatten(double x)
-{
-    if (x != x || __builtin_isinf(x)) return 255;
-    const int w = (x >= 2147483648.0 || x < -2147483648.0) ? (int)0x80000000 : (int)x;     // (int)x truncates toward zero
-    const int v = (int)(short)(unsigned short)(unsigned)w;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 struct ReprojParams {
     int P, m;
     const double *xs0, *xs1, *f_star, *c_star, *R, *means, *rgb_means;

@@ -390,6 +390,72 @@ int gpc_patches_raycast_dev(gpc_ctx* ctx, const gpc_patches* map, const gpc_spar
 int gpc_occupancy_batch_dev(gpc_ctx* ctx, const gpc_patches* map, const uint8_t* cells, int32_t* off, double* x0, double* x1, double* y,
                             int32_t* n_total, int32_t* n_max);
 
+/* ---- rendering: the map as a sensor at a pose would see it ------------------------------------------------------------------------
+ * The inverse of a scan: n rays o + t d from one origin are cast through the leaf table of `map`, front to back, and each stops at
+ * the first leaf whose depth GP's MEAN SURFACE it meets inside that leaf's window.  Output is organised (record i belongs to ray i):
+ * with gpc_camera_rays_dev the cloud is the width x height image a depth camera at that pose would report.  The reference has no
+ * such read-out (its only one is load_compressed, every leaf's whole grid); the rule below is this library's, stated per ray with no
+ * order left to the scheduler, like the rules of gpc_patches_insert_cloud and gpc_patches_raycast.
+ *   objects  map; depth (ny == 1, the map's P) REQUIRED; rgb (ny == 3, the map's P) or NULL (colours 0); cells: P x m uint8 labels
+ *            in the layout of W (gpc_patches_raycast) or NULL.  All live objects of ctx, else GPC_EINVAL.
+ *   ray      origin o (host, 3 doubles, finite, else GPC_EINVAL) and direction d = dirs[3 i .. 3 i + 2], NOT normalised: t counts in
+ *            units of |d|.  A direction with a non-finite component, or all zero, is a miss (images carry masked pixels), not an error.
+ *   entry    slab test of o + t d, t >= 0, against the grid box, whose faces on axis a are mn_a + (k - koff_a) res for k = 0 and
+ *            kmax_a + 1: per axis with d_a != 0 the two face parameters (face - o_a) / d_a, tn = max of the smaller ones, tf = min of
+ *            the larger ones; an axis with d_a == 0 needs lo <= o_a < hi.  The ray meets the box iff tn <= tf and tf >= 0.
+ *            t_in = max(tn, 0); start voxel k_a = clamp(floor((o_a + t_in d_a - mn_a) / res) + koff_a, 0, kmax_a).
+ *   walk     at voxel k: if k is a leaf L whose depth GP has a basis vector, run the surface test of L; an accepted test ends the
+ *            ray (a hit).  Otherwise the exit parameters x_a = (face_a - o_a) / d_a (the HIGH face mn_a + (k_a - koff_a + 1) res if
+ *            d_a > 0, else the low face; axes with d_a == 0 are skipped) are recomputed from the integer coordinate, and the ray
+ *            steps across the first axis that attains the minimum.  Leaving [0, kmax] is a miss.  At most
+ *            kmax_x + kmax_y + kmax_z + 1 voxels are visited (every step moves one coordinate away from the origin).
+ *   surface  with R_L = (n, u, v) column-major and mean_L:  a = R_L^T (o - mean_L), c = R_L^T d (each a three-term sum, left to
+ *   test     right); t starts on the leaf's plane, t = n.(mean_L - o) / n.d as gpc_patches_raycast evaluates it.  Then exactly
+ *            newton_iters times, with no early exit:  q = (a1 + t c1, a2 + t c2);  k_j = sigmaf_sq exp(-0.5f / l_sq |q - BV_j|^2)
+ *            with the library's exp;  f = sum_j alpha_j k_j,  (fx, fy) = (sum_j alpha_j k_j (BV_j - q)) / l_sq, j ascending over the
+ *            min(basis count, ld) basis vectors;  g = (a0 + t c0) - f;  g' = c0 - (fx c1 + fy c2);  t <- t - g / g'.  One last
+ *            evaluation of q, f, g at the final t.  The test is ACCEPTED iff all of:
+ *              t, q, f, g finite;   |g| <= eps_rel res;   0 < t <= t_max;
+ *              not (q1 > res/2 or q1 < -res/2 or q2 > res/2 or q2 < -res/2)                          (upstream's window form);
+ *              x = R_L (f, q1, q2) + mean_L (in gpc_reproject's association, in double) has squared distance <= radius^2 to the
+ *              centre of voxel k, radius = float(sqrt(3.0f) / 2.0f) res                            (the producer's membership rule);
+ *              use_w != 0:  W[L][cell] != 0, cell = sz gx + gy, gx = clip(int(sz (q1 / res + 0.5)), 0, sz - 1), gy from q2;
+ *              cells != NULL:  cells[L][cell] != GPC_CELL_FREE.
+ *            A rejected test lets the ray go on to the next voxel.
+ *   hit      cloud[i]: xyz = float(x), w = 1, a = 255; r, g, b = flatten_colors(c_k + rgb_mean_L[k]) as gpc_reproject, c the colour
+ *            GP's mean at q under ITS parameters and basis (empty basis: the mean colour); 0 without rgb.  leaf[i] = L,
+ *            range[i] = t, local[3 i ..] = (f, q1, q2).
+ *   miss     x = y = z = NaN (PCL's organised-cloud convention), w = 1, a = 255, colours 0, leaf = -1, range = NaN, local = NaN.
+ *   counts   host int32[5] or NULL: rays; hits; rays that never met the grid (invalid directions included); surface tests run;
+ *            tests with finite t, q, f, g and |g| > eps_rel res.
+ * Deviations: only the leaves of the voxels a ray visits are tested (as train_classification does): the sliver of a patch that
+ * protrudes into a neighbouring voxel that is no trained leaf is not seen.  The predictive sigma at the hit is not computed: leaf and
+ * local let a caller bucket the hits by leaf and call gpc_sparse_predict_points_dev.
+ * The same inputs give the same bits: integer atomics (the counters) only.  gpc_patches_render takes HOST dirs / cells / outputs and
+ * is synchronous; gpc_patches_render_dev takes DEVICE dirs, cells and per-ray outputs (leaf, range, local may each be NULL), enqueues
+ * on the context's stream and synchronises only when counts != NULL.  n == 0: GPC_OK.  GPC_EINVAL: a NULL or destroyed object, objects
+ * of different contexts, depth with another P or ny != 1, rgb with another P or ny != 3, a non-finite origin, newton_iters < 0,
+ * n < 0, NULL dirs or cloud with n > 0.  GPC_ERANGE: newton_iters > 64. */
+typedef struct gpc_render_params {
+    int32_t newton_iters;   /* 4 */
+    int32_t use_w;          /* 1: a cell the producer's mask W never saw a point in does not stop a ray */
+    double eps_rel;         /* 1e-6: accept |g| <= eps_rel * res */
+    double t_max;           /* +inf */
+} gpc_render_params;
+void gpc_default_params_render(gpc_render_params* p);
+int gpc_patches_render(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* depth, const gpc_sparse* rgb, const uint8_t* cells,
+                       const gpc_render_params* params, const double origin[3], const double* dirs, int n, gpc_point_xyzrgb* cloud,
+                       int32_t* leaf, double* range, double* local, int32_t* counts);
+int gpc_patches_render_dev(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* depth, const gpc_sparse* rgb, const uint8_t* cells,
+                           const gpc_render_params* params, const double origin[3], const double* dirs, int n,
+                           gpc_point_xyzrgb* cloud, int32_t* leaf, double* range, double* local, int32_t* counts);
+/* Pinhole rays for gpc_patches_render_dev: pixel i = v width + u gets dir = R ((u - cx) / fx, (v - cy) / fy, 1), R host, column-major
+ * (the camera's axes in the world).  Not normalised, so `range` is the depth along the optical axis, as a depth camera reports it.
+ * dirs_dev: DEVICE, width * height x 3.  Enqueued on the context's stream.  GPC_EINVAL: negative sizes, fx or fy zero or not finite,
+ * a non-finite R, cx or cy; GPC_ERANGE: more than 2^31 - 1 pixels. */
+int gpc_camera_rays_dev(gpc_ctx* ctx, const double R[9], double fx, double fy, double cx, double cy, int width, int height,
+                        double* dirs_dev);
+
 /* ---- scan-to-model registration (SURVEY section 8, row f): gp_registration on the GPU ------------------------------------ */
 /* gp_registration (src/gp_registration.h, src/gp_registration.cpp) aligns a scan to a trained model by gradient ascent on the
  * mean likelihood of the scan's points under the per-leaf depth and colour GPs.  One step (registration_step, :73-92) is
