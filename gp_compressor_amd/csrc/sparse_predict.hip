@@ -39,6 +39,9 @@ typedef double sp_d4 __attribute__((ext_vector_type(4)));
 #define SP_RT 4   // row tiles per wave (4 waves x 4 x 16 rows = 256 = GPC_MAX_BV)
 __device__ static inline void sp_ck_chunk(const double* __restrict__ Cg, int ld, int b, const double* Kc, double* Vc)
 {
+    // (workgroup-uniform, and no barrier below.)  An empty basis has no product and no row to clamp an address to: min(i, b - 1) = -1
+    // sent the unconditional prefetch to Cg[-1 - ld], in front of the patch's matrix and, for patch 0, in front of the allocation.
+    if (b <= 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
     const int nrt = (b + 15) >> 4;

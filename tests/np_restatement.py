@@ -204,14 +204,24 @@ def grid(res, sz):
     return X0, X1
 
 
-def train_sigmaf_np(p0, p1, s20, alpha, Cm, BV, q0, q1, y, step, max_counter):
-    """the live part of train_parameters (src/sparse_gp.hpp:586-640), NumPy, on a given state"""
-    if len(BV) < 20:
+def train_sigmaf_np(p0, p1, s20, alpha, Cm, BV, q0, q1, y, step, max_counter, dtype=None, raw=False):
+    """the live part of train_parameters (src/sparse_gp.hpp:586-640), NumPy, on a given state.
+    dtype: evaluate in that type (np.longdouble) instead of float64.  raw=True: only the three per-point sums the loop is made of, at
+    sigma_f^2 = 1 -- e^T C e, alpha^T e, sum_j |x - BV_j|^2 e_j alpha_j, each (n,) -- whatever the size of the basis."""
+    half, pi, ft = np.float64(np.float32(-0.5)), np.pi, np.float64
+    if dtype is not None:
+        ft = dtype
+        p0, p1, s20, step, half = dtype(p0), dtype(p1), dtype(s20), dtype(step), dtype(np.float32(-0.5))
+        alpha, Cm, BV, q0, q1, y = (np.asarray(a, dtype=dtype) for a in (alpha, Cm, BV, q0, q1, y))
+        pi = 4 * np.arctan(dtype(1))
+    if len(BV) < 20 and not raw:
         return p0, 0, np.zeros(max_counter + 2), np.zeros(2)
     d2 = (q0[:, None] - BV[None, :, 0]) ** 2 + (q1[:, None] - BV[None, :, 1]) ** 2
-    e = np.exp(np.float64(np.float32(-0.5)) / p1 * d2)                      # n x b
-    ls = np.zeros(max_counter + 2)
-    c0 = 0.5 * np.log(2.0 * np.pi)
+    e = np.exp(half / p1 * d2)                                              # n x b
+    if raw:
+        return np.einsum("ij,jk,ik->i", e, Cm, e), e @ alpha, (d2 * e) @ alpha
+    ls = np.zeros(max_counter + 2, dtype=ft)
+    c0 = 0.5 * np.log(2.0 * pi)
     counter = 0
     while True:
         ak = (p0 * e) @ alpha

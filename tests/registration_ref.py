@@ -86,26 +86,44 @@ def bucket(owner, P):
     return order, off
 
 
-def closed_form_likelihood(p0, p1, s20, alpha, Cm, BV, q0, q1, yq):
+def likelihood_tail(ny, sigma, sdx, second, offs, sq, pi=np.pi):
+    """The per-point end of closed_form_likelihood, after the sums over the basis: sigma (..., m), sdx and second (..., m, 2),
+    offs (ny, m), sq (m,) -> dX (..., m, 3), l (..., m).  Leading axes broadcast (a stack of variants of the sums at once)."""
+    lik = 1.0 / np.sqrt((2 * pi) ** ny * sigma) * np.exp(-0.5 / sigma * sq)
+    exppart = 0.5 / sigma ** 1.5 * np.exp(-0.5 / sigma * sq)
+    d12 = exppart[..., None] * (-sdx + second + sdx / sigma[..., None] * sq[..., None])
+    d0 = -1.0 / sigma ** 1.5 * offs[0] * exppart if ny == 1 else np.zeros_like(sigma)
+    return np.concatenate([d0[..., None], d12], axis=-1), lik
+
+
+def closed_form_likelihood(p0, p1, s20, alpha, Cm, BV, q0, q1, yq, dtype=None, parts=False):
     """likelihood and likelihood_dx (src/sparse_gp.hpp:387-427, 463-508; field src/sparse_gp_field.hpp:322-392) on a given state:
-    alpha (ny, b), Cm (b, b), BV (b, 2), query q0, q1 (m,), yq (ny, m).  Returns dX (m, 3), l (m,)."""
+    alpha (ny, b), Cm (b, b), BV (b, 2), query q0, q1 (m,), yq (ny, m).  Returns dX (m, 3), l (m,).
+    dtype: evaluate in that type (np.longdouble for an extended-precision reference) instead of the arguments' own.
+    parts=True: a dict of the intermediate quantities as well -- A (b, m) the exponent's argument, K (b, m), mu (ny, m) the
+    predictive mean, CK (b, m), sigma (m,) = s20 + k* + k^T C k (not clamped), Kdx, sdx, second, offs, sq, dX, l."""
+    pi = np.pi
+    if dtype is not None:
+        p0, p1, s20 = dtype(p0), dtype(p1), dtype(s20)
+        alpha, Cm, BV, q0, q1, yq = (np.asarray(a, dtype=dtype) for a in (alpha, Cm, BV, q0, q1, yq))
+        pi = 4 * np.arctan(dtype(1))
     ny = alpha.shape[0]
     Xq = np.stack([q0, q1], 1)
     D = Xq[None, :, :] - BV[:, None, :]
-    K = p0 * np.exp(-0.5 / p1 * np.sum(D * D, axis=2))
+    A = -0.5 / p1 * np.sum(D * D, axis=2)
+    K = p0 * np.exp(A)
     mu = alpha @ K
     CK = Cm @ K
     sigma = s20 + p0 + np.sum(K * CK, axis=0)
     offs = yq - mu
     sq = np.sum(offs * offs, axis=0)
-    lik = 1.0 / np.sqrt((2 * np.pi) ** ny * sigma) * np.exp(-0.5 / sigma * sq)
     Kdx = -(1.0 / p1) * D * K[:, :, None]
     sdx = 2.0 * np.einsum("imd,im->md", Kdx, CK)
-    exppart = 0.5 / sigma ** 1.5 * np.exp(-0.5 / sigma * sq)
     second = 2.0 * np.einsum("imd,ci,cm->md", Kdx, alpha, offs)
-    d12 = exppart[:, None] * (-sdx + second + sdx / sigma[:, None] * sq[:, None])
-    d0 = -1.0 / sigma ** 1.5 * offs[0] * exppart if ny == 1 else np.zeros_like(sigma)
-    return np.concatenate([d0[:, None], d12], axis=1), lik
+    dX, lik = likelihood_tail(ny, sigma, sdx, second, offs, sq, pi)
+    if parts:
+        return dict(A=A, K=K, mu=mu, CK=CK, sigma=sigma, Kdx=Kdx, sdx=sdx, second=second, offs=offs, sq=sq, dX=dX, l=lik)
+    return dX, lik
 
 
 def reduce_step(scan_rgb, owner, local, batch, lik_depth, lik_rgb):
