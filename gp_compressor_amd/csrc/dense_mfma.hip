@@ -906,7 +906,11 @@ int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in
     if (v_star) {
         if (a.sel) return gpc_fail(ctx, GPC_EINVAL, "variance + size-class dispatch is not supported");
         fbytes = sizeof(double) * (size_t)a.P * (nt_max * (nt_max + 1) / 2) * MF_IMG;
-        const int rc = gpc_ws_reserve(ctx, site, fbytes + sizeof(double) * (size_t)a.n_total * a.ny);
+        // dense_variance_kernel fetches the factor in whole chunks of eight images: 10, 36 and 78 images per patch (NT = 4, 8, 12) end
+        // inside a chunk, and the last patch's last fetch reaches up to six images past the export -- one chunk of slack behind alpha
+        // keeps that read inside the workspace however few weights follow it
+        const size_t chunk_slack = sizeof(double) * 8 * MF_IMG;
+        const int rc = gpc_ws_reserve(ctx, site, fbytes + sizeof(double) * (size_t)a.n_total * a.ny + chunk_slack);
         if (rc != GPC_OK) return rc;
         // the variance kernel evaluates K* anyway: it forms the mean from the same tiles, so the fit predicts nothing
         a.m = 0;

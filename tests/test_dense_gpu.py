@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from gp_compressor_amd import synth
+from variance_cases import _mixed_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -191,20 +192,6 @@ def test_dense_edge_cases(gp, oracle):
     fo, vo, so = oracle.dense_fit_predict_batch(oracle.dense_params(sigman_sq=0.0), off, x0, x1, y, xs0, xs1)
     assert st.tolist() == so.tolist() == [1, 0]
     assert np.all(np.isnan(f[0])) and np.all(np.isnan(al[0, :3])) and np.all(np.isfinite(f[1]))
-
-
-def _mixed_batch(sizes, seed, res=0.15):
-    """A batch with exactly the given point counts (zeros allowed), surfaces as synth.make_patches draws them."""
-    rng = np.random.default_rng(seed)
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    N = int(off[-1])
-    x0, x1 = rng.uniform(-res / 2, res / 2, N), rng.uniform(-res / 2, res / 2, N)
-    y = np.zeros((1, N))
-    for i, n in enumerate(sizes):
-        sl = slice(off[i], off[i + 1])
-        d = 0.01 * np.sin(rng.uniform(5, 30) * x0[sl] + rng.uniform(0, 6)) * np.cos(rng.uniform(5, 30) * x1[sl]) + rng.normal(0, 0.003, n)
-        y[0, sl] = d - (d.mean() if n else 0.0)
-    return off, x0, x1, y
 
 
 @pytest.mark.parametrize("want_var", [0, 1])
