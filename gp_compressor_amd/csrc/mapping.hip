@@ -20,18 +20,20 @@
 //
 // The grid keeps the model's anchor mn and resolution; its whole-voxel origin shift koff and its extent kmax grow to cover the scan
 // (producer_internal.h), so no old voxel centre moves.  Pipeline (integer / gather work, one stream, three reads of a few bytes):
-//   1 pc_bounds_kernel      the scan's corners -> koff, kmax, key widths;  mp_rekey_kernel: the model's keys in the grown grid
-//   2 pc_keys / radix sort / pc_heads / pc_leaves / pc_gather (producer_internal.h): the scan's own voxel table, points in sorted order
+//   1 pc_cloud_bounds       the scan's corners -> koff, kmax, key widths;  mp_rekey_kernel: the model's keys in the grown grid
+//   2 pc_voxel_table_build, pc_voxel_table_leaves (the producer's stages, producer_internal.h): the scan's own voxel table, points in
+//                           sorted order
 //   3 mp_moment_kernel      one wave per scan voxel and per untrained old leaf: sphere count and moment matrix over the SCAN's points,
 //                           in the producer's hit order (pc_sphere_moments)
 //   4 mp_flag_kernel + scan which scan voxels become leaves;  mp_merge_kernel: merge of the two sorted key lists by rank (binary search)
 //   5 mp_frame_kernel       a thread per merged leaf: class, frame (copied or pc_frame_of_moments), window origin
-//   6 mp_claim_kernel       a thread per scan point: candidates in ascending leaf order, sphere test against the voxel centre, window in
-//                           the candidate's frame around its origin; the first that accepts owns the point
+//   6 mp_claim_kernel       a thread per scan point: pc_first_accepting_leaf, the walk of the registration assignment, over the
+//                           merged table, idle leaves skipped, window around the leaf's origin
 //   7 bucket                stable radix sort of (owner, scan index): patch order, ascending scan index inside a patch; offsets by
-//                           binary search in the sorted owners (no atomics)
+//                           binary search in the sorted owners (pc_bucket_offsets; no atomics)
 //   8 mp_means_kernel       one wave per leaf: depth sum in patch order (a serial chain, like the producer's), colour sums, the leaf's
-//                           mean / rgb_mean, the mask it starts from;  mp_emit_kernel: a thread per owned point: the batch rows, W
+//                           mean / rgb_mean, the mask it starts from;  mp_emit_kernel: a thread per owned point: the batch rows, W;
+//                           pc_nmax and pc_patches_publish: the size classes, the view, the new object
 // No floating-point atomics, no order left to the scheduler: the same inputs give the same bits.  Contraction is off (producer_internal.h)
 // and every expression shared with the producer or the registration assignment is written in their association.
 #include <algorithm>
@@ -122,16 +124,6 @@ __global__ __launch_bounds__(PC_THREADS) void mp_moment_kernel(MpArgs A, const u
 }
 
 // ---- 4: which scan voxels become leaves; the merge ---------------------------------------------------------------------------------
-__device__ static inline int mp_lower_bound(const uint64_t* a, int n, uint64_t key)
-{
-    int lo = 0, hi = n;                                       // first element >= key
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(PC_THREADS) void mp_flag_kernel(MpArgs A)
 {
     const int u = blockIdx.x * PC_THREADS + threadIdx.x;
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(PC_THREADS) void mp_merge_kernel(MpArgs A)
     const int t = blockIdx.x * PC_THREADS + threadIdx.x;
     if (t < A.P0) {
         const uint64_t key = A.okey[t];
-        const int pos = t + A.arank[mp_lower_bound(A.ukey, A.U, key)];
+        const int pos = t + A.arank[pc_lower_bound(A.ukey, A.U, key)];
         A.mkey[pos] = key;
         A.from[pos] = t;
         A.o2n[t] = pos;
@@ -155,7 +147,7 @@ __global__ __launch_bounds__(PC_THREADS) void mp_merge_kernel(MpArgs A)
         const int u = t - A.P0;
         if (!A.add[u]) return;
         const uint64_t key = A.ukey[u];
-        const int pos = A.arank[u] + mp_lower_bound(A.okey, A.P0, key);
+        const int pos = A.arank[u] + pc_lower_bound(A.okey, A.P0, key);
         A.mkey[pos] = key;
         A.from[pos] = -1 - u;
     }
@@ -206,40 +198,13 @@ __global__ __launch_bounds__(PC_THREADS) void mp_claim_kernel(MpArgs A)
 {
     const int i = blockIdx.x * PC_THREADS + threadIdx.x;
     if (i >= A.n) return;
-    const PcGrid& g = A.g;
     const float4 f = *reinterpret_cast<const float4*>(&A.cloud[i]);
     const double p[3] = {(double)f.x, (double)f.y, (double)f.z};
     int k[3];
-    pc_voxel(g, f.x, f.y, f.z, k);                            // inside the grid: it was grown over the scan
-    const double r2 = g.radius * g.radius;
-    int owner = -1;
+    pc_voxel(A.g, f.x, f.y, f.z, k);                          // inside the grid: it was grown over the scan
     double q[3] = {0.0, 0.0, 0.0};
-    const int xlo = max(k[0] - 1, 0), xhi = min(k[0] + 1, g.kmax[0]);
-    for (int j = 0; j < 9 && owner < 0; ++j) {                // rows (dz, dy) in ascending key order
-        const int nz = k[2] + j / 3 - 1, ny = k[1] + j % 3 - 1;
-        if (nz < 0 || nz > g.kmax[2] || ny < 0 || ny > g.kmax[1]) continue;
-        const uint64_t key_lo = pc_pack(g, xlo, ny, nz), key_hi = pc_pack(g, xhi, ny, nz);
-        for (int L = mp_lower_bound(A.mkey, A.P, key_lo); L < A.P && owner < 0; ++L) {        // the row's leaves are consecutive
-            const uint64_t key = A.mkey[L];
-            if (key > key_hi) break;
-            if (A.cls[L] == MP_IDLE) continue;
-            int c3[3];
-            pc_unpack(g, key, c3);
-            double cen[3];
-            pc_center(g, c3, cen);
-            const double d[3] = {p[0] - cen[0], p[1] - cen[1], p[2] - cen[2]};
-            if (!(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= r2)) continue;                    // radiusSearch (:96)
-            const double* R = A.R + (size_t)L * 9;
-            const double* o = A.org + (size_t)L * 3;
-            const double e[3] = {p[0] - o[0], p[1] - o[1], p[2] - o[2]};
-            double t[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) t[a] = R[3 * a] * e[0] + R[3 * a + 1] * e[1] + R[3 * a + 2] * e[2];       // R^T (p - origin)
-            if (t[1] > g.half || t[1] < -g.half || t[2] > g.half || t[2] < -g.half) continue;
-            owner = L;
-            q[0] = t[0]; q[1] = t[1]; q[2] = t[2];
-        }
-    }
+    const int32_t* cls = A.cls;
+    const int owner = pc_first_accepting_leaf(A.g, A.mkey, A.P, p, k, A.R, A.org, [cls](int L) { return cls[L] == MP_IDLE; }, q);
     A.local[(size_t)i * 3] = q[0];
     A.local[(size_t)i * 3 + 1] = q[1];
     A.local[(size_t)i * 3 + 2] = q[2];
@@ -247,49 +212,7 @@ __global__ __launch_bounds__(PC_THREADS) void mp_claim_kernel(MpArgs A)
     A.bval[i] = i;
 }
 
-// ---- 7: offsets of the buckets -----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PC_THREADS) void mp_offsets_kernel(MpArgs A)
-{
-    const int j = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (j > A.P) return;
-    int lo = 0, hi = A.n;                                     // first sorted position with key >= j
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (A.skey[mid] < (uint32_t)j) lo = mid + 1; else hi = mid;
-    }
-    A.off[j] = lo;
-}
-
-// nmax[0] = largest patch; nmax[1], nmax[2] = patches of <= 256 / <= 272 points (the size classes of the dense dispatch, as the producer
-// counts them)
-__global__ __launch_bounds__(PC_THREADS) void mp_nmax_kernel(const int32_t* off, int P, int32_t* nmax)
-{
-    int m = 0, c0 = 0, c1 = 0;
-    for (int i = blockIdx.x * PC_THREADS + threadIdx.x; i < P; i += gridDim.x * PC_THREADS) {
-        const int n = off[i + 1] - off[i];
-        m = max(m, n);
-        c0 += n <= 256;
-        c1 += n <= 272;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        m = max(m, __shfl_xor(m, o));
-        c0 += __shfl_xor(c0, o);
-        c1 += __shfl_xor(c1, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMax(nmax, m);
-        atomicAdd(nmax + 1, c0);
-        atomicAdd(nmax + 2, c1);
-    }
-}
-
 // ---- 8: means, masks, the batch ----------------------------------------------------------------------------------------------------
-__device__ static inline uint32_t mp_rgb_of(const gpc_point_xyzrgb* q)    // r | g << 8 | b << 16
-{
-    const uint32_t c = *reinterpret_cast<const uint32_t*>(&q->b);         // b | g << 8 | r << 16 | a << 24
-    return ((c >> 16) & 0xffu) | (c & 0xff00u) | ((c & 0xffu) << 16);
-}
-
 __global__ __launch_bounds__(PC_THREADS) void mp_means_kernel(MpArgs A)
 {
     const int lane = threadIdx.x & 63;
@@ -310,7 +233,7 @@ __global__ __launch_bounds__(PC_THREADS) void mp_means_kernel(MpArgs A)
             if (s < s1) {
                 const int i = A.sval[s];
                 d = A.local[(size_t)i * 3];
-                const uint32_t c = mp_rgb_of(&A.cloud[i]);
+                const uint32_t c = pc_rgb_of(&A.cloud[i]);
                 cs[0] += (int)(c & 0xffu); cs[1] += (int)((c >> 8) & 0xffu); cs[2] += (int)((c >> 16) & 0xffu);
             }
             const int here = min(64, s1 - b0);
@@ -358,26 +281,22 @@ __global__ __launch_bounds__(PC_THREADS) void mp_emit_kernel(MpArgs A)
     A.x0[s] = u;
     A.x1[s] = w;
     A.src[s] = i;
-    const uint32_t c = mp_rgb_of(&A.cloud[i]);
+    const uint32_t c = pc_rgb_of(&A.cloud[i]);
     const double* cm = A.rgb_mean + (size_t)L * 3;            // the leaf's own mean (fresh) | the stored one (kept, :237)
     A.rgb[s] = (double)(c & 0xffu) - cm[0];
     A.rgb[total + s] = (double)((c >> 8) & 0xffu) - cm[1];
     A.rgb[2 * total + s] = (double)((c >> 16) & 0xffu) - cm[2];
-    int gx = (int)((double)g.sz * (u / g.res + 0.5)), gy = (int)((double)g.sz * (w / g.res + 0.5));
-    gx = min(max(gx, 0), g.sz - 1);
-    gy = min(max(gy, 0), g.sz - 1);
-    A.W[(size_t)L * (size_t)(g.sz * g.sz) + (size_t)(g.sz * gx + gy)] = 1;
+    A.W[(size_t)L * (size_t)(g.sz * g.sz) + (size_t)pc_mask_cell(g, u, w)] = 1;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
 struct MpScratch {
-    uint32_t* bounds;
-    uint64_t *k0, *k1, *okey, *ukey;
-    int32_t *v0, *vals, *head, *leaf_of, *ustart, *ku, *ko, *add, *arank, *o2n, *from, *cls, *bval, *sval, *nmax;
+    PcVoxelTable T;
+    uint64_t *okey, *ukey;
+    int32_t *ustart, *ku, *ko, *add, *arank, *o2n, *from, *cls, *bval, *sval, *nmax;
     uint32_t *bkey, *skey;
-    PcPoint* sp;
     double *Mu, *Mo, *org, *shift, *local;
     void* prim;
 };
@@ -385,11 +304,7 @@ struct MpScratch {
 // pl: bound on the number of merged leaves
 size_t mp_carve(PcCarver& c, MpScratch& s, size_t n, size_t p0, size_t pl, size_t prim_bytes)
 {
-    s.bounds = c.take<uint32_t>(8);
-    s.k0 = c.take<uint64_t>(n); s.k1 = c.take<uint64_t>(n);
-    s.v0 = c.take<int32_t>(n); s.vals = c.take<int32_t>(n);
-    s.head = c.take<int32_t>(n); s.leaf_of = c.take<int32_t>(n);
-    s.sp = c.take<PcPoint>(n);
+    s.T.carve(c, n);
     s.ukey = c.take<uint64_t>(n); s.ustart = c.take<int32_t>(n + 1);
     s.Mu = c.take<double>(16 * n); s.ku = c.take<int32_t>(n);
     s.add = c.take<int32_t>(n + 1); s.arank = c.take<int32_t>(n + 1);
@@ -404,20 +319,7 @@ size_t mp_carve(PcCarver& c, MpScratch& s, size_t n, size_t p0, size_t pl, size_
 
 }  // namespace
 
-#define MP_HIP(call)                                                                                           \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) {                                                                                \
-            pc_patches_release(o);                                                                             \
-            return gpc_fail(ctx, e_ == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_patches_insert_cloud: %s failed: %s", \
-                            #call, hipGetErrorString(e_));                                                     \
-        }                                                                                                      \
-    } while (0)
-#define MP_FAIL(...)                    \
-    do {                                \
-        pc_patches_release(o);          \
-        return gpc_fail(ctx, __VA_ARGS__); \
-    } while (0)
+#define MP_HIP(call) PC_HIP_IN("gpc_patches_insert_cloud", call)
 
 extern "C" {
 
@@ -455,50 +357,35 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
     // 1: the scan's corners; the grid grows over them by whole voxels
     PcGrid g = g0;
     if (n > 0) {
-        {
-            const int rc = gpc_ws_reserve(ctx, 4096);
-            if (rc != GPC_OK) { pc_patches_release(o); return rc; }
-        }
-        uint32_t* d_bounds = static_cast<uint32_t*>(ctx->ws);
-        const uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0, 0, 0};
-        MP_HIP(hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(pc_bounds_kernel, dim3(nblk < ctx->num_cus * 4 ? nblk : ctx->num_cus * 4), dim3(PC_THREADS), 0, st, cloud, n, d_bounds);
-        MP_HIP(hipGetLastError());
         uint32_t hb[8];
-        MP_HIP(hipMemcpyAsync(hb, d_bounds, sizeof(hb), hipMemcpyDeviceToHost, st));
-        MP_HIP(hipStreamSynchronize(st));
-        if (hb[6]) MP_FAIL(GPC_EINVAL, "the cloud holds a non-finite coordinate");
+        if (int rc = pc_cloud_bounds(ctx, "gpc_patches_insert_cloud", cloud, n, hb)) { pc_patches_release(o); return rc; }
         for (int a = 0; a < 3; ++a) {
             // unshifted voxel coordinates of the scan's corners (floor((x - mn) / res) is monotone in x: the corners bound every point's)
             const double lo = std::floor(((double)pc_unordered(hb[a]) - g0.mn[a]) / g0.res);
             const double hi = std::floor(((double)pc_unordered(hb[3 + a]) - g0.mn[a]) / g0.res);
             const double koff = std::max((double)g0.koff[a], -lo);
             const double kmax = std::max((double)(g0.kmax[a] - g0.koff[a]), hi) + koff;
-            if (!(kmax < 2097152.0)) MP_FAIL(GPC_ERANGE, "more than 2^21 voxels of side res along an axis");
+            if (!(kmax < 2097152.0)) PC_FAIL(GPC_ERANGE, "more than 2^21 voxels of side res along an axis");
             g.koff[a] = (int)koff;
             g.kmax[a] = (int)kmax;
         }
         g.bx = pc_bits_for(g.kmax[0]); g.by = pc_bits_for(g.kmax[1]); g.bz = pc_bits_for(g.kmax[2]);
     }
-    const int key_bits = g.bx + g.by + g.bz;           // <= 63
 
     // scratch
-    size_t sort_bytes = 0, scan_bytes = 0, scan2_bytes = 0, sort2_bytes = 0;
+    size_t table_bytes = 0, scan2_bytes = 0, sort2_bytes = 0;
     const size_t Pbound = P0z + N;
     if (n > 0) {
-        MP_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, N,
-                                         0u, (unsigned)key_bits, st));
-        MP_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, N, rocprim::plus<int32_t>(), st));
+        MP_HIP(pc_voxel_table_prim_bytes(ctx, g, N, &table_bytes));
         MP_HIP(rocprim::exclusive_scan(nullptr, scan2_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t)0, N + 1, rocprim::plus<int32_t>(), st));
         MP_HIP(rocprim::radix_sort_pairs(nullptr, sort2_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, N,
                                          0u, (unsigned)pc_bits_for((int)std::min<size_t>(Pbound, 0x7fffffff)), st));
     }
-    const size_t prim_bytes = std::max(std::max(sort_bytes, sort2_bytes), std::max(scan_bytes, scan2_bytes));
+    const size_t prim_bytes = std::max(table_bytes, std::max(sort2_bytes, scan2_bytes));
     MpScratch S;
     {
         PcCarver measure(nullptr);
-        const int rc = gpc_ws_reserve(ctx, mp_carve(measure, S, N, P0z, Pbound, prim_bytes));
-        if (rc != GPC_OK) { pc_patches_release(o); return rc; }
+        if (int rc = gpc_ws_reserve(ctx, mp_carve(measure, S, N, P0z, Pbound, prim_bytes))) { pc_patches_release(o); return rc; }
         PcCarver c(ctx->ws);
         mp_carve(c, S, N, P0z, Pbound, prim_bytes);
     }
@@ -508,7 +395,7 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
     A.cloud = cloud;
     A.key0 = model->leaf_key; A.bv = depth ? depth->b : nullptr;
     A.R0 = model->v.rotations; A.mean0 = model->v.means; A.rgbm0 = model->v.rgb_means; A.W0 = model->v.W;
-    A.okey = S.okey; A.ukey = S.ukey; A.ustart = S.ustart; A.sp = S.sp;
+    A.okey = S.okey; A.ukey = S.ukey; A.ustart = S.ustart; A.sp = S.T.sp;
     A.Mu = S.Mu; A.Mo = S.Mo; A.ku = S.ku; A.ko = S.ko; A.add = S.add; A.arank = S.arank; A.o2n = S.o2n; A.from = S.from; A.cls = S.cls;
     A.org = S.org; A.shift = S.shift; A.local = S.local;
     A.bkey = S.bkey; A.skey = S.skey; A.bval = S.bval; A.sval = S.sval; A.nmax = S.nmax;
@@ -519,21 +406,9 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
     int32_t U = 0;
     size_t tb;
     if (n > 0) {
-        hipLaunchKernelGGL(pc_keys_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, g, cloud, n, S.k0, S.v0);
-        MP_HIP(hipGetLastError());
-        tb = prim_bytes;
-        MP_HIP(rocprim::radix_sort_pairs(S.prim, tb, S.k0, S.k1, S.v0, S.vals, N, 0u, (unsigned)key_bits, st));
-        hipLaunchKernelGGL(pc_heads_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, S.k1, n, S.head);
-        MP_HIP(hipGetLastError());
-        tb = prim_bytes;
-        MP_HIP(rocprim::inclusive_scan(S.prim, tb, S.head, S.leaf_of, N, rocprim::plus<int32_t>(), st));
-        MP_HIP(hipMemcpyAsync(&U, S.leaf_of + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(pc_gather_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, cloud, S.vals, n, S.sp);
-        MP_HIP(hipGetLastError());
-        MP_HIP(hipStreamSynchronize(st));
-        if (U < 1 || U > n) MP_FAIL(GPC_EHIP, "internal: %d scan voxels of %d points", (int)U, n);
-        hipLaunchKernelGGL(pc_leaves_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, S.k1, n, (int)U, S.leaf_of, S.ukey, S.ustart);
-        MP_HIP(hipGetLastError());
+        MP_HIP(pc_voxel_table_build(ctx, g, cloud, n, S.T, S.prim, prim_bytes, &U));
+        if (U < 1 || U > n) PC_FAIL(GPC_EHIP, "internal: %d scan voxels of %d points", (int)U, n);
+        MP_HIP(pc_voxel_table_leaves(ctx, n, S.T, U, S.ukey, S.ustart));
     }
     A.U = U;
 
@@ -557,30 +432,15 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
         MP_HIP(hipMemsetAsync(S.arank, 0, sizeof(int32_t), st));
     }
     MP_HIP(hipStreamSynchronize(st));
-    if (nadd < 0 || nadd > U) MP_FAIL(GPC_EHIP, "internal: %d new leaves of %d scan voxels", (int)nadd, (int)U);
+    if (nadd < 0 || nadd > U) PC_FAIL(GPC_EHIP, "internal: %d new leaves of %d scan voxels", (int)nadd, (int)U);
     const long long Pll = (long long)P0 + (long long)nadd;
-    if (Pll * (long long)m > 0x7fffffffLL) MP_FAIL(GPC_ERANGE, "P * sz * sz exceeds 2^31-1");
+    if (Pll * (long long)m > 0x7fffffffLL) PC_FAIL(GPC_ERANGE, "P * sz * sz exceeds 2^31-1");
     const int P = (int)Pll;
     const size_t Pz = (size_t)P;
     A.P = P;
 
-    // the result: one block, laid out as the producer's; per-point arrays are sized by n (an upper bound of the points owned)
-    PcCarver oc(nullptr);
-    for (int pass = 0; pass < 2; ++pass) {
-        oc = PcCarver(pass ? o->block : nullptr);
-        o->v.off = oc.take<int32_t>(Pz + 1);
-        o->v.rotations = oc.take<double>(9 * Pz);
-        o->v.means = oc.take<double>(3 * Pz);
-        o->v.rgb_means = oc.take<double>(3 * Pz);
-        o->v.W = oc.take<uint8_t>(Pz * m);
-        o->v.x0 = oc.take<double>(N);
-        o->v.x1 = oc.take<double>(N);
-        o->v.y = oc.take<double>(N);
-        o->v.rgb = oc.take<double>(3 * N);
-        o->v.src = oc.take<int32_t>(N);
-        o->leaf_key = oc.take<uint64_t>(Pz);
-        if (!pass) MP_HIP(hipMalloc(&o->block, oc.used));
-    }
+    // the result: one block, laid out as the producer's
+    MP_HIP(pc_patches_alloc(o, Pz, N, m));
     o->grid = g;
     A.mkey = const_cast<uint64_t*>(o->leaf_key);
     A.off = const_cast<int32_t*>(o->v.off); A.R = const_cast<double*>(o->v.rotations); A.mean = const_cast<double*>(o->v.means);
@@ -598,8 +458,7 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
         MP_HIP(hipGetLastError());
         tb = prim_bytes;
         MP_HIP(rocprim::radix_sort_pairs(S.prim, tb, S.bkey, S.skey, S.bval, S.sval, N, 0u, (unsigned)pc_bits_for(P), st));
-        hipLaunchKernelGGL(mp_offsets_kernel, dim3((P + 1 + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, st, A);
-        MP_HIP(hipGetLastError());
+        MP_HIP(pc_bucket_offsets(st, S.skey, n, P, A.off));
     } else {
         MP_HIP(hipMemsetAsync(A.off, 0, sizeof(int32_t) * (Pz + 1), st));
     }
@@ -612,16 +471,8 @@ int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const g
         MP_HIP(hipGetLastError());
     }
     MP_HIP(hipMemsetAsync(S.nmax, 0, 4 * sizeof(int32_t), st));
-    hipLaunchKernelGGL(mp_nmax_kernel, dim3(64), dim3(PC_THREADS), 0, st, (const int32_t*)A.off, P, S.nmax);
-    MP_HIP(hipGetLastError());
-    int32_t total = 0, nmax[3] = {0, 0, 0};
-    MP_HIP(hipMemcpyAsync(&total, A.off + P, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MP_HIP(hipMemcpyAsync(nmax, S.nmax, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MP_HIP(hipStreamSynchronize(st));
-    o->v.P = P; o->v.n_total = total; o->v.n_max = nmax[0];
-    // the size classes of this batch, for the dense dispatch (as gpc_project_cloud leaves them)
-    ctx->hint_off = o->v.off; ctx->hint_P = P; ctx->hint_le256 = nmax[1]; ctx->hint_le272 = nmax[2];
-    o->serial = gpc_child_register(ctx, o);
+    MP_HIP(pc_nmax(st, A.off, P, S.nmax));
+    MP_HIP(pc_patches_publish(ctx, o, P, S.nmax));
     *out = o;
     return GPC_OK;
 }
@@ -635,21 +486,10 @@ int gpc_patches_insert_cloud(gpc_ctx* ctx, const gpc_patches* model, const gpc_s
     if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "negative point count");
     if (n > 0 && !cloud) return gpc_fail(ctx, GPC_EINVAL, "cloud is NULL");
     GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void* d_cloud = nullptr;
-    if (n > 0) {
-        GPC_HIP(ctx, hipMalloc(&d_cloud, sizeof(gpc_point_xyzrgb) * (size_t)n));
-        hipError_t e = hipMemcpyAsync(d_cloud, cloud, sizeof(gpc_point_xyzrgb) * (size_t)n, hipMemcpyHostToDevice, gpc_stream_of(ctx));
-        if (e != hipSuccess) {
-            (void)hipFree(d_cloud);
-            return gpc_fail(ctx, GPC_EHIP, "gpc_patches_insert_cloud: upload failed: %s", hipGetErrorString(e));
-        }
-    }
-    const int rc = gpc_patches_insert_cloud_dev(ctx, model, depth, (const gpc_point_xyzrgb*)d_cloud, n, min_nbr, out, old_to_new);
-    if (d_cloud) {
-        (void)hipStreamSynchronize(gpc_stream_of(ctx));
-        (void)hipFree(d_cloud);
-    }
-    return rc;
+    GpcStaging st(ctx, "gpc_patches_insert_cloud");
+    const gpc_point_xyzrgb* d_cloud = st.up(cloud, (size_t)n);
+    if (st.ok()) st.rc = gpc_patches_insert_cloud_dev(ctx, model, depth, d_cloud, n, min_nbr, out, old_to_new);
+    return st.finish();
 }
 
 }  // extern "C"

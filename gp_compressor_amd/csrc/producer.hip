@@ -24,6 +24,9 @@
 //                         mean as the oracle's sequential sum, colour means, mean removal, centre shift, mask W
 // Scratch lives in the context's grow-only workspace and the result in one allocation: a call costs three small
 // device->host reads (bounds, leaf count, totals) and no allocation in steady state beyond the result's.
+// Stages 1-3, the layout of the result and the tail that publishes it are host functions of their own (pc_cloud_bounds,
+// pc_voxel_table_*, pc_patches_alloc, pc_patches_publish: producer_internal.h), which gpc_patches_insert_cloud (mapping.hip) runs
+// too; so are the launchers of the bucket kernels every cutter uses (pc_bucket_offsets, pc_nmax).  Their kernels are defined here, once.
 // Bit-exactness: floating-point contraction is off for this file and every expression is written in the association of
 // oracle/gpc_oracle_producer.c; products of two floats are exact in double, so the moment sums only fix the ORDER.
 #include <algorithm>
@@ -35,10 +38,93 @@
 
 #include "producer_internal.h"   // (switches floating-point contraction off)
 
-// ---- 1: bounds -------------------------------------------------------------------------------------------------------
-// ---- 2: keys, leaf table -----------------------------------------------------------------------------------------------
-// (PcGrid and the key arithmetic: producer_internal.h)
+// ---- 1: bounds; 2: keys, leaf table (PcGrid and the key arithmetic: producer_internal.h) -------------------------------------
+// out[0..2] = ordered min, out[3..5] = ordered max, out[6] = 1 if a coordinate is not finite
+__global__ __launch_bounds__(PC_THREADS) void pc_bounds_kernel(const gpc_point_xyzrgb* cloud, int n, uint32_t* out)
+{
+    __shared__ uint32_t red[PC_WAVES][8];
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0, 0, 0};
+    int bad = 0;
+    for (int i = blockIdx.x * PC_THREADS + threadIdx.x; i < n; i += gridDim.x * PC_THREADS) {
+        const float4 p = *reinterpret_cast<const float4*>(&cloud[i]);
+        const float c[3] = {p.x, p.y, p.z};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            bad |= !(fabsf(c[a]) <= 3.4028234e38f);
+            const uint32_t o = pc_ordered(c[a]);
+            lo[a] = min(lo[a], o);
+            hi[a] = max(hi[a], o);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], o));
+            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], o));
+        }
+    }
+    bad = __any(bad);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[w][a] = lo[a]; red[w][3 + a] = hi[a]; }
+        red[w][6] = (uint32_t)bad;
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const int a = threadIdx.x;
+        uint32_t v = red[0][a];
+        for (int q = 1; q < PC_WAVES; ++q) v = a < 3 ? min(v, red[q][a]) : max(v, red[q][a]);   // [6]: 0 / 1, max == or
+        if (a < 3) atomicMin(&out[a], v); else if (a < 6) atomicMax(&out[a], v); else if (v) atomicOr(&out[6], 1u);
+    }
+}
+
+__global__ __launch_bounds__(PC_THREADS) void pc_keys_kernel(PcGrid g, const gpc_point_xyzrgb* cloud, int n, uint64_t* keys, int32_t* vals)
+{
+    const int i = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = *reinterpret_cast<const float4*>(&cloud[i]);
+    int k[3];
+    pc_voxel(g, p.x, p.y, p.z, k);
+    keys[i] = pc_pack(g, k[0], k[1], k[2]);
+    vals[i] = i;
+}
+
+__global__ __launch_bounds__(PC_THREADS) void pc_heads_kernel(const uint64_t* keys, int n, int32_t* head)
+{
+    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (s < n) head[s] = (s == 0 || keys[s] != keys[s - 1]) ? 1 : 0;
+}
+
+// leaf_of[s] holds the inclusive scan of head[] on entry (leaf id + 1) and the leaf id on exit
+__global__ __launch_bounds__(PC_THREADS) void pc_leaves_kernel(const uint64_t* keys, int n, int P, int32_t* leaf_of, uint64_t* leaf_key,
+                                                        int32_t* leaf_start)
+{
+    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (s >= n) return;
+    const int id = leaf_of[s] - 1;
+    leaf_of[s] = id;
+    if (s == 0 || keys[s] != keys[s - 1]) {
+        leaf_key[id] = keys[s];
+        leaf_start[id] = s;
+    }
+    if (s == n - 1) leaf_start[P] = n;
+}
+
 // ---- 3: sorted-order copy ------------------------------------------------------------------------------------------------
+// points re-laid in sorted order
+__global__ __launch_bounds__(PC_THREADS) void pc_gather_kernel(const gpc_point_xyzrgb* cloud, const int32_t* vals, int n, PcPoint* sp)
+{
+    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (s >= n) return;
+    const gpc_point_xyzrgb* q = &cloud[vals[s]];
+    const float4 p = *reinterpret_cast<const float4*>(q);
+    PcPoint o;
+    o.x = p.x; o.y = p.y; o.z = p.z;
+    o.rgb = pc_rgb_of(q);
+    *reinterpret_cast<float4*>(&sp[s]) = *reinterpret_cast<const float4*>(&o);
+}
+
 // ---- 4: frames -------------------------------------------------------------------------------------------------------------
 struct PcArgs {
     PcGrid g;
@@ -146,8 +232,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_claim_kernel(PcArgs A)
             const bool in = valid && owner < 0 && d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= r2;    // in L's search sphere
             if (!__any(in)) continue;
             double q[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) q[a] = fr[3 + 3 * a] * d[0] + fr[3 + 3 * a + 1] * d[1] + fr[3 + 3 * a + 2] * d[2];   // R^T d  (:84)
+            pc_to_frame(fr + 3, d, q);                        // R^T d  (:84)
             const bool acc = in && !(q[1] > g.half || q[1] < -g.half || q[2] > g.half || q[2] < -g.half);     // :85-87
             if (acc) { owner = L; pt[0] = q[0]; pt[1] = q[1]; pt[2] = q[2]; }
             const int c = __popcll(__ballot(acc));
@@ -162,13 +247,18 @@ __global__ __launch_bounds__(PC_THREADS) void pc_claim_kernel(PcArgs A)
     }
 }
 
-// nmax[0] = largest patch; nmax[1], nmax[2] = patches of <= 256 / <= 272 points: the size classes of the dense dispatch
-// (dense_api.hip), which the host reads together with n_max and hands to it so that the class launches are sized exactly
-__global__ __launch_bounds__(PC_THREADS) void pc_nmax_kernel(const int32_t* cnt, int P, int32_t* nmax)
+// ---- the bucket kernels of every cutter (pc_bucket_offsets, pc_nmax: producer_internal.h) -----------------------------------------
+__global__ __launch_bounds__(PC_THREADS) void pc_bucket_offsets_kernel(const uint32_t* skey, int n, int P, int32_t* off)
+{
+    const int j = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (j <= P) off[j] = pc_lower_bound(skey, n, (uint32_t)j);
+}
+
+__global__ __launch_bounds__(PC_THREADS) void pc_nmax_kernel(const int32_t* off, int P, int32_t* nmax)
 {
     int m = 0, c0 = 0, c1 = 0;
     for (int i = blockIdx.x * PC_THREADS + threadIdx.x; i < P; i += gridDim.x * PC_THREADS) {
-        const int n = cnt[i];
+        const int n = off[i + 1] - off[i];
         m = max(m, n);
         c0 += n <= 256;
         c1 += n <= 272;
@@ -260,10 +350,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_emit_kernel(PcArgs A)
                 A.rgb[q] = (double)(c & 0xffu) - cmean[0];
                 A.rgb[(size_t)total + q] = (double)((c >> 8) & 0xffu) - cmean[1];
                 A.rgb[2 * (size_t)total + q] = (double)((c >> 16) & 0xffu) - cmean[2];
-                int gx = (int)((double)g.sz * (u / g.res + 0.5)), gy = (int)((double)g.sz * (w / g.res + 0.5));   // :90-92
-                gx = min(max(gx, 0), g.sz - 1);
-                gy = min(max(gy, 0), g.sz - 1);
-                W[g.sz * gx + gy] = 1;
+                W[pc_mask_cell(g, u, w)] = 1;                 // :90-92
             }
             run += __popcll(mask);
         }
@@ -271,29 +358,133 @@ __global__ __launch_bounds__(PC_THREADS) void pc_emit_kernel(PcArgs A)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-// (struct gpc_patches: producer_internal.h)
+// (struct gpc_patches and the stages' contracts: producer_internal.h)
+int pc_cloud_bounds(gpc_ctx* ctx, const char* entry, const gpc_point_xyzrgb* cloud, int n, uint32_t hb[8])
+{
+    if (int rc = gpc_ws_reserve(ctx, 4096)) return rc;
+    hipStream_t st = ctx->stream;
+    uint32_t* d_bounds = static_cast<uint32_t*>(ctx->ws);
+    const uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0, 0, 0};
+    const int nblk = (n + PC_THREADS - 1) / PC_THREADS;
+    hipError_t e = hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pc_bounds_kernel, dim3(nblk < ctx->num_cus * 4 ? nblk : ctx->num_cus * 4), dim3(PC_THREADS), 0, st, cloud, n, d_bounds);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hb, d_bounds, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess)
+        return gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "%s: the bounds pass failed: %s", entry, hipGetErrorString(e));
+    if (hb[6]) return gpc_fail(ctx, GPC_EINVAL, "the cloud holds a non-finite coordinate");
+    return GPC_OK;
+}
+
+#define PC_RET(call)                      \
+    do {                                  \
+        hipError_t e_ = (call);           \
+        if (e_ != hipSuccess) return e_;  \
+    } while (0)
+
+hipError_t pc_voxel_table_prim_bytes(gpc_ctx* ctx, const PcGrid& g, size_t n, size_t* bytes)
+{
+    size_t sort_bytes = 0, scan_bytes = 0;
+    PC_RET(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, n, 0u,
+                                     (unsigned)(g.bx + g.by + g.bz), ctx->stream));
+    PC_RET(rocprim::inclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, n, rocprim::plus<int32_t>(), ctx->stream));
+    *bytes = std::max(sort_bytes, scan_bytes);
+    return hipSuccess;
+}
+
+hipError_t pc_voxel_table_build(gpc_ctx* ctx, const PcGrid& g, const gpc_point_xyzrgb* cloud, int n, const PcVoxelTable& T, void* prim,
+                                size_t prim_bytes, int32_t* count)
+{
+    hipStream_t st = ctx->stream;
+    const int nblk = (n + PC_THREADS - 1) / PC_THREADS;
+    const size_t N = (size_t)n;
+    // 2: keys, stable sort over exactly the key's bits (<= 63), heads, leaf id + 1 per sorted position
+    hipLaunchKernelGGL(pc_keys_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, g, cloud, n, T.k0, T.v0);
+    PC_RET(hipGetLastError());
+    size_t tb = prim_bytes;
+    PC_RET(rocprim::radix_sort_pairs(prim, tb, T.k0, T.keys, T.v0, T.vals, N, 0u, (unsigned)(g.bx + g.by + g.bz), st));
+    hipLaunchKernelGGL(pc_heads_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, T.keys, n, T.head);
+    PC_RET(hipGetLastError());
+    tb = prim_bytes;
+    PC_RET(rocprim::inclusive_scan(prim, tb, T.head, T.leaf_of, N, rocprim::plus<int32_t>(), st));
+    PC_RET(hipMemcpyAsync(count, T.leaf_of + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // 3: sorted-order copy (does not need the count: overlaps the read-back)
+    hipLaunchKernelGGL(pc_gather_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, cloud, T.vals, n, T.sp);
+    PC_RET(hipGetLastError());
+    return hipStreamSynchronize(st);
+}
+
+hipError_t pc_voxel_table_leaves(gpc_ctx* ctx, int n, const PcVoxelTable& T, int count, uint64_t* leaf_key, int32_t* leaf_start)
+{
+    hipLaunchKernelGGL(pc_leaves_kernel, dim3((n + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, ctx->stream, T.keys, n, count, T.leaf_of,
+                       leaf_key, leaf_start);
+    return hipGetLastError();
+}
+
+// per-point arrays are sized by N (an upper bound of the points owned)
+hipError_t pc_patches_alloc(gpc_patches* o, size_t P, size_t N, size_t m)
+{
+    for (int pass = 0; pass < 2; ++pass) {
+        PcCarver oc(pass ? o->block : nullptr);
+        o->v.off = oc.take<int32_t>(P + 1);
+        o->v.rotations = oc.take<double>(9 * P);
+        o->v.means = oc.take<double>(3 * P);
+        o->v.rgb_means = oc.take<double>(3 * P);
+        o->v.W = oc.take<uint8_t>(P * m);
+        o->v.x0 = oc.take<double>(N);
+        o->v.x1 = oc.take<double>(N);
+        o->v.y = oc.take<double>(N);
+        o->v.rgb = oc.take<double>(3 * N);
+        o->v.src = oc.take<int32_t>(N);
+        o->leaf_key = oc.take<uint64_t>(P);             // (last: the batch's own arrays keep their places)
+        if (!pass) PC_RET(hipMalloc(&o->block, oc.used));
+    }
+    return hipSuccess;
+}
+
+hipError_t pc_patches_publish(gpc_ctx* ctx, gpc_patches* o, int P, const int32_t* nmax_dev)
+{
+    hipStream_t st = ctx->stream;
+    int32_t total = 0, nmax[3] = {0, 0, 0};
+    PC_RET(hipMemcpyAsync(&total, o->v.off + P, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    PC_RET(hipMemcpyAsync(nmax, nmax_dev, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    PC_RET(hipStreamSynchronize(st));
+    o->v.P = P; o->v.n_total = total; o->v.n_max = nmax[0];
+    // the size classes of this batch, for the dense dispatch (keyed by the batch's own `off` buffer, which lives as long as the object)
+    ctx->hint_off = o->v.off; ctx->hint_P = P; ctx->hint_le256 = nmax[1]; ctx->hint_le272 = nmax[2];
+    o->serial = gpc_child_register(ctx, o);
+    return hipSuccess;
+}
+
+hipError_t pc_bucket_offsets(hipStream_t st, const uint32_t* skey, int n, int P, int32_t* off)
+{
+    hipLaunchKernelGGL(pc_bucket_offsets_kernel, dim3((P + 1 + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, st, skey, n, P, off);
+    return hipGetLastError();
+}
+
+hipError_t pc_nmax(hipStream_t st, const int32_t* off, int P, int32_t* nmax)
+{
+    hipLaunchKernelGGL(pc_nmax_kernel, dim3(64), dim3(PC_THREADS), 0, st, off, P, nmax);
+    return hipGetLastError();
+}
+
 namespace {
 
 struct Scratch {                // per call, in the context's workspace
-    uint32_t* bounds;
-    uint64_t *k0, *k1, *leaf_key;
-    int32_t *v0, *vals, *head, *leaf_of, *leaf_start, *nbr, *kcount, *owner, *cnt;
-    PcPoint* sp;
+    PcVoxelTable T;
+    int32_t *leaf_start, *nbr, *kcount, *owner, *cnt;
     double *py, *px0, *px1, *M, *cen;
     void* prim;
-    size_t prim_bytes;
 };
 
 size_t carve_scratch(PcCarver& c, Scratch& s, size_t n, size_t pb, size_t prim_bytes)
 {
-    s.bounds = c.take<uint32_t>(8);
-    s.k0 = c.take<uint64_t>(n); s.k1 = c.take<uint64_t>(n);
-    s.v0 = c.take<int32_t>(n); s.vals = c.take<int32_t>(n);
-    s.head = c.take<int32_t>(n); s.leaf_of = c.take<int32_t>(n);
+    s.T.carve(c, n);
     s.owner = c.take<int32_t>(n);
-    s.sp = c.take<PcPoint>(n);
     s.py = c.take<double>(n); s.px0 = c.take<double>(n); s.px1 = c.take<double>(n);
-    s.leaf_key = c.take<uint64_t>(pb);
     s.leaf_start = c.take<int32_t>(pb + 1);
     s.nbr = c.take<int32_t>(27 * pb);
     s.kcount = c.take<int32_t>(pb);
@@ -301,26 +492,17 @@ size_t carve_scratch(PcCarver& c, Scratch& s, size_t n, size_t pb, size_t prim_b
     s.M = c.take<double>(16 * pb);
     s.cen = c.take<double>(3 * pb);
     s.prim = c.take<char>(prim_bytes);
-    s.prim_bytes = prim_bytes;
     return c.used;
 }
 
 }  // namespace
 
-#define PC_HIP(call)                                                                                           \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) {                                                                                \
-            pc_patches_release(o);                                                                            \
-            return gpc_fail(ctx, e_ == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_project_cloud: %s failed: %s", \
-                            #call, hipGetErrorString(e_));                                                     \
-        }                                                                                                      \
-    } while (0)
+#define PC_HIP(call) PC_HIP_IN("gpc_project_cloud", call)
 
 extern "C" {
 
 // Safe in either order with gpc_ctx_destroy (the batch holds a reference on its context; hipFree synchronises the device).
-// the caller holds ctx->mu (or the object was never published): the error paths of gpc_project_cloud_dev end here
+// the caller holds ctx->mu (or the object was never published): the error paths of the cutters end here
 void pc_patches_release(gpc_patches* o)
 {
     if (!o) return;
@@ -372,26 +554,11 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
         *out = o;
         return GPC_OK;
     }
-    const int nblk = (n + PC_THREADS - 1) / PC_THREADS;
     const size_t N = (size_t)n;
 
-    // 1: bounds (its 32 bytes of scratch sit at the start of the workspace whatever the leaf bound turns out to be)
-    {
-        const int rc = gpc_ws_reserve(ctx, 4096);
-        if (rc != GPC_OK) { pc_patches_release(o); return rc; }
-    }
-    uint32_t* d_bounds = static_cast<uint32_t*>(ctx->ws);
-    const uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0, 0, 0};
-    PC_HIP(hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pc_bounds_kernel, dim3(nblk < ctx->num_cus * 4 ? nblk : ctx->num_cus * 4), dim3(PC_THREADS), 0, st, cloud, n, d_bounds);
-    PC_HIP(hipGetLastError());
+    // 1: bounds; the grid is anchored at the cloud's minimum corner
     uint32_t hb[8];
-    PC_HIP(hipMemcpyAsync(hb, d_bounds, sizeof(hb), hipMemcpyDeviceToHost, st));
-    PC_HIP(hipStreamSynchronize(st));
-    if (hb[6]) {
-        pc_patches_release(o);
-        return gpc_fail(ctx, GPC_EINVAL, "the cloud holds a non-finite coordinate");
-    }
+    if (int rc = pc_cloud_bounds(ctx, "gpc_project_cloud", cloud, n, hb)) { pc_patches_release(o); return rc; }
     PcGrid g;
     g.res = res;
     g.radius = std::sqrt(3.0f) / 2.0f * res;            // :194
@@ -402,81 +569,41 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
     for (int a = 0; a < 3; ++a) {
         g.mn[a] = (double)pc_unordered(hb[a]);
         const double ext = std::floor(((double)pc_unordered(hb[3 + a]) - g.mn[a]) / res);
-        if (!(ext < 2097152.0)) {
-            pc_patches_release(o);
-            return gpc_fail(ctx, GPC_ERANGE, "more than 2^21 voxels of side res along an axis");
-        }
+        if (!(ext < 2097152.0)) PC_FAIL(GPC_ERANGE, "more than 2^21 voxels of side res along an axis");
         g.kmax[a] = (int)ext;
         cells *= ext + 1.0;
     }
     g.bx = pc_bits_for(g.kmax[0]); g.by = pc_bits_for(g.kmax[1]); g.bz = pc_bits_for(g.kmax[2]);
-    const int key_bits = g.bx + g.by + g.bz;           // <= 63
     const size_t pb = cells < (double)n ? (size_t)cells : N;   // bound on the number of leaves
 
     // scratch
-    size_t sort_bytes = 0, scan_bytes = 0, scan2_bytes = 0;
-    PC_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, N,
-                                     0u, (unsigned)key_bits, st));
-    PC_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, N, rocprim::plus<int32_t>(), st));
+    size_t table_bytes = 0, scan2_bytes = 0;
+    PC_HIP(pc_voxel_table_prim_bytes(ctx, g, N, &table_bytes));
     PC_HIP(rocprim::exclusive_scan(nullptr, scan2_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t)0, pb + 1, rocprim::plus<int32_t>(), st));
-    const size_t prim_bytes = std::max(sort_bytes, std::max(scan_bytes, scan2_bytes));
+    const size_t prim_bytes = std::max(table_bytes, scan2_bytes);
     Scratch S;
     {
         PcCarver measure(nullptr);
-        const int rc = gpc_ws_reserve(ctx, carve_scratch(measure, S, N, pb, prim_bytes));
-        if (rc != GPC_OK) { pc_patches_release(o); return rc; }
+        if (int rc = gpc_ws_reserve(ctx, carve_scratch(measure, S, N, pb, prim_bytes))) { pc_patches_release(o); return rc; }
         PcCarver c(ctx->ws);
         carve_scratch(c, S, N, pb, prim_bytes);
     }
 
-    // 2: keys, stable sort, leaf table
-    hipLaunchKernelGGL(pc_keys_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, g, cloud, n, S.k0, S.v0);
-    PC_HIP(hipGetLastError());
-    size_t tb = S.prim_bytes;
-    PC_HIP(rocprim::radix_sort_pairs(S.prim, tb, S.k0, S.k1, S.v0, S.vals, N, 0u, (unsigned)key_bits, st));
-    hipLaunchKernelGGL(pc_heads_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, S.k1, n, S.head);
-    PC_HIP(hipGetLastError());
-    tb = S.prim_bytes;
-    PC_HIP(rocprim::inclusive_scan(S.prim, tb, S.head, S.leaf_of, N, rocprim::plus<int32_t>(), st));
+    // 2, 3: the voxel table, points in sorted order
     int32_t P = 0;
-    PC_HIP(hipMemcpyAsync(&P, S.leaf_of + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    // 3: sorted-order copy (does not need P: overlaps the read-back)
-    hipLaunchKernelGGL(pc_gather_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, cloud, S.vals, n, S.sp);
-    PC_HIP(hipGetLastError());
-    PC_HIP(hipStreamSynchronize(st));
-    if ((long long)P * (long long)(sz * sz) > 0x7fffffffLL) {
-        pc_patches_release(o);
-        return gpc_fail(ctx, GPC_ERANGE, "P * sz * sz exceeds 2^31-1");
-    }
-    if ((size_t)P > pb) {
-        pc_patches_release(o);
-        return gpc_fail(ctx, GPC_EHIP, "internal: %d leaves exceed the bound %zu", (int)P, pb);
-    }
+    PC_HIP(pc_voxel_table_build(ctx, g, cloud, n, S.T, S.prim, prim_bytes, &P));
+    if ((long long)P * (long long)(sz * sz) > 0x7fffffffLL) PC_FAIL(GPC_ERANGE, "P * sz * sz exceeds 2^31-1");
+    if ((size_t)P > pb) PC_FAIL(GPC_EHIP, "internal: %d leaves exceed the bound %zu", (int)P, pb);
 
-    // the result: one block; per-point arrays are sized by n (an upper bound of the points owned)
+    // the result: one block
     const size_t Pz = (size_t)P, m = (size_t)(sz * sz);
-    PcCarver oc(nullptr);
-    for (int pass = 0; pass < 2; ++pass) {
-        oc = PcCarver(pass ? o->block : nullptr);
-        o->v.off = oc.take<int32_t>(Pz + 1);
-        o->v.rotations = oc.take<double>(9 * Pz);
-        o->v.means = oc.take<double>(3 * Pz);
-        o->v.rgb_means = oc.take<double>(3 * Pz);
-        o->v.W = oc.take<uint8_t>(Pz * m);
-        o->v.x0 = oc.take<double>(N);
-        o->v.x1 = oc.take<double>(N);
-        o->v.y = oc.take<double>(N);
-        o->v.rgb = oc.take<double>(3 * N);
-        o->v.src = oc.take<int32_t>(N);
-        o->leaf_key = oc.take<uint64_t>(Pz);            // (last: the batch's own arrays keep their places)
-        if (!pass) PC_HIP(hipMalloc(&o->block, oc.used));
-    }
+    PC_HIP(pc_patches_alloc(o, Pz, N, m));
     PcArgs A;
     memset(&A, 0, sizeof(A));
     A.g = g; A.n = n; A.P = P;
-    S.leaf_key = const_cast<uint64_t*>(o->leaf_key);    // the leaf table outlives the call: pc_leaves_kernel writes it into the result
+    uint64_t* leaf_key = const_cast<uint64_t*>(o->leaf_key);   // the leaf table outlives the call: it is written into the result
     o->grid = g;
-    A.leaf_key = S.leaf_key; A.leaf_start = S.leaf_start; A.leaf_of = S.leaf_of; A.vals = S.vals; A.sp = S.sp;
+    A.leaf_key = leaf_key; A.leaf_start = S.leaf_start; A.leaf_of = S.T.leaf_of; A.vals = S.T.vals; A.sp = S.T.sp;
     A.nbr = S.nbr; A.M = S.M; A.kcount = S.kcount; A.cen = S.cen; A.owner = S.owner; A.py = S.py; A.px0 = S.px0; A.px1 = S.px1;
     A.cnt = S.cnt; A.nmax = S.cnt + (P + 1);
     A.off = const_cast<int32_t*>(o->v.off); A.R = const_cast<double*>(o->v.rotations); A.mean = const_cast<double*>(o->v.means);
@@ -485,8 +612,7 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
     A.rgb = const_cast<double*>(o->v.rgb); A.src = const_cast<int32_t*>(o->v.src);
     PC_HIP(hipMemsetAsync(S.cnt, 0, sizeof(int32_t) * (Pz + 4), st));
     PC_HIP(hipMemsetAsync(A.W, 0, Pz * m, st));
-    hipLaunchKernelGGL(pc_leaves_kernel, dim3(nblk), dim3(PC_THREADS), 0, st, S.k1, n, (int)P, S.leaf_of, S.leaf_key, S.leaf_start);
-    PC_HIP(hipGetLastError());
+    PC_HIP(pc_voxel_table_leaves(ctx, n, S.T, P, leaf_key, S.leaf_start));
     // 4: frames
     const int lblk = (P + PC_WAVES - 1) / PC_WAVES;
     hipLaunchKernelGGL(pc_moment_kernel, dim3(lblk), dim3(PC_THREADS), 0, st, A);
@@ -496,21 +622,13 @@ int gpc_project_cloud_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, do
     // 5: ownership, offsets
     hipLaunchKernelGGL(pc_claim_kernel, dim3(lblk), dim3(PC_THREADS), 0, st, A);
     PC_HIP(hipGetLastError());
-    tb = S.prim_bytes;
+    size_t tb = prim_bytes;
     PC_HIP(rocprim::exclusive_scan(S.prim, tb, S.cnt, A.off, (int32_t)0, Pz + 1, rocprim::plus<int32_t>(), st));
-    hipLaunchKernelGGL(pc_nmax_kernel, dim3(64), dim3(PC_THREADS), 0, st, S.cnt, (int)P, A.nmax);
-    PC_HIP(hipGetLastError());
+    PC_HIP(pc_nmax(st, A.off, P, A.nmax));
     // 6: the patch batch (the colour planes' pitch is the total, read from off[P] on the device)
     hipLaunchKernelGGL(pc_emit_kernel, dim3(lblk), dim3(PC_THREADS), 0, st, A);
     PC_HIP(hipGetLastError());
-    int32_t total = 0, nmax[3] = {0, 0, 0};
-    PC_HIP(hipMemcpyAsync(&total, A.off + P, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PC_HIP(hipMemcpyAsync(nmax, A.nmax, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PC_HIP(hipStreamSynchronize(st));
-    o->v.P = P; o->v.n_total = total; o->v.n_max = nmax[0];
-    // the size classes of this batch, for the dense dispatch (keyed by the batch's own `off` buffer, which lives as long as the object)
-    ctx->hint_off = o->v.off; ctx->hint_P = P; ctx->hint_le256 = nmax[1]; ctx->hint_le272 = nmax[2];
-    o->serial = gpc_child_register(ctx, o);
+    PC_HIP(pc_patches_publish(ctx, o, P, A.nmax));
     *out = o;
     return GPC_OK;
 }
@@ -523,21 +641,10 @@ int gpc_project_cloud(gpc_ctx* ctx, const gpc_point_xyzrgb* cloud, int n, double
     if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "negative point count");
     if (n > 0 && !cloud) return gpc_fail(ctx, GPC_EINVAL, "cloud is NULL");
     GPC_HIP(ctx, hipSetDevice(ctx->device));
-    void* d_cloud = nullptr;
-    if (n > 0) {
-        GPC_HIP(ctx, hipMalloc(&d_cloud, sizeof(gpc_point_xyzrgb) * (size_t)n));
-        hipError_t e = hipMemcpyAsync(d_cloud, cloud, sizeof(gpc_point_xyzrgb) * (size_t)n, hipMemcpyHostToDevice, gpc_stream_of(ctx));
-        if (e != hipSuccess) {
-            (void)hipFree(d_cloud);
-            return gpc_fail(ctx, GPC_EHIP, "gpc_project_cloud: upload failed: %s", hipGetErrorString(e));
-        }
-    }
-    const int rc = gpc_project_cloud_dev(ctx, (const gpc_point_xyzrgb*)d_cloud, n, res, sz, out);
-    if (d_cloud) {
-        (void)hipStreamSynchronize(gpc_stream_of(ctx));
-        (void)hipFree(d_cloud);
-    }
-    return rc;
+    GpcStaging st(ctx, "gpc_project_cloud");
+    const gpc_point_xyzrgb* d_cloud = st.up(cloud, (size_t)n);
+    if (st.ok()) st.rc = gpc_project_cloud_dev(ctx, d_cloud, n, res, sz, out);
+    return st.finish();
 }
 
 int gpc_patches_view_dev(const gpc_patches* p, gpc_patches_view* view)

@@ -1,13 +1,16 @@
-// producer_internal.h -- what producer.hip (gpc_project_cloud) shares with registration.hip (gpc_registration_*) and mapping.hip
-// (gpc_patches_insert_cloud): the voxel grid of a patch batch, the key arithmetic of its leaf table, the plane frame of a search
-// sphere's moment matrix, and the batch object itself.
+// producer_internal.h -- the cloud cutter: what producer.hip (gpc_project_cloud), registration.hip (gpc_registration_*), mapping.hip
+// (gpc_patches_insert_cloud), raycast.hip (gpc_patches_raycast) and render.hip (gpc_patches_render) share.  Inline device pieces: the
+// voxel grid of a patch batch and the key arithmetic of its leaf table, the search in that table, the per-point walk to the first leaf
+// that accepts a point, a leaf's frame, mask cell and moment matrix, the ray / box test.  Declarations of what producer.hip defines
+// once for every unit: the host stages that turn a cloud into a voxel table and a batch object, and the launchers of the bucket
+// kernels (the library is built without relocatable device code: a kernel is launched from the unit that defines it).
 #pragma once
 
 #include <cmath>
 
 #include "gpc_internal.h"
 
-// Both translation units are bit-exact against CPU restatements: floating-point contraction is off from here to their end, and
+// These translation units are bit-exact against CPU restatements: floating-point contraction is off from here to their end, and
 // every expression below is written in the association of oracle/gpc_oracle_producer.c.
 #pragma clang fp contract(off)
 
@@ -63,14 +66,99 @@ __host__ __device__ static inline float pc_unordered(uint32_t o)
     return f;
 }
 
-__device__ static inline int pc_find_leaf(const uint64_t* leaf_key, int P, uint64_t key)
+// first element >= key of the sorted a[0 .. n)
+template <class T> __device__ static inline int pc_lower_bound(const T* a, int n, T key)
 {
-    int lo = 0, hi = P;                       // first element >= key
+    int lo = 0, hi = n;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if (leaf_key[mid] < key) lo = mid + 1; else hi = mid;
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
     }
+    return lo;
+}
+__device__ static inline int pc_find_leaf(const uint64_t* leaf_key, int P, uint64_t key)
+{
+    const int lo = pc_lower_bound(leaf_key, P, key);
     return (lo < P && leaf_key[lo] == key) ? lo : -1;
+}
+
+// r | g << 8 | b << 16 of a record
+__device__ static inline uint32_t pc_rgb_of(const gpc_point_xyzrgb* q)
+{
+    const uint32_t c = *reinterpret_cast<const uint32_t*>(&q->b);     // b | g << 8 | r << 16 | a << 24
+    return ((c >> 16) & 0xffu) | (c & 0xff00u) | ((c & 0xffu) << 16);
+}
+
+// t = R^T e: e in the frame R (column-major: normal, u, v)
+__device__ static inline void pc_to_frame(const double* R, const double e[3], double t[3])
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[a] = R[3 * a] * e[0] + R[3 * a + 1] * e[1] + R[3 * a + 2] * e[2];
+}
+
+// cell of the sz x sz mask that the in-plane coordinates (u, w) fall into (src/gp_compressor.cpp:90-92), clamped
+__device__ static inline int pc_mask_cell(const PcGrid& g, double u, double w)
+{
+    int gx = (int)((double)g.sz * (u / g.res + 0.5)), gy = (int)((double)g.sz * (w / g.res + 0.5));
+    gx = min(max(gx, 0), g.sz - 1);
+    gy = min(max(gy, 0), g.sz - 1);
+    return g.sz * gx + gy;
+}
+
+// slabs: does the ray o + t d meet the box [lo, hi) at some t >= 0?  tn, tf: where it enters and leaves
+__device__ static inline bool pc_ray_box(const double lo[3], const double hi[3], const double o[3], const double d[3], double& tn, double& tf)
+{
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    tn = -inf;
+    tf = inf;
+    bool meets = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (d[a] != 0.0) {
+            const double t1 = (lo[a] - o[a]) / d[a], t2 = (hi[a] - o[a]) / d[a];
+            tn = fmax(tn, fmin(t1, t2));
+            tf = fmin(tf, fmax(t1, t2));
+        } else if (!(lo[a] <= o[a] && o[a] < hi[a])) {
+            meets = false;
+        }
+    }
+    return meets && tn <= tf && tf >= 0.0;
+}
+
+// The per-point walk of registration and insertion: point p of voxel k (at most one voxel beyond the grid) belongs to the FIRST leaf in
+// leaf order, out of the <= 27 around k, that skip(leaf) does not rule out, whose search sphere (around the voxel centre) holds p and
+// whose +-half window, in the frame R[leaf] around origin[leaf], accepts it.  One binary search per (dz, dy) row: the <= 3 leaves of a row
+// are neighbours in the sorted table.  Returns that leaf and q = R^T (p - origin), or -1 with q untouched.
+template <class Skip>
+__device__ static inline int pc_first_accepting_leaf(const PcGrid& g, const uint64_t* leaf_key, int P, const double p[3], const int k[3],
+                                                     const double* R, const double* origin, Skip skip, double q[3])
+{
+    const double r2 = g.radius * g.radius;
+    const int xlo = max(k[0] - 1, 0), xhi = min(k[0] + 1, g.kmax[0]);
+    for (int j = 0; j < 9 && xlo <= xhi; ++j) {                             // rows (dz, dy) in ascending key order
+        const int nz = k[2] + j / 3 - 1, ny = k[1] + j % 3 - 1;
+        if (nz < 0 || nz > g.kmax[2] || ny < 0 || ny > g.kmax[1]) continue;
+        const uint64_t key_lo = pc_pack(g, xlo, ny, nz), key_hi = pc_pack(g, xhi, ny, nz);
+        for (int L = pc_lower_bound(leaf_key, P, key_lo); L < P; ++L) {     // the row's leaves are consecutive in the table
+            const uint64_t key = leaf_key[L];
+            if (key > key_hi) break;
+            if (skip(L)) continue;
+            int c3[3];
+            pc_unpack(g, key, c3);
+            double cen[3];
+            pc_center(g, c3, cen);
+            const double d[3] = {p[0] - cen[0], p[1] - cen[1], p[2] - cen[2]};
+            if (!(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= r2)) continue;                  // radiusSearch
+            const double* o = origin + (size_t)L * 3;
+            const double e[3] = {p[0] - o[0], p[1] - o[1], p[2] - o[2]};
+            double t[3];
+            pc_to_frame(R + (size_t)L * 9, e, t);
+            if (t[1] > g.half || t[1] < -g.half || t[2] > g.half || t[2] < -g.half) continue;
+            q[0] = t[0]; q[1] = t[1]; q[2] = t[2];
+            return L;
+        }
+    }
+    return -1;
 }
 
 __device__ static inline float pc_readlane_f(float v, int lane)
@@ -197,94 +285,6 @@ __device__ static inline void pc_frame_of_moments(const double* M, int k, double
 #define PC_THREADS 256
 #define PC_WAVES (PC_THREADS / 64)
 
-// ---- the stages both cutters run: bounds, voxel keys, leaf table of the sorted keys, sorted-order copy (launch sites: producer.hip,
-// mapping.hip)
-// out[0..2] = ordered min, out[3..5] = ordered max, out[6] = 1 if a coordinate is not finite
-static __global__ __launch_bounds__(PC_THREADS) void pc_bounds_kernel(const gpc_point_xyzrgb* cloud, int n, uint32_t* out)
-{
-    __shared__ uint32_t red[PC_WAVES][8];
-    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0, 0, 0};
-    int bad = 0;
-    for (int i = blockIdx.x * PC_THREADS + threadIdx.x; i < n; i += gridDim.x * PC_THREADS) {
-        const float4 p = *reinterpret_cast<const float4*>(&cloud[i]);
-        const float c[3] = {p.x, p.y, p.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            bad |= !(fabsf(c[a]) <= 3.4028234e38f);
-            const uint32_t o = pc_ordered(c[a]);
-            lo[a] = min(lo[a], o);
-            hi[a] = max(hi[a], o);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], o));
-            hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], o));
-        }
-    }
-    bad = __any(bad);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[w][a] = lo[a]; red[w][3 + a] = hi[a]; }
-        red[w][6] = (uint32_t)bad;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const int a = threadIdx.x;
-        uint32_t v = red[0][a];
-        for (int q = 1; q < PC_WAVES; ++q) v = a < 3 ? min(v, red[q][a]) : max(v, red[q][a]);   // [6]: 0 / 1, max == or
-        if (a < 3) atomicMin(&out[a], v); else if (a < 6) atomicMax(&out[a], v); else if (v) atomicOr(&out[6], 1u);
-    }
-}
-
-static __global__ __launch_bounds__(PC_THREADS) void pc_keys_kernel(PcGrid g, const gpc_point_xyzrgb* cloud, int n, uint64_t* keys, int32_t* vals)
-{
-    const int i = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = *reinterpret_cast<const float4*>(&cloud[i]);
-    int k[3];
-    pc_voxel(g, p.x, p.y, p.z, k);
-    keys[i] = pc_pack(g, k[0], k[1], k[2]);
-    vals[i] = i;
-}
-
-static __global__ __launch_bounds__(PC_THREADS) void pc_heads_kernel(const uint64_t* keys, int n, int32_t* head)
-{
-    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (s < n) head[s] = (s == 0 || keys[s] != keys[s - 1]) ? 1 : 0;
-}
-
-// leaf_of[s] holds the inclusive scan of head[] on entry (leaf id + 1) and the leaf id on exit
-static __global__ __launch_bounds__(PC_THREADS) void pc_leaves_kernel(const uint64_t* keys, int n, int P, int32_t* leaf_of, uint64_t* leaf_key,
-                                                               int32_t* leaf_start)
-{
-    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (s >= n) return;
-    const int id = leaf_of[s] - 1;
-    leaf_of[s] = id;
-    if (s == 0 || keys[s] != keys[s - 1]) {
-        leaf_key[id] = keys[s];
-        leaf_start[id] = s;
-    }
-    if (s == n - 1) leaf_start[P] = n;
-}
-
-// points re-laid in sorted order
-static __global__ __launch_bounds__(PC_THREADS) void pc_gather_kernel(const gpc_point_xyzrgb* cloud, const int32_t* vals, int n, PcPoint* sp)
-{
-    const int s = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (s >= n) return;
-    const gpc_point_xyzrgb* q = &cloud[vals[s]];
-    const float4 p = *reinterpret_cast<const float4*>(q);
-    const uint32_t c = *reinterpret_cast<const uint32_t*>(&q->b);     // b | g << 8 | r << 16 | a << 24
-    PcPoint o;
-    o.x = p.x; o.y = p.y; o.z = p.z;
-    o.rgb = ((c >> 16) & 0xffu) | (c & 0xff00u) | ((c & 0xffu) << 16);
-    *reinterpret_cast<float4*>(&sp[s]) = *reinterpret_cast<const float4*>(&o);
-}
-
 #define PC_LROW 66         // LDS row pitch (doubles) of the product table: 64 hits + padding against bank conflicts
 
 // One wave, one search sphere: lane j < 27 holds the sorted-order segment [seg0, seg1) of neighbour voxel (dz, dy, dx) = (j / 9, j / 3 % 3,
@@ -362,5 +362,58 @@ struct gpc_patches {
     uint64_t serial = 0;        // gpc_child_register
 };
 
-// producer.hip: unregisters, frees and deletes a batch.  The caller holds ctx->mu (or the object was never published).
+// ---- defined once in producer.hip, for every unit --------------------------------------------------------------------------------
+// unregisters, frees and deletes a batch.  The caller holds ctx->mu (or the object was never published).
 extern "C" void pc_patches_release(gpc_patches* o);
+
+// The error paths of an entry that is building the batch `o` of context `ctx`: release it and fail.
+#define PC_FAIL(...)                       \
+    do {                                   \
+        pc_patches_release(o);             \
+        return gpc_fail(ctx, __VA_ARGS__); \
+    } while (0)
+#define PC_HIP_IN(entry, call)                                                                                                       \
+    do {                                                                                                                             \
+        hipError_t e_ = (call);                                                                                                      \
+        if (e_ != hipSuccess)                                                                                                        \
+            PC_FAIL(e_ == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, entry ": %s failed: %s", #call, hipGetErrorString(e_));        \
+    } while (0)
+
+// The host stages of a cutter, on ctx->stream; the caller holds ctx->mu.  Those that return hipError_t go into PC_HIP_IN.
+// Bounds pass over n > 0 points, in the first 4096 bytes of the workspace: hb[0..2] = ordered min corner, hb[3..5] = ordered max corner
+// (pc_unordered).  Refuses a non-finite coordinate (GPC_EINVAL).
+int pc_cloud_bounds(gpc_ctx* ctx, const char* entry, const gpc_point_xyzrgb* cloud, int n, uint32_t hb[8]);
+
+// scratch of the voxel table of n points: the caller carves it among its own and provides prim_bytes >= pc_voxel_table_prim_bytes
+struct PcVoxelTable {
+    uint64_t *k0, *keys;        // n: voxel keys in cloud order; sorted
+    int32_t *v0, *vals;         // n: cloud index; in sorted order
+    int32_t *head, *leaf_of;    // n: 1 where a voxel starts; leaf id per sorted position
+    PcPoint* sp;                // n: the points in sorted order
+    void carve(PcCarver& c, size_t n)
+    {
+        k0 = c.take<uint64_t>(n); keys = c.take<uint64_t>(n);
+        v0 = c.take<int32_t>(n); vals = c.take<int32_t>(n);
+        head = c.take<int32_t>(n); leaf_of = c.take<int32_t>(n);
+        sp = c.take<PcPoint>(n);
+    }
+};
+// rocPRIM's temporary storage for the sort and the scan of pc_voxel_table_build
+hipError_t pc_voxel_table_prim_bytes(gpc_ctx* ctx, const PcGrid& g, size_t n, size_t* bytes);
+// keys -> stable sort -> heads -> scan -> gather; *count = the number of occupied voxels, read back (the stream is idle on return)
+hipError_t pc_voxel_table_build(gpc_ctx* ctx, const PcGrid& g, const gpc_point_xyzrgb* cloud, int n, const PcVoxelTable& T, void* prim,
+                                size_t prim_bytes, int32_t* count);
+// ... and, once the caller knows where they go: leaf_key[count] sorted unique keys, leaf_start[count + 1] their segments of T.sp
+hipError_t pc_voxel_table_leaves(gpc_ctx* ctx, int n, const PcVoxelTable& T, int count, uint64_t* leaf_key, int32_t* leaf_start);
+
+// the one layout of a batch's block: allocates o->block for P leaves of m cells and at most N points, sets o->v's pointers and o->leaf_key
+hipError_t pc_patches_alloc(gpc_patches* o, size_t P, size_t N, size_t m);
+// the tail of a cutter: reads off[P] and nmax_dev[0..2] (pc_nmax), fills the view, leaves the size classes with the context, registers o
+hipError_t pc_patches_publish(gpc_ctx* ctx, gpc_patches* o, int P, const int32_t* nmax_dev);
+
+// off[j] = first position of the sorted owners skey[0 .. n) that holds an owner >= j, j = 0 .. P: the exclusive scan of the per-leaf counts
+// read off the sorted keys (no atomics); the unowned points (key P) sit behind off[P]
+hipError_t pc_bucket_offsets(hipStream_t st, const uint32_t* skey, int n, int P, int32_t* off);
+// nmax[0] = largest patch; nmax[1], nmax[2] = patches of <= 256 / <= 272 points: the size classes of the dense dispatch (dense_api.hip), which
+// the host reads together with n_max and hands to it so that the class launches are sized exactly.  nmax[0..2] are zero on entry.
+hipError_t pc_nmax(hipStream_t st, const int32_t* off, int P, int32_t* nmax);

@@ -76,16 +76,12 @@ __device__ static inline int rc_plane_cell(const RcArgs& A, int L, const double 
     const double d = num / den;                               // :194
     const double e[3] = {(A.org[0] + d * delta[0]) - mu[0], (A.org[1] + d * delta[1]) - mu[1], (A.org[2] + d * delta[2]) - mu[2]};   // :195
     double t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t[a] = R[3 * a] * e[0] + R[3 * a + 1] * e[1] + R[3 * a + 2] * e[2];          // R^T (x - mean), :196
+    pc_to_frame(R, e, t);                                     // R^T (x - mean), :196
     if (!(fabs(d) <= 1.7976931348623157e308) || !(fabs(t[0]) <= 1.7976931348623157e308) || !(fabs(t[1]) <= 1.7976931348623157e308) ||
         !(fabs(t[2]) <= 1.7976931348623157e308))
         return -1;
     if (t[1] > g.half || t[1] < -g.half || t[2] > g.half || t[2] < -g.half) return -1;                        // :197
-    int gx = (int)((double)g.sz * (t[1] / g.res + 0.5)), gy = (int)((double)g.sz * (t[2] / g.res + 0.5));      // :200-201
-    gx = min(max(gx, 0), g.sz - 1);
-    gy = min(max(gy, 0), g.sz - 1);
-    return g.sz * gx + gy;
+    return pc_mask_cell(g, t[1], t[2]);                       // :200-201
 }
 
 // ---- a thread per ray ------------------------------------------------------------------------------------------------------------
@@ -109,22 +105,15 @@ __global__ __launch_bounds__(PC_THREADS) void rc_cast_kernel(RcArgs A)
             }
             int k[3];
             pc_unpack(g, A.leaf_key[own], k);
-            // the owner's voxel against the ray: slabs
-            const double inf = __longlong_as_double(0x7ff0000000000000ll);
-            double tn = -inf, tf = inf;
-            bool meets = true;
+            // the owner's voxel against the ray
+            double lo[3], hi[3], tn, tf;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const double lo = g.mn[a] + (double)(k[a] - g.koff[a]) * g.res, hi = g.mn[a] + (double)(k[a] - g.koff[a] + 1) * g.res;
-                if (delta[a] != 0.0) {
-                    const double t1 = (lo - o[a]) / delta[a], t2 = (hi - o[a]) / delta[a];
-                    tn = fmax(tn, fmin(t1, t2));
-                    tf = fmin(tf, fmax(t1, t2));
-                } else if (!(lo <= o[a] && o[a] < hi)) {
-                    meets = false;
-                }
+                lo[a] = g.mn[a] + (double)(k[a] - g.koff[a]) * g.res;
+                hi[a] = g.mn[a] + (double)(k[a] - g.koff[a] + 1) * g.res;
             }
-            meets = meets && tn <= tf && tf >= 0.0;
+            const double inf = __longlong_as_double(0x7ff0000000000000ll);
+            const bool meets = pc_ray_box(lo, hi, o, delta, tn, tf);
             if (meets) {
                 noop = 0;
                 const int m = g.sz * g.sz;

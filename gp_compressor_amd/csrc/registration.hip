@@ -8,11 +8,12 @@
 // FIRST leaf in leaf order that accepts it, and only the <= 27 leaves around the point's own voxel can.  The model's voxel table
 // (PcGrid + sorted leaf keys, kept by gpc_patches) stands in for the octree; leaf id = patch id = GP index.
 // Pipeline (wave64, integer / gather work except the two likelihood launches):
-//   1 rg_assign_kernel    a lane per scan point: voxel key, one binary search per (dz, dy) row of the 3 x 3 x 3 neighbourhood (the <= 3
-//                         leaves of a row are neighbours in the sorted table), candidates in ascending leaf order, untrained leaves
-//                         skipped (:158), sphere test against the voxel centre, q = R_i^T (p - mean_i) (:104), window (:105)
+//   1 rg_assign_kernel    a lane per scan point: voxel key, then pc_first_accepting_leaf (producer_internal.h): one binary search per
+//                         (dz, dy) row of the 3 x 3 x 3 neighbourhood (the <= 3 leaves of a row are neighbours in the sorted table),
+//                         candidates in ascending leaf order, untrained leaves skipped (:158), sphere test against the voxel centre,
+//                         q = R_i^T (p - mean_i) (:104), window (:105)
 //   2 bucket              rocPRIM's stable radix sort of (owner, scan index) -- patch order, ascending scan index within a patch, the
-//                         unused points (key P) behind off[P]; rg_offsets_kernel: off[j] = first sorted position whose key is >= j
+//                         unused points (key P) behind off[P]; pc_bucket_offsets: off[j] = first sorted position whose key is >= j
 //                         (the exclusive scan of the per-patch counts, read off the sorted keys: no atomics);
 //     rg_gather_kernel    X, depth and mean-removed colours (:166-171) in bucket order, planes of pitch n
 //   3 sparse_likelihood_kernel twice (sparse_predict.hip): dX, l of the depth GP, dCX, cl of the colour field (:175-195)
@@ -96,38 +97,8 @@ __global__ __launch_bounds__(RG_THREADS) void rg_assign_kernel(RgArgs A)
     double q[3] = {0.0, 0.0, 0.0};
     if (near) {
         const int k[3] = {(int)kd[0], (int)kd[1], (int)kd[2]};
-        const double r2 = g.radius * g.radius;
-        const int xlo = max(k[0] - 1, 0), xhi = min(k[0] + 1, g.kmax[0]);
-        for (int j = 0; j < 9 && owner < 0 && xlo <= xhi; ++j) {            // rows (dz, dy) in ascending key order
-            const int nz = k[2] + j / 3 - 1, ny = k[1] + j % 3 - 1;
-            if (nz < 0 || nz > g.kmax[2] || ny < 0 || ny > g.kmax[1]) continue;
-            const uint64_t key_lo = pc_pack(g, xlo, ny, nz), key_hi = pc_pack(g, xhi, ny, nz);
-            int lo = 0, hi = A.P;                                           // first leaf with key >= key_lo
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (A.leaf_key[mid] < key_lo) lo = mid + 1; else hi = mid;
-            }
-            for (int L = lo; L < A.P && owner < 0; ++L) {                   // the row's leaves are consecutive in the table
-                const uint64_t key = A.leaf_key[L];
-                if (key > key_hi) break;
-                if (A.bv[L] == 0) continue;                                 // gps[i].size() == 0 (:158)
-                int c3[3];
-                pc_unpack(g, key, c3);
-                double cen[3];
-                pc_center(g, c3, cen);
-                const double d[3] = {p[0] - cen[0], p[1] - cen[1], p[2] - cen[2]};
-                if (!(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= r2)) continue;          // radiusSearch (:161)
-                const double* R = A.R + (size_t)L * 9;
-                const double* mu = A.mean + (size_t)L * 3;
-                const double e[3] = {p[0] - mu[0], p[1] - mu[1], p[2] - mu[2]};
-                double t[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) t[a] = R[3 * a] * e[0] + R[3 * a + 1] * e[1] + R[3 * a + 2] * e[2];   // R^T (p - mean) (:104)
-                if (t[1] > g.half || t[1] < -g.half || t[2] > g.half || t[2] < -g.half) continue;                // :105
-                owner = L;
-                q[0] = t[0]; q[1] = t[1]; q[2] = t[2];
-            }
-        }
+        const int32_t* bv = A.bv;                                           // skipped: gps[i].size() == 0 (:158); q = R^T (p - mean) (:104)
+        owner = pc_first_accepting_leaf(g, A.leaf_key, A.P, p, k, A.R, A.mean, [bv](int L) { return bv[L] == 0; }, q);
     }
     A.owner[i] = owner;
     A.local[(size_t)i * 3] = q[0];
@@ -138,18 +109,6 @@ __global__ __launch_bounds__(RG_THREADS) void rg_assign_kernel(RgArgs A)
 }
 
 // ---- 2: bucket ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RG_THREADS) void rg_offsets_kernel(RgArgs A)
-{
-    const int j = blockIdx.x * RG_THREADS + threadIdx.x;
-    if (j > A.P) return;
-    int lo = 0, hi = A.n;                                                    // first sorted position with key >= j
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (A.skey[mid] < (uint32_t)j) lo = mid + 1; else hi = mid;
-    }
-    A.off[j] = lo;
-}
-
 __global__ __launch_bounds__(RG_THREADS) void rg_gather_kernel(RgArgs A)
 {
     const int s = blockIdx.x * RG_THREADS + threadIdx.x;
@@ -161,11 +120,11 @@ __global__ __launch_bounds__(RG_THREADS) void rg_gather_kernel(RgArgs A)
         y = A.local[(size_t)i * 3];
         x0 = A.local[(size_t)i * 3 + 1];
         x1 = A.local[(size_t)i * 3 + 2];
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(&A.cloud[i].b);     // b | g << 8 | r << 16 | a << 24
+        const uint32_t w = pc_rgb_of(&A.cloud[i]);
         const double* cm = A.rgb_mean + (size_t)o * 3;
-        c[0] = (double)((w >> 16) & 0xffu) - cm[0];                               // :169-171
+        c[0] = (double)(w & 0xffu) - cm[0];                                       // :169-171
         c[1] = (double)((w >> 8) & 0xffu) - cm[1];
-        c[2] = (double)(w & 0xffu) - cm[2];
+        c[2] = (double)((w >> 16) & 0xffu) - cm[2];
     }
     A.y[s] = y;
     A.x0[s] = x0;
@@ -312,13 +271,6 @@ __global__ __launch_bounds__(64) void rg_reset_kernel(double* state)
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-int rg_bits_for(int kmax)
-{
-    int b = 1;
-    while ((1ll << b) <= (long long)kmax) ++b;
-    return b;
-}
-
 // the caller holds ctx->mu
 bool rg_usable(const gpc_registration* r)
 {
@@ -349,30 +301,24 @@ int rg_step_locked(gpc_registration* r, const gpc_registration_params* prm, doub
     memset(&A, 0, sizeof(A));
     int nred = 0;
     if (work) {
-        const unsigned key_bits = (unsigned)rg_bits_for(P);
+        const unsigned key_bits = (unsigned)pc_bits_for(P);
         size_t sort_bytes = 0;
         GPC_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                                                (int32_t*)nullptr, N, 0u, key_bits, st));
         const int nblk = (n + RG_THREADS - 1) / RG_THREADS;
         nred = std::min(nblk, ctx->num_cus * 8);
         void* prim = nullptr;
-        for (int pass = 0; pass < 2; ++pass) {            // measure, reserve, carve (256-byte aligned pieces)
-            char* base = pass ? static_cast<char*>(ctx->ws) : nullptr;
-            size_t used = 0;
-            auto take = [&](size_t bytes) {
-                void* q = base ? base + used : nullptr;
-                used += (bytes + 255) & ~(size_t)255;
-                return q;
-            };
-            A.key = (uint32_t*)take(4 * N); A.skey = (uint32_t*)take(4 * N);
-            A.val = (int32_t*)take(4 * N); A.sval = (int32_t*)take(4 * N);
-            A.off = (int32_t*)take(4 * (Pz + 1));
-            A.x0 = (double*)take(8 * N); A.x1 = (double*)take(8 * N); A.y = (double*)take(8 * N); A.rgb = (double*)take(24 * N);
-            A.dXd = (double*)take(24 * N); A.ld = (double*)take(8 * N); A.dXc = (double*)take(24 * N); A.lc = (double*)take(8 * N);
-            A.part = (double*)take(8 * (size_t)nred * RG_NQ);
-            prim = take(sort_bytes);
+        for (int pass = 0; pass < 2; ++pass) {            // measure, reserve, carve
+            PcCarver c(pass ? ctx->ws : nullptr);
+            A.key = c.take<uint32_t>(N); A.skey = c.take<uint32_t>(N);
+            A.val = c.take<int32_t>(N); A.sval = c.take<int32_t>(N);
+            A.off = c.take<int32_t>(Pz + 1);
+            A.x0 = c.take<double>(N); A.x1 = c.take<double>(N); A.y = c.take<double>(N); A.rgb = c.take<double>(3 * N);
+            A.dXd = c.take<double>(3 * N); A.ld = c.take<double>(N); A.dXc = c.take<double>(3 * N); A.lc = c.take<double>(N);
+            A.part = c.take<double>((size_t)nred * RG_NQ);
+            prim = c.take<char>(sort_bytes);
             if (!pass)
-                if (int rc = gpc_ws_reserve(ctx, used)) return rc;
+                if (int rc = gpc_ws_reserve(ctx, c.used)) return rc;
         }
         const gpc_patches* pt = r->pt;
         A.g = pt->grid; A.n = n; A.P = P;
@@ -382,8 +328,7 @@ int rg_step_locked(gpc_registration* r, const gpc_registration_params* prm, doub
         hipLaunchKernelGGL(rg_assign_kernel, dim3(nblk), dim3(RG_THREADS), 0, st, A);
         GPC_HIP(ctx, hipGetLastError());
         GPC_HIP(ctx, rocprim::radix_sort_pairs(prim, sort_bytes, A.key, A.skey, A.val, A.sval, N, 0u, key_bits, st));
-        hipLaunchKernelGGL(rg_offsets_kernel, dim3((P + 1 + RG_THREADS - 1) / RG_THREADS), dim3(RG_THREADS), 0, st, A);
-        GPC_HIP(ctx, hipGetLastError());
+        GPC_HIP(ctx, pc_bucket_offsets(st, A.skey, n, P, A.off));
         hipLaunchKernelGGL(rg_gather_kernel, dim3(nblk), dim3(RG_THREADS), 0, st, A);
         GPC_HIP(ctx, hipGetLastError());
         // 3: the registration inner loop on the bucketed scan (plane pitch n; the kernel reads off on the device)

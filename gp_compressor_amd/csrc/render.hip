@@ -77,11 +77,8 @@ __device__ static inline int rn_surface(const RnArgs& A, int L, const int k[3], 
     double a[3], c[3];
     {
         const double e[3] = {A.org[0] - mu[0], A.org[1] - mu[1], A.org[2] - mu[2]};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            a[j] = R[3 * j] * e[0] + R[3 * j + 1] * e[1] + R[3 * j + 2] * e[2];
-            c[j] = R[3 * j] * d[0] + R[3 * j + 1] * d[1] + R[3 * j + 2] * d[2];
-        }
+        pc_to_frame(R, e, a);
+        pc_to_frame(R, d, c);
     }
     // the plane (rc_plane_cell's association)
     const double num = R[0] * (mu[0] - A.org[0]) + R[1] * (mu[1] - A.org[1]) + R[2] * (mu[2] - A.org[2]);
@@ -123,10 +120,7 @@ __device__ static inline int rn_surface(const RnArgs& A, int L, const int k[3], 
     }
     if (!(r2 <= g.radius * g.radius)) return 0;
     if (A.W || A.cells) {
-        int gx = (int)((double)g.sz * (q1 / g.res + 0.5)), gy = (int)((double)g.sz * (q2 / g.res + 0.5));   // (|q| <= half: in range)
-        gx = min(max(gx, 0), g.sz - 1);
-        gy = min(max(gy, 0), g.sz - 1);
-        const size_t cell = (size_t)L * (size_t)A.m + (size_t)(g.sz * gx + gy);
+        const size_t cell = (size_t)L * (size_t)A.m + (size_t)pc_mask_cell(g, q1, q2);
         if (A.W && A.W[cell] == 0) return 0;
         if (A.cells && A.cells[cell] == GPC_CELL_FREE) return 0;
     }
@@ -149,19 +143,14 @@ __global__ __launch_bounds__(PC_THREADS) void rn_render_kernel(RnArgs A)
         const double d[3] = {A.dirs[(size_t)i * 3], A.dirs[(size_t)i * 3 + 1], A.dirs[(size_t)i * 3 + 2]};
         bool meets = rn_finite(d[0]) && rn_finite(d[1]) && rn_finite(d[2]) && !(d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) && A.P > 0;
         double tn = -inf, tf = inf;
-        if (meets) {
+        if (meets) {                                          // the grid box against the ray
+            double lo[3], hi[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const double lo = g.mn[a] + (double)(0 - g.koff[a]) * g.res, hi = g.mn[a] + (double)(g.kmax[a] + 1 - g.koff[a]) * g.res;
-                if (d[a] != 0.0) {
-                    const double t1 = (lo - A.org[a]) / d[a], t2 = (hi - A.org[a]) / d[a];
-                    tn = fmax(tn, fmin(t1, t2));
-                    tf = fmin(tf, fmax(t1, t2));
-                } else if (!(lo <= A.org[a] && A.org[a] < hi)) {
-                    meets = false;
-                }
+                lo[a] = g.mn[a] + (double)(0 - g.koff[a]) * g.res;
+                hi[a] = g.mn[a] + (double)(g.kmax[a] + 1 - g.koff[a]) * g.res;
             }
-            meets = meets && tn <= tf && tf >= 0.0;
+            meets = pc_ray_box(lo, hi, A.org, d, tn, tf);
         }
         RnHit h;
         int hitL = -1;

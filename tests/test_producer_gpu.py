@@ -71,6 +71,13 @@ def test_producer_matches_oracle_bit_for_bit(gp, oracle, case):
     pt.close()
 
 
+def _device(cloud):
+    import torch
+    d = torch.from_numpy(cloud.view(np.uint8).reshape(-1, 32)).cuda()
+    torch.cuda.synchronize()
+    return d
+
+
 def test_producer_edge_cases(gp, oracle):
     capi, ctx = gp
     # empty cloud
@@ -82,8 +89,14 @@ def test_producer_edge_cases(gp, oracle):
                 np.tile(np.array([[0.5, 0.5, 0.5]]), (70, 1))):
         rgb = (np.arange(3 * len(xyz)).reshape(-1, 3) * 7 % 256).astype(np.uint8)
         want = oracle.project_cloud(xyz, rgb, 0.1, 4)
-        pt = ctx.project_cloud(ctx.make_cloud(xyz, rgb), 0.1, 4)
+        cloud = ctx.make_cloud(xyz, rgb)
+        pt = ctx.project_cloud(cloud, 0.1, 4)
         _same(pt.fetch(), want)
+        # the device-pointer entry on the same cloud: the same batch
+        pt_dev = ctx.project_cloud(_device(cloud), 0.1, 4, n=len(cloud))
+        _same(pt_dev.fetch(), pt.fetch())
+        assert pt_dev.view.n_max == pt.view.n_max
+        pt_dev.close()
         pt.close()
     # argument checking: never aborts, reports
     cloud = ctx.make_cloud(np.array([[0, 0, 0], [1, 1, 1]]), np.zeros((2, 3)))
@@ -119,6 +132,10 @@ def test_producer_feeds_the_gp_kernels_on_device(gp, oracle):
     v = pt.view
     b = pt.fetch()
     assert np.array_equal(b["off"], oracle.project_cloud(xyz, rgb, res, sz)["off"])
+    pt_host = ctx.project_cloud(cloud, res, sz)                       # the host-pointer entry on the same cloud: the same batch
+    _same(pt_host.fetch(), b)
+    assert (pt_host.view.P, pt_host.view.n_total, pt_host.view.n_max) == (v.P, v.n_total, v.n_max)
+    pt_host.close()
     p = capi.default_params_dense(sigmaf_sq=1.0, l_sq=(res / 8) ** 2, noise=1e-4)
     m = sz * sz
     f = torch.zeros(v.P, m, dtype=torch.float64, device="cuda")
