@@ -122,3 +122,103 @@ def test_sharded_dense_flow_through_the_c_abi(gp, oracle):
     assert np.max(np.abs(got - fo[:, 0, :])) <= 1e-9 * np.max(np.abs(fo))
     comm.close()
     ctx.set_stream(None)
+
+
+# ---- the un-permutation kernel on its own, and chained into the reprojection it feeds -------------------------------------------------------
+UNPERMUTE_ROWS = (1, 2, 3, 256, 257, 258)      # even: 16-byte accesses, odd: 8-byte; below, at and above two passes of the 128 threads
+
+
+@pytest.mark.parametrize("P", [1, 1025, 3000])
+def test_unpermute_alone_under_a_random_permutation(gp, P):
+    """gpc_unpermute_fstar_dev without a collective: every row of f* is its source row bit for bit, none stays as it was (NaN)"""
+    import torch
+    capi, ctx = gp
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    rng = np.random.default_rng(300 + P)
+    slots = rng.permutation(P).astype(np.int32)                 # slot s holds patch slots[s]: not the LPT order of a cost
+    comm = capi.Comm(ctx, 1, 0)
+    try:
+        comm.set_partition(P, slots)
+        for row in UNPERMUTE_ROWS:
+            elems = row // 2 if row % 2 == 0 else row
+            print("P = %d workgroups, rows of %d doubles: %d accesses of %d bytes, %d passes of the 128 threads" % (P, row, elems, 8 * row // elems, -(-elems // 128)))
+            gathered = torch.randn((P, row), dtype=torch.float64, device="cuda")
+            f_star = torch.full((P, row), float("nan"), dtype=torch.float64, device="cuda")
+            comm.unpermute_fstar_dev(row, gathered, f_star)
+            ctx.synchronize()
+            want = np.empty((P, row))
+            want[slots] = gathered.cpu().numpy()
+            got = f_star.cpu().numpy()
+            assert not np.isnan(got).any()
+            assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
+    finally:
+        comm.close()
+        ctx.set_stream(None)
+
+
+def test_sharded_tail_gather_unpermute_reproject(gp, oracle):
+    """the tail of the sharded flow in one piece: f* (P, m) and C* (P, 3 m) in slot order -> all-gather + un-permutation of each (rows of
+    m and of 3 m doubles) -> gpc_reproject_dev with a bv_count in patch order; the cloud is the oracle's on the patch-order inputs"""
+    import torch
+    import reproject_cases as RC
+    capi, ctx = gp
+    P, m = 1025, RC.COMPACTION_M
+    bv, (xs0, xs1, f, R, mu, cs, cm) = RC.compaction_case(P, "random")
+    n_on = len(RC.trained(P, bv))
+    grid = min(P, 8 * torch.cuda.get_device_properties(0).multi_processor_count)
+    print("P = %d, per = %d, emit grid = %d, trained = %d; un-permuted rows of %d and %d doubles" % (P, RC.per_of(P), grid, n_on, m, 3 * m))
+    want = RC.expected(oracle, xs0, xs1, f, R, mu, cs, cm, bv)
+    slots = np.random.default_rng(41).permutation(P).astype(np.int32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    comm = capi.Comm(ctx, 1, 0)
+    try:
+        comm.set_partition(P, slots)
+        local_f, local_c = t(f[slots]), t(cs.reshape(P, 3 * m)[slots])      # row s = the grids of the patch in slot s
+        gath_f, gath_c = torch.empty_like(local_f), torch.empty_like(local_c)
+        f_star = torch.full((P, m), float("nan"), dtype=torch.float64, device="cuda")
+        c_star = torch.full((P, 3 * m), float("nan"), dtype=torch.float64, device="cuda")
+        comm.allgather_fstar_dev(m, local_f, gath_f, f_star)
+        comm.allgather_fstar_dev(3 * m, local_c, gath_c, c_star)
+        out = torch.full((P * m, 32), 0xA5, dtype=torch.uint8, device="cuda")
+        n_pts = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        d_bv, d_xs0, d_xs1, d_R, d_mu, d_cm = (t(a) for a in (bv, xs0, xs1, R, mu, cm))
+        ctx.reproject_dev(P, m, d_bv, d_xs0, d_xs1, f_star, c_star, d_R, d_mu, d_cm, out, n_pts)
+        ctx.synchronize()
+        n, raw = int(n_pts.cpu()[0]), out.cpu().numpy()
+        assert np.array_equal(f_star.cpu().numpy(), f)
+    finally:
+        comm.close()
+        ctx.set_stream(None)
+    assert n == m * n_on == len(want)
+    assert raw[:n].tobytes() == want.tobytes()
+    assert np.all(raw[n:] == 0xA5)
+
+
+def test_set_partition_refusals_keep_the_table(gp):
+    """a slot that names no patch of the batch, a slot below -1 and an empty slot at world 1 (a patch is left without one): GPC_EINVAL
+    each, and the un-permutation after each still goes by the table set before"""
+    import torch
+    capi, ctx = gp
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    P, row = 37, 6
+    slots = np.random.default_rng(17).permutation(P).astype(np.int32)
+    comm = capi.Comm(ctx, 1, 0)
+    try:
+        comm.set_partition(P, slots)
+        gathered = torch.randn((P, row), dtype=torch.float64, device="cuda")
+        want = np.empty((P, row))
+        want[slots] = gathered.cpu().numpy()
+        for at, bad in ((3, P), (P - 1, P + 5), (0, -2), (20, -1)):
+            table = slots.copy()
+            table[at] = bad
+            with pytest.raises(capi.GpcError) as e:
+                comm.set_partition(P, table)
+            assert e.value.code == capi.GPC_EINVAL
+            f_star = torch.full((P, row), float("nan"), dtype=torch.float64, device="cuda")
+            comm.unpermute_fstar_dev(row, gathered, f_star)
+            ctx.synchronize()
+            assert np.array_equal(f_star.cpu().numpy(), want)
+    finally:
+        comm.close()
+        ctx.set_stream(None)
