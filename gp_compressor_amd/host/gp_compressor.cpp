@@ -98,19 +98,186 @@ void check(int rc, gpc_ctx* ctx, const char* what)
                                                " (code " + std::to_string(rc) + ")");
 }
 
+// Device memory of one context, owned: allocated (and optionally filled from a host vector) in the constructor, freed in the destructor
+// (gpc_dev_free synchronises the context's stream first).  Whatever throws, nothing allocated through it leaks.
+class dev_buf {
+    gpc_ctx* ctx_ = nullptr;
+    void* p_ = nullptr;
+public:
+    dev_buf() = default;
+    dev_buf(gpc_ctx* c, size_t bytes) : ctx_(c) { check(gpc_dev_malloc(c, bytes, &p_), c, "gpc_dev_malloc"); }
+    template <class T> dev_buf(gpc_ctx* c, const std::vector<T>& h) : dev_buf(c, sizeof(T) * h.size())   // delegating: a failed upload frees
+    {
+        check(gpc_dev_memcpy(c, p_, h.data(), sizeof(T) * h.size(), GPC_COPY_H2D), c, "gpc_dev_memcpy (upload)");
+    }
+    dev_buf(dev_buf&& o) noexcept : ctx_(o.ctx_), p_(o.release<void>()) {}
+    dev_buf& operator=(dev_buf&& o) noexcept { std::swap(ctx_, o.ctx_); std::swap(p_, o.p_); return *this; }
+    ~dev_buf() { if (p_) (void)gpc_dev_free(ctx_, p_); }
+    template <class T> T* as() const { return static_cast<T*>(p_); }
+    template <class T> T* release() { T* q = as<T>(); p_ = nullptr; return q; }   // the caller owns it from here
+    void download(void* h, size_t bytes) const { check(gpc_dev_memcpy(ctx_, h, p_, bytes, GPC_COPY_D2H), ctx_, "gpc_dev_memcpy (download)"); }
+};
+
+// Declared AFTER the buffers of a sharded scope, so that it runs before them, on the normal and on the throwing path: no buffer of any
+// device is freed before every shard context has been synchronised -- a peer may still be reading it in the exchange.
+struct sync_shards {
+    const std::vector<gpc_ctx*>& ctxs;
+    ~sync_shards() { for (gpc_ctx* c : ctxs) (void)gpc_ctx_synchronize(c); }
+};
+
+// The RCCL group bracket: a group left open would swallow every later collective of the process, so the destructor ends it.
+class rccl_group {
+    gpc_ctx* ctx_;
+    bool open_ = false;
+public:
+    explicit rccl_group(gpc_ctx* c) : ctx_(c) { check(gpc_group_start(), c, "gpc_group_start"); open_ = true; }
+    void end() { open_ = false; check(gpc_group_end(), ctx_, "gpc_group_end"); }
+    ~rccl_group() { if (open_) (void)gpc_group_end(); }
+};
+
+// ---- the shard layout: pure host code (reached without a GPU through gpc_host_shard / gpc_host_shard_scatter) ------------------------
+// what the two sharded flows hand gpc_partition_patches as the cost model: 0 = dense (n^3), > 0 = sparse (n min(n, capacity)^2)
+int sparse_cost(const gpc_params& depth) { return depth.capacity > 0 ? depth.capacity : 1; }
+
+// slot -> patch table, world * S entries with S = ceil(P / world), -1 = padding
+std::vector<int32_t> deal_patches(const patch_batch& b, int world, int cost)
+{
+    if (world <= 0) throw std::invalid_argument("deal_patches: world must be positive");
+    const int P = b.patches();
+    std::vector<int32_t> slots((size_t)((P + world - 1) / world) * world, -1);
+    if (P > 0) check(gpc_partition_patches(P, b.off.data(), world, cost, slots.data()), nullptr, "gpc_partition_patches");
+    return slots;
+}
+
+struct shard_batch {
+    std::vector<int32_t> off, pd, pc;       // off: S + 1; pd / pc: the insertion orders of the local points (empty when none were given)
+    std::vector<double> x0, x1, y, rgb;     // rgb: three planes with the LOCAL stride off[S]
+    int n_max = 0;
+};
+
+// The slots of device r as a local CSR batch: slot q holds the rows of patch slots[r * S + q], a padding slot is an empty patch.
+// perm_d / perm_c (patch order, may be null) hold patch-local indices, so they travel with their patch unchanged.
+shard_batch cut_shard(const patch_batch& b, const std::vector<int32_t>& slots, int world, int r, const int32_t* perm_d = nullptr,
+                      const int32_t* perm_c = nullptr)
+{
+    const size_t S = slots.size() / world, N = b.x0.size();
+    const int32_t* mine = slots.data() + r * S;
+    shard_batch s;
+    s.off.assign(S + 1, 0);
+    for (size_t q = 0; q < S; ++q) {
+        const int p = mine[q];
+        const int n = p >= 0 ? b.off[p + 1] - b.off[p] : 0;
+        s.off[q + 1] = s.off[q] + n;
+        s.n_max = std::max(s.n_max, n);
+    }
+    const size_t Nl = (size_t)s.off[S];
+    s.x0.resize(Nl); s.x1.resize(Nl); s.y.resize(Nl); s.rgb.resize(3 * Nl);
+    if (perm_d) s.pd.resize(Nl);
+    if (perm_c) s.pc.resize(Nl);
+    for (size_t q = 0; q < S; ++q) {
+        const int p = mine[q];
+        if (p < 0) continue;
+        const size_t o = (size_t)b.off[p], n = (size_t)(b.off[p + 1] - b.off[p]), lo = (size_t)s.off[q];
+        std::copy_n(b.x0.data() + o, n, s.x0.data() + lo);
+        std::copy_n(b.x1.data() + o, n, s.x1.data() + lo);
+        std::copy_n(b.y.data() + o, n, s.y.data() + lo);
+        for (int a = 0; a < 3; ++a) std::copy_n(b.rgb.data() + a * N + o, n, s.rgb.data() + a * Nl + lo);
+        if (perm_d) std::copy_n(perm_d + o, n, s.pd.data() + lo);
+        if (perm_c) std::copy_n(perm_c + o, n, s.pc.data() + lo);
+    }
+    return s;
+}
+
+// a per-slot array of device r into patch order; padding slots write nothing
+void scatter_slots(const std::vector<int32_t>& slots, int world, int r, const int32_t* per_slot, int32_t* per_patch)
+{
+    const size_t S = slots.size() / world;
+    for (size_t q = 0; q < S; ++q) {
+        const int p = slots[r * S + q];
+        if (p >= 0) per_patch[p] = per_slot[q];
+    }
+}
+
+// ---- the device side of a shard ------------------------------------------------------------------------------------------------------
+struct dev_shard {
+    shard_batch h;
+    dev_buf off, x0, x1, y, rgb, pd, pc, st;     // st: one status word per slot; pd / pc stay 8 spare bytes without insertion orders
+    dev_shard(gpc_ctx* c, shard_batch&& b)
+        : h(std::move(b)), off(c, h.off), x0(c, h.x0), x1(c, h.x1), y(c, h.y), rgb(c, h.rgb), pd(c, h.pd), pc(c, h.pc),
+          st(c, sizeof(int32_t) * (h.off.size() - 1)) {}
+};
+
+void fetch_status(const std::vector<dev_shard>& sh, const std::vector<int32_t>& slots, std::vector<int32_t>& status)
+{
+    const int world = (int)sh.size();
+    std::vector<int32_t> st(slots.size() / world);
+    for (int r = 0; r < world; ++r) {
+        sh[r].st.download(st.data(), sizeof(int32_t) * st.size());
+        scatter_slots(slots, world, r, st.data(), status.data());
+    }
+}
+
+// The one exchange.  lf / lc: per device the depth [S][m] and colour [S][3m] grids of its slots, already enqueued.  The partition goes to
+// the communicators, ONE bracket holds the all-gather of both (one fused exchange), device 0 un-permutes to patch order and the host
+// gets f* [P][m] and c* [P][3m].
+void gather_grids(const std::vector<gpc_ctx*>& ctx, const std::vector<gpc_comm*>& comm, const std::vector<int32_t>& slots, int P, int m,
+                  const std::vector<dev_buf>& lf, const std::vector<dev_buf>& lc, std::vector<double>& f_star, std::vector<double>& c_star)
+{
+    const int world = (int)ctx.size();
+    const size_t row = sizeof(double) * (size_t)m;
+    std::vector<dev_buf> gf, gc;
+    for (gpc_ctx* c : ctx) {
+        gf.emplace_back(c, slots.size() * row);
+        gc.emplace_back(c, slots.size() * 3 * row);
+    }
+    dev_buf f(ctx[0], P * row), c(ctx[0], P * 3 * row);
+    sync_shards sync{ctx};
+    for (int r = 0; r < world; ++r) check(gpc_comm_set_partition(comm[r], P, slots.data()), ctx[r], "gpc_comm_set_partition");
+    rccl_group group(ctx[0]);
+    for (int r = 0; r < world; ++r) {
+        check(gpc_allgather_fstar_dev(comm[r], m, lf[r].as<const double>(), gf[r].as<double>(), nullptr), ctx[r], "all-gather f*");
+        check(gpc_allgather_fstar_dev(comm[r], 3 * m, lc[r].as<const double>(), gc[r].as<double>(), nullptr), ctx[r], "all-gather c*");
+    }
+    group.end();
+    check(gpc_unpermute_fstar_dev(comm[0], m, gf[0].as<const double>(), f.as<double>()), ctx[0], "un-permute f*");
+    check(gpc_unpermute_fstar_dev(comm[0], 3 * m, gc[0].as<const double>(), c.as<double>()), ctx[0], "un-permute c*");
+    f_star.assign((size_t)P * m, 0.0);
+    c_star.assign((size_t)P * 3 * m, 0.0);
+    f.download(f_star.data(), P * row);
+    c.download(c_star.data(), P * 3 * row);
+}
+
+pointcloud to_cloud(const std::vector<gpc_point_xyzrgb>& recs)
+{
+    pointcloud out(recs.size());
+    for (size_t q = 0; q < recs.size(); ++q) out[q] = point{recs[q].x, recs[q].y, recs[q].z, recs[q].r, recs[q].g, recs[q].b};
+    return out;
+}
+
 }  // namespace
 
-gp_compressor::gp_compressor(const pointcloud& ncloud, double res, int sz, gp_model model, int device)
-    : rng([] { return std::rand(); }), cloud_(ncloud), res_(res), sz_(sz), model_(model), device_(device)
+gp_compressor::gp_compressor(double res, int sz, int device)
+    : rng([] { return std::rand(); }), res_(res), sz_(sz), model_(gp_model::sparse), device_(device)
 {
     gpc_default_params_sparse(&depth_params, 1);
     gpc_default_params_sparse(&rgb_params, 3);
     gpc_default_params_dense(&dense_params);
 }
 
+gp_compressor::gp_compressor(const pointcloud& ncloud, double res, int sz, gp_model model, int device) : gp_compressor(res, sz, device)
+{
+    cloud_ = ncloud;
+    model_ = model;
+}
+
 void gp_compressor::release_device()
 {
     if (dev_patches_) { gpc_patches_destroy(dev_patches_); dev_patches_ = nullptr; }
+    drop_dense_grids();
+}
+
+void gp_compressor::drop_dense_grids()
+{
     if (ctx_) {
         if (d_dense_f_) (void)gpc_dev_free(ctx_, d_dense_f_);
         if (d_dense_c_) (void)gpc_dev_free(ctx_, d_dense_c_);
@@ -159,15 +326,13 @@ void gp_compressor::init_shards()
 // patch order, as train_processes() drew them.
 void gp_compressor::train_sparse_sharded(const std::vector<int32_t>& perm_d, const std::vector<int32_t>& perm_c)
 {
-    const int P = batch_.patches(), world = (int)devices_.size();
+    const int world = (int)devices_.size();
     init_shards();
-    const int S = (P + world - 1) / world;
     if (shard_slots_.empty()) {
         // built in locals and committed to the members only when every create has succeeded (as init_shards() does): a create that
         // throws midway must not leave shard_slots_ filled beside half-created GPs
-        std::vector<int32_t> slots((size_t)S * world, -1);
-        check(gpc_partition_patches(P, batch_.off.data(), world, depth_params.capacity > 0 ? depth_params.capacity : 1, slots.data()),
-              nullptr, "gpc_partition_patches");
+        std::vector<int32_t> slots = deal_patches(batch_, world, sparse_cost(depth_params));
+        const int S = (int)slots.size() / world;
         std::vector<gpc_sparse*> gps(world, nullptr), rgb(world, nullptr);
         try {
             for (int r = 0; r < world; ++r) {
@@ -185,271 +350,91 @@ void gp_compressor::train_sparse_sharded(const std::vector<int32_t>& perm_d, con
         shard_gps_.swap(gps);
         shard_rgb_.swap(rgb);
     }
-    const size_t N = batch_.x0.size();
-    struct Shard {
-        std::vector<int32_t> off, pd, pc;
-        std::vector<double> x0, x1, y, rgb;
-        int n_max = 0;
-        void *d_off = nullptr, *d_x0 = nullptr, *d_x1 = nullptr, *d_y = nullptr, *d_rgb = nullptr, *d_pd = nullptr, *d_pc = nullptr, *d_st = nullptr;
-    };
-    std::vector<Shard> sh(world);
-    auto free_all = [&]() {
-        for (int r = 0; r < world; ++r) {
-            (void)gpc_ctx_synchronize(shard_ctx_[r]);
-            for (void* q : {sh[r].d_off, sh[r].d_x0, sh[r].d_x1, sh[r].d_y, sh[r].d_rgb, sh[r].d_pd, sh[r].d_pc, sh[r].d_st})
-                if (q) (void)gpc_dev_free(shard_ctx_[r], q);
-        }
-    };
-    try {
-        for (int r = 0; r < world; ++r) {
-            Shard& s = sh[r];
-            gpc_ctx* c = shard_ctx_[r];
-            s.off.assign(S + 1, 0);
-            for (int q = 0; q < S; ++q) {
-                const int p = shard_slots_[(size_t)r * S + q];
-                const int n = p >= 0 ? batch_.off[p + 1] - batch_.off[p] : 0;
-                s.off[q + 1] = s.off[q] + n;
-                s.n_max = std::max(s.n_max, n);
-            }
-            const size_t Nl = (size_t)s.off[S];
-            s.x0.resize(Nl); s.x1.resize(Nl); s.y.resize(Nl); s.rgb.resize(3 * Nl); s.pd.resize(Nl); s.pc.resize(Nl);
-            for (int q = 0; q < S; ++q) {
-                const int p = shard_slots_[(size_t)r * S + q];
-                if (p < 0) continue;
-                const size_t o = (size_t)batch_.off[p], n = (size_t)(batch_.off[p + 1] - batch_.off[p]), lo = (size_t)s.off[q];
-                std::copy_n(&batch_.x0[o], n, &s.x0[lo]);
-                std::copy_n(&batch_.x1[o], n, &s.x1[lo]);
-                std::copy_n(&batch_.y[o], n, &s.y[lo]);
-                std::copy_n(&perm_d[o], n, &s.pd[lo]);            // patch-local indices: they travel with the patch
-                std::copy_n(&perm_c[o], n, &s.pc[lo]);
-                for (int a = 0; a < 3; ++a) std::copy_n(&batch_.rgb[a * N + o], n, &s.rgb[a * Nl + lo]);
-            }
-            auto up = [&](void** d, const void* h, size_t bytes) {
-                check(gpc_dev_malloc(c, bytes ? bytes : 8, d), c, "gpc_dev_malloc (shard)");
-                if (bytes) check(gpc_dev_memcpy(c, *d, h, bytes, GPC_COPY_H2D), c, "gpc_dev_memcpy (shard)");
-            };
-            up(&s.d_off, s.off.data(), sizeof(int32_t) * (size_t)(S + 1));
-            up(&s.d_x0, s.x0.data(), 8 * Nl);
-            up(&s.d_x1, s.x1.data(), 8 * Nl);
-            up(&s.d_y, s.y.data(), 8 * Nl);
-            up(&s.d_rgb, s.rgb.data(), 24 * Nl);
-            up(&s.d_pd, s.pd.data(), 4 * Nl);
-            up(&s.d_pc, s.pc.data(), 4 * Nl);
-            check(gpc_dev_malloc(c, sizeof(int32_t) * (size_t)S, &s.d_st), c, "gpc_dev_malloc");
-        }
-        // the add calls only enqueue: the devices run side by side
-        for (int r = 0; r < world; ++r) {
-            Shard& s = sh[r];
-            check(gpc_sparse_add_dev(shard_gps_[r], (const int32_t*)s.d_off, s.n_max, s.off[S], (const double*)s.d_x0, (const double*)s.d_x1,
-                                     (const double*)s.d_y, (const int32_t*)s.d_pd, (int32_t*)s.d_st), shard_ctx_[r], "gpc_sparse_add_dev (shard, depth)");
-            check(gpc_sparse_add_dev(shard_rgb_[r], (const int32_t*)s.d_off, s.n_max, s.off[S], (const double*)s.d_x0, (const double*)s.d_x1,
-                                     (const double*)s.d_rgb, (const int32_t*)s.d_pc, (int32_t*)s.d_st), shard_ctx_[r], "gpc_sparse_add_dev (shard, rgb)");
-        }
-        std::vector<int32_t> st(S);
-        for (int r = 0; r < world; ++r) {
-            check(gpc_dev_memcpy(shard_ctx_[r], st.data(), sh[r].d_st, sizeof(int32_t) * (size_t)S, GPC_COPY_D2H), shard_ctx_[r], "download status");
-            for (int q = 0; q < S; ++q) {
-                const int p = shard_slots_[(size_t)r * S + q];
-                if (p >= 0) status_[p] = st[q];
-            }
-        }
-    } catch (...) {
-        free_all();
-        throw;
+    std::vector<dev_shard> sh;
+    sync_shards sync{shard_ctx_};
+    for (int r = 0; r < world; ++r) sh.emplace_back(shard_ctx_[r], cut_shard(batch_, shard_slots_, world, r, perm_d.data(), perm_c.data()));
+    // the add calls only enqueue: the devices run side by side
+    for (int r = 0; r < world; ++r) {
+        const dev_shard& s = sh[r];
+        check(gpc_sparse_add_dev(shard_gps_[r], s.off.as<int32_t>(), s.h.n_max, s.h.off.back(), s.x0.as<double>(), s.x1.as<double>(),
+                                 s.y.as<double>(), s.pd.as<int32_t>(), s.st.as<int32_t>()), shard_ctx_[r], "gpc_sparse_add_dev (shard, depth)");
+        check(gpc_sparse_add_dev(shard_rgb_[r], s.off.as<int32_t>(), s.h.n_max, s.h.off.back(), s.x0.as<double>(), s.x1.as<double>(),
+                                 s.rgb.as<double>(), s.pc.as<int32_t>(), s.st.as<int32_t>()), shard_ctx_[r], "gpc_sparse_add_dev (shard, rgb)");
     }
-    free_all();
+    fetch_status(sh, shard_slots_, status_);
+}
+
+// basis sizes of the sharded sparse model, slot by slot into patch order
+std::vector<int32_t> gp_compressor::shard_basis_sizes() const
+{
+    const int world = (int)devices_.size();
+    std::vector<int32_t> bv(batch_.patches(), 0), sz_slot(shard_slots_.size() / world);
+    for (int r = 0; r < world; ++r) {
+        check(gpc_sparse_sizes(shard_gps_[r], sz_slot.data()), shard_ctx_[r], "gpc_sparse_sizes (shard)");
+        scatter_slots(shard_slots_, world, r, sz_slot.data(), bv.data());
+    }
+    return bv;
 }
 
 // load_compressed() of the sharded sparse model: every device predicts the grids of its slots, ONE grouped all-gather of the depth and
-// the colour grids reassembles them on device 0 in patch order; basis sizes come back slot by slot.
+// the colour grids reassembles them on device 0 in patch order.
 void gp_compressor::predict_sparse_sharded(const std::vector<double>& xs0, const std::vector<double>& xs1, std::vector<double>& f_star,
-                                           std::vector<double>& c_star, std::vector<int32_t>& bv)
+                                           std::vector<double>& c_star)
 {
-    const int P = batch_.patches(), m = sz_ * sz_, world = (int)devices_.size();
-    const int S = (P + world - 1) / world;
-    struct Buf { void *xs0 = nullptr, *xs1 = nullptr, *lf = nullptr, *lc = nullptr, *gf = nullptr, *gc = nullptr, *f = nullptr, *c = nullptr; };
-    std::vector<Buf> b(world);
-    bool in_group = false;
-    auto free_all = [&]() {
-        for (int r = 0; r < world; ++r) {
-            (void)gpc_ctx_synchronize(shard_ctx_[r]);
-            for (void* q : {b[r].xs0, b[r].xs1, b[r].lf, b[r].lc, b[r].gf, b[r].gc, b[r].f, b[r].c})
-                if (q) (void)gpc_dev_free(shard_ctx_[r], q);
-        }
-    };
-    try {
-        for (int r = 0; r < world; ++r) {
-            gpc_ctx* c = shard_ctx_[r];
-            check(gpc_dev_malloc(c, 8 * (size_t)m, &b[r].xs0), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)m, &b[r].xs1), c, "gpc_dev_malloc");
-            check(gpc_dev_memcpy(c, b[r].xs0, xs0.data(), 8 * (size_t)m, GPC_COPY_H2D), c, "upload grid");
-            check(gpc_dev_memcpy(c, b[r].xs1, xs1.data(), 8 * (size_t)m, GPC_COPY_H2D), c, "upload grid");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * m, &b[r].lf), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * 3 * m, &b[r].lc), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * world * m, &b[r].gf), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * world * 3 * m, &b[r].gc), c, "gpc_dev_malloc");
-            if (r == 0) {
-                check(gpc_dev_malloc(c, 8 * (size_t)P * m, &b[r].f), c, "gpc_dev_malloc");
-                check(gpc_dev_malloc(c, 8 * (size_t)P * 3 * m, &b[r].c), c, "gpc_dev_malloc");
-            }
-            check(gpc_comm_set_partition(shard_comm_[r], P, shard_slots_.data()), c, "gpc_comm_set_partition");
-        }
-        for (int r = 0; r < world; ++r) {
-            check(gpc_sparse_predict_dev(shard_gps_[r], m, (const double*)b[r].xs0, (const double*)b[r].xs1, (double*)b[r].lf, nullptr, 0, nullptr),
-                  shard_ctx_[r], "gpc_sparse_predict_dev (shard, depth)");
-            check(gpc_sparse_predict_dev(shard_rgb_[r], m, (const double*)b[r].xs0, (const double*)b[r].xs1, (double*)b[r].lc, nullptr, 0, nullptr),
-                  shard_ctx_[r], "gpc_sparse_predict_dev (shard, rgb)");
-        }
-        check(gpc_group_start(), shard_ctx_[0], "gpc_group_start");
-        in_group = true;
-        for (int r = 0; r < world; ++r) {
-            check(gpc_allgather_fstar_dev(shard_comm_[r], m, (const double*)b[r].lf, (double*)b[r].gf, nullptr), shard_ctx_[r], "all-gather f*");
-            check(gpc_allgather_fstar_dev(shard_comm_[r], 3 * m, (const double*)b[r].lc, (double*)b[r].gc, nullptr), shard_ctx_[r], "all-gather c*");
-        }
-        in_group = false;
-        check(gpc_group_end(), shard_ctx_[0], "gpc_group_end");
-        check(gpc_unpermute_fstar_dev(shard_comm_[0], m, (const double*)b[0].gf, (double*)b[0].f), shard_ctx_[0], "un-permute f*");
-        check(gpc_unpermute_fstar_dev(shard_comm_[0], 3 * m, (const double*)b[0].gc, (double*)b[0].c), shard_ctx_[0], "un-permute c*");
-        f_star.assign((size_t)P * m, 0.0);
-        c_star.assign((size_t)P * 3 * m, 0.0);
-        check(gpc_dev_memcpy(shard_ctx_[0], f_star.data(), b[0].f, 8 * (size_t)P * m, GPC_COPY_D2H), shard_ctx_[0], "download f*");
-        check(gpc_dev_memcpy(shard_ctx_[0], c_star.data(), b[0].c, 8 * (size_t)P * 3 * m, GPC_COPY_D2H), shard_ctx_[0], "download c*");
-        std::vector<int32_t> sz_slot(S);
-        bv.assign(P, 0);
-        for (int r = 0; r < world; ++r) {
-            check(gpc_sparse_sizes(shard_gps_[r], sz_slot.data()), shard_ctx_[r], "gpc_sparse_sizes (shard)");
-            for (int q = 0; q < S; ++q) {
-                const int p = shard_slots_[(size_t)r * S + q];
-                if (p >= 0) bv[p] = sz_slot[q];
-            }
-        }
-    } catch (...) {
-        if (in_group) (void)gpc_group_end();
-        free_all();
-        throw;
+    const int world = (int)devices_.size();
+    const size_t grid = sizeof(double) * xs0.size() * (shard_slots_.size() / world);     // the depth grids of one device's slots
+    std::vector<dev_buf> d_xs0, d_xs1, lf, lc;
+    sync_shards sync{shard_ctx_};
+    for (gpc_ctx* c : shard_ctx_) {
+        d_xs0.emplace_back(c, xs0);
+        d_xs1.emplace_back(c, xs1);
+        lf.emplace_back(c, grid);
+        lc.emplace_back(c, 3 * grid);
     }
-    free_all();
+    for (int r = 0; r < world; ++r) {
+        check(gpc_sparse_predict_dev(shard_gps_[r], (int)xs0.size(), d_xs0[r].as<double>(), d_xs1[r].as<double>(), lf[r].as<double>(), nullptr, 0,
+                                     nullptr), shard_ctx_[r], "gpc_sparse_predict_dev (shard, depth)");
+        check(gpc_sparse_predict_dev(shard_rgb_[r], (int)xs0.size(), d_xs0[r].as<double>(), d_xs1[r].as<double>(), lc[r].as<double>(), nullptr, 0,
+                                     nullptr), shard_ctx_[r], "gpc_sparse_predict_dev (shard, rgb)");
+    }
+    gather_grids(shard_ctx_, shard_comm_, shard_slots_, batch_.patches(), (int)xs0.size(), lf, lc, f_star, c_star);
 }
 
 // The dense model over several GPUs: the batched form of "patches shard embarrassingly, one all-gather reassembles the
 // decompressed cloud" (BASELINE north_star; patches are independent, src/gp_compressor.cpp:146-163).
 void gp_compressor::train_dense_sharded()
 {
-    const int P = batch_.patches(), m = sz_ * sz_, world = (int)devices_.size();
+    const int m = sz_ * sz_, world = (int)devices_.size();
     init_shards();
-    const int S = (P + world - 1) / world;
-    std::vector<int32_t> slots((size_t)S * world);
-    check(gpc_partition_patches(P, batch_.off.data(), world, 0, slots.data()), nullptr, "gpc_partition_patches");
-    const size_t N = batch_.x0.size();
-    struct Shard {
-        std::vector<int32_t> off;
-        std::vector<double> x0, x1, y, rgb;
-        int n_max = 0;
-        void *d_off = nullptr, *d_x0 = nullptr, *d_x1 = nullptr, *d_y = nullptr, *d_rgb = nullptr, *d_st = nullptr;
-        void *d_lf = nullptr, *d_lc = nullptr, *d_gf = nullptr, *d_gc = nullptr, *d_f = nullptr, *d_c = nullptr;
-    };
-    std::vector<Shard> sh(world);
-    bool in_group = false;                    // an RCCL group left open would swallow every later collective of the process
-    auto free_all = [&]() {
-        for (int r = 0; r < world; ++r)
-            for (void* q : {sh[r].d_off, sh[r].d_x0, sh[r].d_x1, sh[r].d_y, sh[r].d_rgb, sh[r].d_st, sh[r].d_lf, sh[r].d_lc, sh[r].d_gf,
-                            sh[r].d_gc, sh[r].d_f, sh[r].d_c})
-                if (q) (void)gpc_dev_free(shard_ctx_[r], q);
-    };
-    try {
-        for (int r = 0; r < world; ++r) {
-            Shard& s = sh[r];
-            gpc_ctx* c = shard_ctx_[r];
-            // this device's slots as a CSR batch (padding slots are empty patches)
-            s.off.assign(S + 1, 0);
-            for (int q = 0; q < S; ++q) {
-                const int p = slots[(size_t)r * S + q];
-                const int n = p >= 0 ? batch_.off[p + 1] - batch_.off[p] : 0;
-                s.off[q + 1] = s.off[q] + n;
-                s.n_max = std::max(s.n_max, n);
-            }
-            const size_t Nl = (size_t)s.off[S];
-            s.x0.resize(Nl); s.x1.resize(Nl); s.y.resize(Nl); s.rgb.resize(3 * Nl);
-            for (int q = 0; q < S; ++q) {
-                const int p = slots[(size_t)r * S + q];
-                if (p < 0) continue;
-                const size_t o = (size_t)batch_.off[p], n = (size_t)(batch_.off[p + 1] - batch_.off[p]), lo = (size_t)s.off[q];
-                std::copy_n(&batch_.x0[o], n, &s.x0[lo]);
-                std::copy_n(&batch_.x1[o], n, &s.x1[lo]);
-                std::copy_n(&batch_.y[o], n, &s.y[lo]);
-                for (int a = 0; a < 3; ++a) std::copy_n(&batch_.rgb[a * N + o], n, &s.rgb[a * Nl + lo]);
-            }
-            auto up = [&](void** d, const void* h, size_t bytes) {
-                check(gpc_dev_malloc(c, bytes, d), c, "gpc_dev_malloc (shard)");
-                if (bytes) check(gpc_dev_memcpy(c, *d, h, bytes, GPC_COPY_H2D), c, "gpc_dev_memcpy (shard)");
-            };
-            up(&s.d_off, s.off.data(), sizeof(int32_t) * (size_t)(S + 1));
-            up(&s.d_x0, s.x0.data(), 8 * Nl);
-            up(&s.d_x1, s.x1.data(), 8 * Nl);
-            up(&s.d_y, s.y.data(), 8 * Nl);
-            up(&s.d_rgb, s.rgb.data(), 24 * Nl);
-            check(gpc_dev_malloc(c, sizeof(int32_t) * (size_t)S, &s.d_st), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * m, &s.d_lf), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * 3 * m, &s.d_lc), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * world * m, &s.d_gf), c, "gpc_dev_malloc");
-            check(gpc_dev_malloc(c, 8 * (size_t)S * world * 3 * m, &s.d_gc), c, "gpc_dev_malloc");
-            if (r == 0) {
-                check(gpc_dev_malloc(c, 8 * (size_t)P * m, &s.d_f), c, "gpc_dev_malloc");
-                check(gpc_dev_malloc(c, 8 * (size_t)P * 3 * m, &s.d_c), c, "gpc_dev_malloc");
-            }
-            check(gpc_comm_set_partition(shard_comm_[r], P, slots.data()), c, "gpc_comm_set_partition");
-        }
-        // every device fits + predicts its slots: the launches only enqueue, so the devices run concurrently
-        for (int r = 0; r < world; ++r) {
-            Shard& s = sh[r];
-            gpc_ctx* c = shard_ctx_[r];
-            check(gpc_dense_fit_predict_grid_dev(c, &dense_params, S, (const int32_t*)s.d_off, s.n_max, s.off[S], (const double*)s.d_x0,
-                                                 (const double*)s.d_x1, (const double*)s.d_y, 1, res_, sz_, (double*)s.d_lf, nullptr,
-                                                 (int32_t*)s.d_st), c, "gpc_dense_fit_predict_grid_dev (shard, depth)");
-            check(gpc_dense_fit_predict_grid_dev(c, &dense_params, S, (const int32_t*)s.d_off, s.n_max, s.off[S], (const double*)s.d_x0,
-                                                 (const double*)s.d_x1, (const double*)s.d_rgb, 3, res_, sz_, (double*)s.d_lc, nullptr,
-                                                 nullptr), c, "gpc_dense_fit_predict_grid_dev (shard, rgb)");
-        }
-        // the one exchange: all-gather of the depth grids and of the colour grids (inside one bracket: one fused exchange)
-        check(gpc_group_start(), shard_ctx_[0], "gpc_group_start");
-        in_group = true;
-        for (int r = 0; r < world; ++r) {
-            check(gpc_allgather_fstar_dev(shard_comm_[r], m, (const double*)sh[r].d_lf, (double*)sh[r].d_gf, nullptr), shard_ctx_[r], "all-gather f*");
-            check(gpc_allgather_fstar_dev(shard_comm_[r], 3 * m, (const double*)sh[r].d_lc, (double*)sh[r].d_gc, nullptr), shard_ctx_[r], "all-gather c*");
-        }
-        in_group = false;
-        check(gpc_group_end(), shard_ctx_[0], "gpc_group_end");
-        // device 0 un-permutes to patch order and hands the grids to the host flow (load_compressed reprojects them)
-        check(gpc_unpermute_fstar_dev(shard_comm_[0], m, (const double*)sh[0].d_gf, (double*)sh[0].d_f), shard_ctx_[0], "un-permute f*");
-        check(gpc_unpermute_fstar_dev(shard_comm_[0], 3 * m, (const double*)sh[0].d_gc, (double*)sh[0].d_c), shard_ctx_[0], "un-permute c*");
-        dense_f_.assign((size_t)P * m, 0.0);
-        dense_c_.assign((size_t)P * 3 * m, 0.0);
-        check(gpc_dev_memcpy(shard_ctx_[0], dense_f_.data(), sh[0].d_f, 8 * (size_t)P * m, GPC_COPY_D2H), shard_ctx_[0], "download f*");
-        check(gpc_dev_memcpy(shard_ctx_[0], dense_c_.data(), sh[0].d_c, 8 * (size_t)P * 3 * m, GPC_COPY_D2H), shard_ctx_[0], "download c*");
-        std::vector<int32_t> st(S);
-        for (int r = 0; r < world; ++r) {
-            check(gpc_dev_memcpy(shard_ctx_[r], st.data(), sh[r].d_st, sizeof(int32_t) * (size_t)S, GPC_COPY_D2H), shard_ctx_[r], "download status");
-            for (int q = 0; q < S; ++q) {
-                const int p = slots[(size_t)r * S + q];
-                if (p >= 0) status_[p] = st[q];
-            }
-        }
-        for (int r = 0; r < world; ++r) check(gpc_ctx_synchronize(shard_ctx_[r]), shard_ctx_[r], "gpc_ctx_synchronize");
-    } catch (...) {
-        if (in_group) (void)gpc_group_end();
-        for (int r = 0; r < world; ++r) (void)gpc_ctx_synchronize(shard_ctx_[r]);    // nothing may still read the buffers freed below
-        free_all();
-        throw;
+    const std::vector<int32_t> slots = deal_patches(batch_, world, 0);
+    const int S = (int)slots.size() / world;
+    std::vector<dev_shard> sh;
+    std::vector<dev_buf> lf, lc;
+    sync_shards sync{shard_ctx_};
+    for (int r = 0; r < world; ++r) {
+        sh.emplace_back(shard_ctx_[r], cut_shard(batch_, slots, world, r));
+        lf.emplace_back(shard_ctx_[r], sizeof(double) * (size_t)S * m);
+        lc.emplace_back(shard_ctx_[r], sizeof(double) * (size_t)S * 3 * m);
     }
-    free_all();
+    // every device fits + predicts its slots: the launches only enqueue, so the devices run concurrently
+    for (int r = 0; r < world; ++r) {
+        const dev_shard& s = sh[r];
+        gpc_ctx* c = shard_ctx_[r];
+        check(gpc_dense_fit_predict_grid_dev(c, &dense_params, S, s.off.as<int32_t>(), s.h.n_max, s.h.off.back(), s.x0.as<double>(),
+                                             s.x1.as<double>(), s.y.as<double>(), 1, res_, sz_, lf[r].as<double>(), nullptr,
+                                             s.st.as<int32_t>()), c, "gpc_dense_fit_predict_grid_dev (shard, depth)");
+        check(gpc_dense_fit_predict_grid_dev(c, &dense_params, S, s.off.as<int32_t>(), s.h.n_max, s.h.off.back(), s.x0.as<double>(),
+                                             s.x1.as<double>(), s.rgb.as<double>(), 3, res_, sz_, lc[r].as<double>(), nullptr, nullptr),
+              c, "gpc_dense_fit_predict_grid_dev (shard, rgb)");
+    }
+    // device 0 hands the grids to the host flow (load_compressed reprojects them)
+    gather_grids(shard_ctx_, shard_comm_, slots, batch_.patches(), m, lf, lc, dense_f_, dense_c_);
+    fetch_status(sh, slots, status_);
 }
 
 gp_compressor::~gp_compressor()
 {
-    for (gpc_sparse* q : shard_gps_) if (q) gpc_sparse_destroy(q);
-    for (gpc_sparse* q : shard_rgb_) if (q) gpc_sparse_destroy(q);
-    for (gpc_comm* c : shard_comm_) gpc_comm_destroy(c);
-    for (gpc_ctx* c : shard_ctx_) gpc_ctx_destroy(c);
+    set_devices({});          // the shard GPs, communicators and contexts
     release_device();
     if (gps_) gpc_sparse_destroy(gps_);
     if (rgb_gps_) gpc_sparse_destroy(rgb_gps_);
@@ -660,35 +645,19 @@ void gp_compressor::train_processes()
     gpc_patches_view dv{};
     const bool on_device = dev_patches_ != nullptr;
     if (on_device) gpc_patches_view_dev(dev_patches_, &dv);
-    if (model_ == gp_model::dense && on_device) {
-        // depth and colour grids predicted straight from the device batch; they stay in HBM for load_compressed()
-        void* d_st = nullptr;
-        if (d_dense_f_) { (void)gpc_dev_free(ctx_, d_dense_f_); d_dense_f_ = nullptr; }
-        if (d_dense_c_) { (void)gpc_dev_free(ctx_, d_dense_c_); d_dense_c_ = nullptr; }
-        check(gpc_dev_malloc(ctx_, sizeof(double) * (size_t)P * m, (void**)&d_dense_f_), ctx_, "gpc_dev_malloc");
-        check(gpc_dev_malloc(ctx_, sizeof(double) * (size_t)P * 3 * m, (void**)&d_dense_c_), ctx_, "gpc_dev_malloc");
-        check(gpc_dev_malloc(ctx_, sizeof(int32_t) * (size_t)P, &d_st), ctx_, "gpc_dev_malloc");
-        int rc = gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.y, 1, res_, sz_,
-                                                d_dense_f_, nullptr, (int32_t*)d_st);
-        if (rc == GPC_OK)
-            rc = gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.rgb, 3, res_, sz_,
-                                                d_dense_c_, nullptr, (int32_t*)d_st);
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, status_.data(), d_st, sizeof(int32_t) * (size_t)P, GPC_COPY_D2H);
-        (void)gpc_dev_free(ctx_, d_st);
-        check(rc, ctx_, "gpc_dense_fit_predict_grid_dev");
-        mean_added_ = 0;
-        max_added_ = 0;
-        for (int i = 0; i < P; ++i) {
-            const int n = batch_.off[i + 1] - batch_.off[i];
-            mean_added_ += n;
-            max_added_ = std::max(max_added_, n);
-        }
-        mean_added_ /= P;
-        trained_ = true;
-        return;
-    }
     if (model_ == gp_model::dense) {
-        if (!devices_.empty()) {
+        if (on_device) {
+            // depth and colour grids predicted straight from the device batch; they stay in HBM for load_compressed()
+            drop_dense_grids();
+            dev_buf f(ctx_, sizeof(double) * (size_t)P * m), c(ctx_, sizeof(double) * (size_t)P * 3 * m), st(ctx_, sizeof(int32_t) * (size_t)P);
+            check(gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.y, 1, res_, sz_,
+                                                 f.as<double>(), nullptr, st.as<int32_t>()), ctx_, "gpc_dense_fit_predict_grid_dev(depth)");
+            check(gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.rgb, 3, res_, sz_,
+                                                 c.as<double>(), nullptr, st.as<int32_t>()), ctx_, "gpc_dense_fit_predict_grid_dev(rgb)");
+            st.download(status_.data(), sizeof(int32_t) * (size_t)P);
+            d_dense_f_ = f.release<double>();         // kept only once both grids exist
+            d_dense_c_ = c.release<double>();
+        } else if (!devices_.empty()) {
             train_dense_sharded();
         } else {
             dense_f_.assign((size_t)P * m, 0.0);
@@ -728,22 +697,12 @@ void gp_compressor::train_processes()
         train_sparse_sharded(perm_d, perm_c);
     } else if (on_device) {
         // the points are already in HBM: only the two insertion orders go up
-        const size_t N = (size_t)dv.n_total;
-        void *d_pd = nullptr, *d_pc = nullptr, *d_st = nullptr;
-        check(gpc_dev_malloc(ctx_, sizeof(int32_t) * N, &d_pd), ctx_, "gpc_dev_malloc");
-        check(gpc_dev_malloc(ctx_, sizeof(int32_t) * N, &d_pc), ctx_, "gpc_dev_malloc");
-        check(gpc_dev_malloc(ctx_, sizeof(int32_t) * (size_t)P, &d_st), ctx_, "gpc_dev_malloc");
-        int rc = gpc_dev_memcpy(ctx_, d_pd, perm_d.data(), sizeof(int32_t) * N, GPC_COPY_H2D);
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, d_pc, perm_c.data(), sizeof(int32_t) * N, GPC_COPY_H2D);
-        if (rc == GPC_OK)
-            rc = gpc_sparse_add_dev(gps_, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.y, (const int32_t*)d_pd, (int32_t*)d_st);
-        if (rc == GPC_OK)
-            rc = gpc_sparse_add_dev(rgb_gps_, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.rgb, (const int32_t*)d_pc, (int32_t*)d_st);
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, status_.data(), d_st, sizeof(int32_t) * (size_t)P, GPC_COPY_D2H);
-        (void)gpc_dev_free(ctx_, d_pd);
-        (void)gpc_dev_free(ctx_, d_pc);
-        (void)gpc_dev_free(ctx_, d_st);
-        check(rc, ctx_, "gpc_sparse_add_dev");
+        dev_buf pd(ctx_, perm_d), pc(ctx_, perm_c), st(ctx_, sizeof(int32_t) * (size_t)P);
+        check(gpc_sparse_add_dev(gps_, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.y, pd.as<int32_t>(), st.as<int32_t>()),
+              ctx_, "gpc_sparse_add_dev(depth)");
+        check(gpc_sparse_add_dev(rgb_gps_, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.rgb, pc.as<int32_t>(), st.as<int32_t>()),
+              ctx_, "gpc_sparse_add_dev(rgb)");
+        st.download(status_.data(), sizeof(int32_t) * (size_t)P);
     } else {
         check(gpc_sparse_add(gps_, batch_.off.data(), batch_.x0.data(), batch_.x1.data(), batch_.y.data(), perm_d.data(),
                              status_.data()), ctx_, "gpc_sparse_add(depth)");
@@ -751,17 +710,8 @@ void gp_compressor::train_processes()
                              status_.data()), ctx_, "gpc_sparse_add(rgb)");
     }
     std::vector<int32_t> bv(P, 0);
-    if (sharded) {
-        const int world = (int)devices_.size(), S = (P + world - 1) / world;
-        std::vector<int32_t> sz_slot(S);
-        for (int r = 0; r < world; ++r) {
-            check(gpc_sparse_sizes(shard_gps_[r], sz_slot.data()), shard_ctx_[r], "gpc_sparse_sizes (shard)");
-            for (int q = 0; q < S; ++q)
-                if (shard_slots_[(size_t)r * S + q] >= 0) bv[shard_slots_[(size_t)r * S + q]] = sz_slot[q];
-        }
-    } else {
-        check(gpc_sparse_sizes(gps_, bv.data()), ctx_, "gpc_sparse_sizes");
-    }
+    if (sharded) bv = shard_basis_sizes();
+    else check(gpc_sparse_sizes(gps_, bv.data()), ctx_, "gpc_sparse_sizes");
     double mean = 0, added = 0;                  // "Mean added" / "Max added" (:164-168, 173-174)
     int maxm = 0;
     for (int i = 0; i < P; ++i) {
@@ -795,11 +745,9 @@ void gp_compressor::flatten_colors(uint8_t out[3], const double c[3])
 // src/gp_compressor.cpp:267-386
 pointcloud gp_compressor::load_compressed()
 {
-    pointcloud out;
-    if (!trained_) return out;
     const int P = batch_.patches();
     const int m = sz_ * sz_;
-    if (P == 0) return out;
+    if (!trained_ || P == 0) return {};
     std::vector<double> xs0(m), xs1(m);
     int pcount = 0;
     for (int y = 0; y < sz_; ++y)                     // :320-331, y outer / x inner
@@ -815,38 +763,26 @@ pointcloud gp_compressor::load_compressed()
         std::vector<int32_t> bvh(P, 1);
         if (model_ == gp_model::dense) for (int i = 0; i < P; ++i) bvh[i] = batch_.off[i + 1] - batch_.off[i];
         else check(gpc_sparse_sizes(gps_, bvh.data()), ctx_, "gpc_sparse_sizes");
-        void *d_xs0 = nullptr, *d_xs1 = nullptr, *d_bv = nullptr, *d_f = nullptr, *d_c = nullptr, *d_rec = nullptr, *d_n = nullptr;
-        auto free_all = [&]() { for (void* q : {d_xs0, d_xs1, d_bv, d_rec, d_n}) if (q) (void)gpc_dev_free(ctx_, q);
-                                if (model_ != gp_model::dense) { if (d_f) (void)gpc_dev_free(ctx_, d_f); if (d_c) (void)gpc_dev_free(ctx_, d_c); } };
-        int rc = gpc_dev_malloc(ctx_, 8 * (size_t)m, &d_xs0);
-        if (rc == GPC_OK) rc = gpc_dev_malloc(ctx_, 8 * (size_t)m, &d_xs1);
-        if (rc == GPC_OK) rc = gpc_dev_malloc(ctx_, 4 * (size_t)P, &d_bv);
-        if (rc == GPC_OK) rc = gpc_dev_malloc(ctx_, sizeof(gpc_point_xyzrgb) * (size_t)P * m, &d_rec);
-        if (rc == GPC_OK) rc = gpc_dev_malloc(ctx_, 4, &d_n);
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, d_xs0, xs0.data(), 8 * (size_t)m, GPC_COPY_H2D);
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, d_xs1, xs1.data(), 8 * (size_t)m, GPC_COPY_H2D);
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, d_bv, bvh.data(), 4 * (size_t)P, GPC_COPY_H2D);
-        if (model_ == gp_model::dense) {
-            d_f = d_dense_f_;
-            d_c = d_dense_c_;
-        } else {
-            if (rc == GPC_OK) rc = gpc_dev_malloc(ctx_, 8 * (size_t)P * m, &d_f);
-            if (rc == GPC_OK) rc = gpc_dev_malloc(ctx_, 8 * (size_t)P * 3 * m, &d_c);
-            if (rc == GPC_OK) rc = gpc_sparse_predict_dev(gps_, m, (const double*)d_xs0, (const double*)d_xs1, (double*)d_f, nullptr, 0, nullptr);
-            if (rc == GPC_OK) rc = gpc_sparse_predict_dev(rgb_gps_, m, (const double*)d_xs0, (const double*)d_xs1, (double*)d_c, nullptr, 0, nullptr);
+        dev_buf d_xs0(ctx_, xs0), d_xs1(ctx_, xs1), d_bv(ctx_, bvh), d_rec(ctx_, sizeof(gpc_point_xyzrgb) * (size_t)P * m), d_n(ctx_, 4);
+        dev_buf d_f, d_c;                             // sparse model: the grids predicted now; the dense model kept its own from training
+        const double *f = d_dense_f_, *c = d_dense_c_;
+        if (model_ != gp_model::dense) {
+            d_f = dev_buf(ctx_, sizeof(double) * (size_t)P * m);
+            d_c = dev_buf(ctx_, sizeof(double) * (size_t)P * 3 * m);
+            f = d_f.as<double>();
+            c = d_c.as<double>();
+            check(gpc_sparse_predict_dev(gps_, m, d_xs0.as<double>(), d_xs1.as<double>(), d_f.as<double>(), nullptr, 0, nullptr),
+                  ctx_, "gpc_sparse_predict_dev(depth)");
+            check(gpc_sparse_predict_dev(rgb_gps_, m, d_xs0.as<double>(), d_xs1.as<double>(), d_c.as<double>(), nullptr, 0, nullptr),
+                  ctx_, "gpc_sparse_predict_dev(rgb)");
         }
-        if (rc == GPC_OK)
-            rc = gpc_reproject_dev(ctx_, P, m, (const int32_t*)d_bv, (const double*)d_xs0, (const double*)d_xs1, (const double*)d_f,
-                                   (const double*)d_c, dv.rotations, dv.means, dv.rgb_means, (gpc_point_xyzrgb*)d_rec, (int32_t*)d_n);
+        check(gpc_reproject_dev(ctx_, P, m, d_bv.as<int32_t>(), d_xs0.as<double>(), d_xs1.as<double>(), f, c, dv.rotations, dv.means,
+                                dv.rgb_means, d_rec.as<gpc_point_xyzrgb>(), d_n.as<int32_t>()), ctx_, "gpc_reproject_dev");
         int32_t npts = 0;
-        if (rc == GPC_OK) rc = gpc_dev_memcpy(ctx_, &npts, d_n, 4, GPC_COPY_D2H);
-        std::vector<gpc_point_xyzrgb> recs((size_t)(rc == GPC_OK ? npts : 0));
-        if (rc == GPC_OK && npts > 0) rc = gpc_dev_memcpy(ctx_, recs.data(), d_rec, sizeof(gpc_point_xyzrgb) * (size_t)npts, GPC_COPY_D2H);
-        free_all();
-        check(rc, ctx_, "load_compressed (device)");
-        out.resize(recs.size());
-        for (size_t q = 0; q < recs.size(); ++q) out[q] = point{recs[q].x, recs[q].y, recs[q].z, recs[q].r, recs[q].g, recs[q].b};
-        return out;
+        d_n.download(&npts, 4);
+        std::vector<gpc_point_xyzrgb> recs((size_t)std::max(npts, 0));
+        d_rec.download(recs.data(), sizeof(gpc_point_xyzrgb) * recs.size());
+        return to_cloud(recs);
     }
     std::vector<double> f_star, c_star;
     std::vector<int32_t> bv(P, 1);
@@ -855,7 +791,8 @@ pointcloud gp_compressor::load_compressed()
         c_star = dense_c_;
         for (int i = 0; i < P; ++i) bv[i] = batch_.off[i + 1] - batch_.off[i];
     } else if (!devices_.empty()) {
-        predict_sparse_sharded(xs0, xs1, f_star, c_star, bv);
+        predict_sparse_sharded(xs0, xs1, f_star, c_star);
+        bv = shard_basis_sizes();
     } else {
         f_star.assign((size_t)P * m, 0.0);
         c_star.assign((size_t)P * 3 * m, 0.0);
@@ -875,9 +812,8 @@ pointcloud gp_compressor::load_compressed()
     int32_t npts = 0;
     check(gpc_reproject(ctx_, P, m, bv.data(), xs0.data(), xs1.data(), f_star.data(), c_star.data(), R.data(), mu.data(), cm.data(),
                         recs.data(), &npts), ctx_, "gpc_reproject");
-    out.resize((size_t)npts);
-    for (int q = 0; q < npts; ++q) out[q] = point{recs[q].x, recs[q].y, recs[q].z, recs[q].r, recs[q].g, recs[q].b};
-    return out;
+    recs.resize((size_t)npts);
+    return to_cloud(recs);
 }
 
 // ---- model file (row f3) ---------------------------------------------------------------------------------------------
@@ -889,14 +825,6 @@ struct file_closer { void operator()(FILE* f) const { if (f) std::fclose(f); } }
 template <class T> void wr(FILE* f, const T* p, size_t n) { if (n && std::fwrite(p, sizeof(T), n, f) != n) throw std::runtime_error("model file: write failed"); }
 template <class T> void rd(FILE* f, T* p, size_t n) { if (n && std::fread(p, sizeof(T), n, f) != n) throw std::runtime_error("model file: truncated"); }
 }  // namespace
-
-gp_compressor::gp_compressor(double res, int sz, int device)
-    : rng([] { return std::rand(); }), res_(res), sz_(sz), model_(gp_model::sparse), device_(device)
-{
-    gpc_default_params_sparse(&depth_params, 1);
-    gpc_default_params_sparse(&rgb_params, 3);
-    gpc_default_params_dense(&dense_params);
-}
 
 size_t gp_compressor::save_model(const std::string& path)
 {
@@ -994,6 +922,30 @@ gp_compressor* gp_compressor::load_model(const std::string& path, int device)
 }  // namespace gpc
 
 // ---- C doors for the Python test-suite -----------------------------------------------------------------------------
+namespace {
+int fail(const std::exception& e, char* err, int errlen)
+{
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", e.what());
+    return -1;
+}
+// out_xyz / out_rgb hold up to capacity_pts points: the count, or -2 when the cloud does not fit
+int put_cloud(const gpc::pointcloud& c, float* out_xyz, uint8_t* out_rgb, int capacity_pts)
+{
+    if ((int)c.size() > capacity_pts) return -2;
+    for (size_t i = 0; i < c.size(); ++i) {
+        out_xyz[3 * i] = c[i].x; out_xyz[3 * i + 1] = c[i].y; out_xyz[3 * i + 2] = c[i].z;
+        out_rgb[3 * i] = c[i].r; out_rgb[3 * i + 1] = c[i].g; out_rgb[3 * i + 2] = c[i].b;
+    }
+    return (int)c.size();
+}
+// the slot table of a `world`-device run as the dense (sparse == 0) or the sparse flow deals it
+std::vector<int32_t> table_of(const gpc::gp_compressor* g, int world, int sparse)
+{
+    return gpc::deal_patches(g->patches(), world, sparse ? gpc::sparse_cost(g->depth_params) : 0);
+}
+template <class T> void put(const std::vector<T>& v, T* out) { if (out && !v.empty()) std::memcpy(out, v.data(), sizeof(T) * v.size()); }
+}  // namespace
+
 extern "C" {
 
 // host-only: cut and project the patches of a cloud (no GPU needed).  Returns an opaque handle.
@@ -1030,7 +982,7 @@ int gpc_host_project(void* h)
 int gpc_host_project_device(void* h, char* err, int errlen)
 {
     try { static_cast<gpc::gp_compressor*>(h)->project_cloud_device(); return 0; }
-    catch (const std::exception& e) { if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", e.what()); return -1; }
+    catch (const std::exception& e) { return fail(e, err, errlen); }
 }
 void gpc_host_set_devices(void* h, const int* devices, int n)
 {
@@ -1069,18 +1021,12 @@ int gpc_host_roundtrip(void* h, float* out_xyz, uint8_t* out_rgb, int capacity_p
     auto* g = static_cast<gpc::gp_compressor*>(h);
     try {
         g->save_compressed("unused");
-        gpc::pointcloud c = g->load_compressed();
-        if ((int)c.size() > capacity_pts) return -2;
-        for (size_t i = 0; i < c.size(); ++i) {
-            out_xyz[3 * i] = c[i].x; out_xyz[3 * i + 1] = c[i].y; out_xyz[3 * i + 2] = c[i].z;
-            out_rgb[3 * i] = c[i].r; out_rgb[3 * i + 1] = c[i].g; out_rgb[3 * i + 2] = c[i].b;
-        }
+        const int n = put_cloud(g->load_compressed(), out_xyz, out_rgb, capacity_pts);
         if (mean_added) *mean_added = g->mean_added();
         if (max_added) *max_added = g->max_added();
-        return (int)c.size();
+        return n;
     } catch (const std::exception& e) {
-        if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
-        return -1;
+        return fail(e, err, errlen);
     }
 }
 
@@ -1090,24 +1036,50 @@ long long gpc_host_save_model(void* h, const char* path, char* err, int errlen)
     try {
         return (long long)static_cast<gpc::gp_compressor*>(h)->save_model(path);
     } catch (const std::exception& e) {
-        if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
-        return -1;
+        return fail(e, err, errlen);
     }
 }
 int gpc_host_decompress_file(const char* path, int device, float* out_xyz, uint8_t* out_rgb, int capacity_pts, char* err, int errlen)
 {
     try {
         std::unique_ptr<gpc::gp_compressor> g(gpc::gp_compressor::load_model(path, device));
-        gpc::pointcloud c = g->load_compressed();
-        if ((int)c.size() > capacity_pts) return -2;
-        for (size_t i = 0; i < c.size(); ++i) {
-            out_xyz[3 * i] = c[i].x; out_xyz[3 * i + 1] = c[i].y; out_xyz[3 * i + 2] = c[i].z;
-            out_rgb[3 * i] = c[i].r; out_rgb[3 * i + 1] = c[i].g; out_rgb[3 * i + 2] = c[i].b;
-        }
-        return (int)c.size();
+        return put_cloud(g->load_compressed(), out_xyz, out_rgb, capacity_pts);
     } catch (const std::exception& e) {
-        if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
-        return -1;
+        return fail(e, err, errlen);
+    }
+}
+
+// ---- the shard layout of the multi-GPU flows, host code only: no context is created, no device touched -------------------------------
+// Device r of a `world`-device run over the projected cloud (sparse != 0: the sparse flow's table).  sizes = {S, local points, n_max};
+// every array may be NULL (the first call asks for the sizes): slots [S], off [S + 1], x0 / x1 / y [Nl], rgb [3][Nl], and pd / pc [Nl] when
+// the insertion orders perm_d / perm_c [N] (patch order) are given.  Returns 0, or -1 with the reason in err.
+int gpc_host_shard(void* h, int world, int sparse, int r, const int32_t* perm_d, const int32_t* perm_c, int32_t sizes[3], int32_t* slots,
+                   int32_t* off, double* x0, double* x1, double* y, double* rgb, int32_t* pd, int32_t* pc, char* err, int errlen)
+{
+    try {
+        const auto* g = static_cast<gpc::gp_compressor*>(h);
+        const std::vector<int32_t> table = table_of(g, world, sparse);
+        if (r < 0 || r >= world) throw std::invalid_argument("gpc_host_shard: no such device");
+        const gpc::shard_batch s = gpc::cut_shard(g->patches(), table, world, r, perm_d, perm_c);
+        const size_t S = s.off.size() - 1;
+        sizes[0] = (int32_t)S; sizes[1] = s.off[S]; sizes[2] = s.n_max;
+        if (slots) std::copy_n(table.data() + r * S, S, slots);
+        put(s.off, off); put(s.x0, x0); put(s.x1, x1); put(s.y, y); put(s.rgb, rgb); put(s.pd, pd); put(s.pc, pc);
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// per_slot [S] of device r into per_patch [P], as the flows scatter status words and basis sizes
+int gpc_host_shard_scatter(void* h, int world, int sparse, int r, const int32_t* per_slot, int32_t* per_patch, char* err, int errlen)
+{
+    try {
+        const std::vector<int32_t> table = table_of(static_cast<gpc::gp_compressor*>(h), world, sparse);
+        if (r < 0 || r >= world) throw std::invalid_argument("gpc_host_shard_scatter: no such device");
+        gpc::scatter_slots(table, world, r, per_slot, per_patch);
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
     }
 }
 

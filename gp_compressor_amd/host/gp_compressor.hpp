@@ -126,11 +126,13 @@ protected:
     gpc_patches* dev_patches_ = nullptr;
     double *d_dense_f_ = nullptr, *d_dense_c_ = nullptr;
     void release_device();
+    void drop_dense_grids();
     void train_dense_sharded();
     void init_shards();
     void train_sparse_sharded(const std::vector<int32_t>& perm_d, const std::vector<int32_t>& perm_c);
     void predict_sparse_sharded(const std::vector<double>& xs0, const std::vector<double>& xs1, std::vector<double>& f_star,
-                                std::vector<double>& c_star, std::vector<int32_t>& bv);
+                                std::vector<double>& c_star);
+    std::vector<int32_t> shard_basis_sizes() const;
     std::vector<gpc_sparse*> shard_gps_, shard_rgb_;   // sparse model, sharded: the GPs of a device's slots
     std::vector<int32_t> shard_slots_;                 // world * S: slot -> patch (-1 padding), from gpc_partition_patches
     std::vector<int> devices_;                // set_devices(): non-empty = the sharded flow

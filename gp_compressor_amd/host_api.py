@@ -45,6 +45,8 @@ def load():
         L.gpc_host_save_model.restype = C.c_longlong
         L.gpc_host_save_model.argtypes = [vp, C.c_char_p, vp, i]
         L.gpc_host_decompress_file.argtypes = [C.c_char_p, i, vp, vp, i, vp, i]
+        L.gpc_host_shard.argtypes = [vp, i, i, i] + [vp] * 12 + [i]
+        L.gpc_host_shard_scatter.argtypes = [vp, i, i, i, vp, vp, vp, i]
         _lib = L
     return _lib
 
@@ -99,7 +101,6 @@ class GpCompressor:
 
     def roundtrip(self):
         """save_compressed("...") then load_compressed(): returns (xyz float32 (M,3), rgb uint8 (M,3), mean_added, max_added)."""
-        cap = max(1, self.L.gpc_host_patch_count(self.h)) if False else 0
         assert self.L.gpc_host_project(self.h) == 0
         cap = self.L.gpc_host_patch_count(self.h) * self.sz * self.sz
         oxyz = np.zeros((max(cap, 1), 3), dtype=np.float32)
@@ -112,6 +113,30 @@ class GpCompressor:
         if n < 0:
             raise RuntimeError(f"gp_compressor round trip failed ({n}): {err.value.decode()}")
         return oxyz[:n], orgb[:n], mean_added.value, max_added.value
+
+    def shard(self, world, r, sparse=False, perm_d=None, perm_c=None):
+        """the local batch the multi-GPU flows cut for device r of `world` (host code only; after project_cloud()): slots (S,), off (S + 1,),
+        n_max, x0 / x1 / y (Nl,), rgb (3, Nl) and, when the insertion orders are given in patch order, pd / pc (Nl,)"""
+        perms = [None if p is None else np.ascontiguousarray(p, dtype=np.int32) for p in (perm_d, perm_c)]
+        head = [self.h, world, int(bool(sparse)), r] + [None if p is None else p.ctypes.data for p in perms]
+        sizes = np.zeros(3, dtype=np.int32)
+        err = C.create_string_buffer(512)
+        if self.L.gpc_host_shard(*head, sizes.ctypes.data, *[None] * 9, C.addressof(err), 512) != 0:
+            raise RuntimeError(f"gpc_host_shard failed: {err.value.decode()}")
+        S, Nl, n_max = (int(v) for v in sizes)
+        out = dict(slots=np.zeros(S, np.int32), off=np.zeros(S + 1, np.int32), x0=np.zeros(Nl), x1=np.zeros(Nl), y=np.zeros(Nl),
+                   rgb=np.zeros((3, Nl)), pd=np.zeros(0 if perms[0] is None else Nl, np.int32), pc=np.zeros(0 if perms[1] is None else Nl, np.int32))
+        if self.L.gpc_host_shard(*head, sizes.ctypes.data, *[a.ctypes.data for a in out.values()], C.addressof(err), 512) != 0:
+            raise RuntimeError(f"gpc_host_shard failed: {err.value.decode()}")
+        return dict(out, n_max=n_max)
+
+    def shard_scatter(self, world, r, per_slot, per_patch, sparse=False):
+        """scatter device r's per-slot int32 array into the patch-ordered int32 array per_patch (in place), skipping padding slots"""
+        per_slot = np.ascontiguousarray(per_slot, dtype=np.int32)
+        assert per_patch.dtype == np.int32 and per_patch.flags.c_contiguous
+        err = C.create_string_buffer(512)
+        if self.L.gpc_host_shard_scatter(self.h, world, int(bool(sparse)), r, per_slot.ctypes.data, per_patch.ctypes.data, C.addressof(err), 512) != 0:
+            raise RuntimeError(f"gpc_host_shard_scatter failed: {err.value.decode()}")
 
 
     def save_model(self, path):
