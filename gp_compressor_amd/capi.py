@@ -96,6 +96,8 @@ PROTOTYPES = {
     "gpc_sparse_predict_dev": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "gpc_sparse_predict_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "gpc_sparse_predict_points_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gpc_sparse_predict_scattered": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "gpc_sparse_predict_scattered_dev": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "gpc_sparse_likelihood": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_likelihood_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_train_sigmaf": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp]),
@@ -120,6 +122,8 @@ PROTOTYPES = {
     "gpc_default_params_render": (None, [C.POINTER(RenderParams)]),
     "gpc_patches_render": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RenderParams), _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "gpc_patches_render_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RenderParams), _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_patches_render_attrs": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "gpc_patches_render_attrs_dev": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "gpc_camera_rays_dev": (C.c_int, [_vp, _vp, _d, _d, _d, _d, _i, _i, _vp]),
     "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
     "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
@@ -503,14 +507,19 @@ class Patches:
         back, complete on return).  depth / rgb: the map's Sparse objects (rgb None: colours 0); cells (P, m) uint8: occupancy labels,
         CELL_FREE cells let a ray through.  Returns a dict: cloud (n,) POINT_DTYPE records (device: (n, 32) uint8), counts (5,) int32 =
         rays, hits, rays that never met the grid, surface tests, tests rejected on the residual, and the outputs named in `want`:
-        leaf (n,) int32 (-1 = miss), range (n,), local (n, 3) = (f, q1, q2)."""
+        leaf (n,) int32 (-1 = miss), range (n,), local (n, 3) = (f, q1, q2); and, by render_attrs on the render's own leaf and local
+        with this origin (so that the normals face the sensor): sigma (n,), conf (n,) the 0-100 confidence form, normal (n, 3)."""
         org = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
         prm = params if params is not None else default_params_render()
         counts = np.zeros(5, dtype=np.int32)
         v = self.view
         rh = rgb.h if rgb is not None else None
         shapes = dict(leaf=((), np.int32), range=((), np.float64), local=((3,), np.float64))
+        attrs = [k for k in ("sigma", "conf", "normal") if k in want]
+        asked, want = tuple(want), [k for k in want if k not in attrs]
         assert set(want) <= set(shapes)
+        if attrs:                                          # what the attrs entry reads
+            want += [k for k in ("leaf", "local") if k not in want]
         out = {}
         if isinstance(dirs, np.ndarray):
             dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -536,8 +545,49 @@ class Patches:
         arg = lambda a: _ptr(a) if (a is not None and n) else None
         self.ctx._check(entry(self.ctx.h, self.h, depth.h, rh, arg(cells), C.byref(prm), _ptr(org), arg(dirs), n, arg(out["cloud"]),
                               arg(out.get("leaf")), arg(out.get("range")), arg(out.get("local")), _ptr(counts)))
+        if attrs:
+            first = "sigma" if "sigma" in attrs else ("conf" if "conf" in attrs else None)
+            sg, nm = self.render_attrs(out["leaf"], out["local"], depth, org, conf=first == "conf", want_sigma=first is not None,
+                                       want_normal="normal" in attrs)
+            if first:
+                out[first] = sg
+            if "normal" in attrs:
+                out["normal"] = nm
+            if "sigma" in attrs and "conf" in attrs:
+                out["conf"] = self.render_attrs(out["leaf"], out["local"], depth, org, conf=True, want_normal=False)[0]
+            for k in ("leaf", "local"):
+                if k not in asked:
+                    del out[k]
         out["counts"] = counts
         return out
+
+    def render_attrs(self, leaf, local, depth, origin=None, conf=False, want_sigma=True, want_normal=True):
+        """gpc_patches_render_attrs[_dev] on the leaf (n,) int32 and local (n, 3) float64 outputs of render (numpy arrays, or device
+        tensors: then device tensors come back, complete on return): sigma (n,) -- the depth GP's predictive sigma at the hit, or with
+        conf the 0-100 confidence form -- and normal (n, 3), the unit surface normal in the world, facing `origin` (3,) when one is
+        given.  NaN at a miss.  Returns (sigma | None, normal | None)."""
+        org = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        if isinstance(leaf, np.ndarray):
+            leaf = np.ascontiguousarray(leaf, dtype=np.int32).reshape(-1)
+            local = np.ascontiguousarray(local, dtype=np.float64).reshape(-1, 3)
+            n = len(leaf)
+            assert len(local) == n
+            sg = np.zeros(n) if want_sigma else None
+            nm = np.zeros((n, 3)) if want_normal else None
+            entry = self.lib.gpc_patches_render_attrs
+        else:
+            import torch
+            assert leaf.dtype == torch.int32 and local.dtype == torch.float64 and local.numel() == 3 * leaf.numel()
+            n = leaf.numel()
+            sg = torch.zeros(n, dtype=torch.float64, device=leaf.device) if want_sigma else None
+            nm = torch.zeros((n, 3), dtype=torch.float64, device=leaf.device) if want_normal else None
+            torch.cuda.synchronize(leaf.device)             # the buffers above were filled on torch's stream
+            entry = self.lib.gpc_patches_render_attrs_dev
+        arg = lambda a: _ptr(a) if (a is not None and n) else None
+        self.ctx._check(entry(self.ctx.h, self.h, depth.h, n, arg(leaf), arg(local), _ptr(org), int(conf), arg(sg), arg(nm)))
+        if entry is self.lib.gpc_patches_render_attrs_dev:
+            self.ctx.synchronize()
+        return sg, nm
 
     def occupancy_batch(self, cells):
         """gpc_occupancy_batch_dev: the labelled cells (device tensor (P, m) uint8) as the ragged batch the probit GP reads -- per leaf the
@@ -646,6 +696,29 @@ class Sparse:
     def predict_points_dev(self, off, n_total, x0, x1, f, sigma=None, conf=False, status=None):
         self.ctx._check(self.lib.gpc_sparse_predict_points_dev(self.h, _ptr(off), int(n_total), _ptr(x0), _ptr(x1), _ptr(f),
                                                                _ptr(sigma), int(conf), _ptr(status)))
+
+    def predict_scattered(self, patch, x0, x1, want_sigma=True, conf=False):
+        """gpc_sparse_predict_scattered: predict_measurements at (patch[i], (x0[i], x1[i])) pairs in any order -- numpy arrays of one
+        length n.  Entries whose patch is outside [0, P) are skipped (NaN).  Returns f (ny, n), sigma (n,)|None, status (P,), bit for
+        bit what predict_points gives on the entries bucketed by patch in ascending i."""
+        patch = np.ascontiguousarray(patch, dtype=np.int32)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        n = patch.shape[0]
+        assert patch.shape == x0.shape == x1.shape == (n,)
+        f = np.full((self.ny, n), np.nan)
+        s = np.full(n, np.nan) if want_sigma else None
+        st = np.full(self.P, -1, dtype=np.int32)
+        arg = lambda a: _ptr(a) if (a is not None and n) else None
+        self.ctx._check(self.lib.gpc_sparse_predict_scattered(self.h, n, arg(patch), arg(x0), arg(x1), 1, arg(f), arg(s),
+                                                              int(conf), _ptr(st)))
+        return f, s, st
+
+    def predict_scattered_dev(self, n, patch, x0, x1, stride=1, f=None, sigma=None, conf=False, status=None):
+        """gpc_sparse_predict_scattered_dev: device pointers (tensors or addresses), enqueued on the context's stream; entry i reads
+        x0[i * stride], x1[i * stride]"""
+        self.ctx._check(self.lib.gpc_sparse_predict_scattered_dev(self.h, int(n), _ptr(patch), _ptr(x0), _ptr(x1), int(stride), _ptr(f),
+                                                                  _ptr(sigma), int(conf), _ptr(status)))
 
     def likelihood(self, off, x0, x1, y, want_dx=True, want_l=True):
         """compute_derivatives + compute_likelihoods (src/sparse_gp.h:44-45) on a ragged batch: dX (N, 3), l (N)"""

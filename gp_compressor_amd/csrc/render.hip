@@ -13,6 +13,8 @@
 // The walk and frame arithmetic is compiled with contraction off (producer_internal.h); tests/render_ref.py evaluates the same
 // expressions in the same association.  The GP sums use the library's exp, which NumPy's differs from by an ulp: decisions within
 // that distance of a boundary are what the restatement's margin names.  Integer atomics (the counters) only: same inputs, same bits.
+// gpc_patches_render_attrs reads a render's leaf / local outputs again, without a walk: the depth GP's predictive sigma at the hits
+// through the scattered read-out (sp_scatter_launch, sparse_scatter.hip) and the world normal from rn_eval's gradient (rn_normal_kernel).
 #include <cmath>
 #include <cstring>
 
@@ -251,6 +253,60 @@ __global__ __launch_bounds__(PC_THREADS) void rn_camera_kernel(int width, size_t
     dirs[i * 3 + 2] = (R2 * x + R5 * y) + R8;
 }
 
+// ---- the surface normal at the hits of a render: a thread per ray, nothing is walked again ---------------------------------------------
+struct RnNormalArgs {
+    int n, P;
+    const int32_t* leaf;
+    const double *local, *R, *mean;
+    RnGp depth;
+    int has_org;                  // 0: the normal keeps the sign of the frame's first column
+    double org[3];
+    double* normal;
+};
+
+__global__ __launch_bounds__(PC_THREADS) void rn_normal_kernel(RnNormalArgs A)
+{
+    __shared__ double T[GPC_EXP_TABLE_SIZE];
+    gpc_exp_table_init(T);
+    __syncthreads();
+    const int i = blockIdx.x * PC_THREADS + threadIdx.x;
+    if (i >= A.n) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double out[3] = {nan, nan, nan};
+    const int L = A.leaf[i];
+    if (L >= 0 && L < A.P) {
+        const double* R = A.R + (size_t)L * 9;                // column-major: R[0..2] = normal
+        const double f0 = A.local[(size_t)i * 3], q1 = A.local[(size_t)i * 3 + 1], q2 = A.local[(size_t)i * 3 + 2];
+        const int b = min(A.depth.b[L], A.depth.ld);
+        double f, s1, s2;
+        rn_eval(A.depth, A.depth.alpha + (size_t)L * A.depth.ld, A.depth.BV + (size_t)L * A.depth.ld * 2, b, q1, q2, T, f, s1, s2);
+        const double fx = s1 / A.depth.l_sq, fy = s2 / A.depth.l_sq;
+        const double v1 = -fx, v2 = -fy;                      // the frame normal (1, -fx, -fy)
+        double w[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) w[a] = __dadd_rn(__dadd_rn(R[a], __dmul_rn(R[a + 3], v1)), __dmul_rn(R[a + 6], v2));
+        const double len = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+        double nr[3] = {w[0] / len, w[1] / len, w[2] / len};
+        bool ok = rn_finite(nr[0]) && rn_finite(nr[1]) && rn_finite(nr[2]);
+        if (A.has_org) {
+            const double* mu = A.mean + (size_t)L * 3;
+            double e[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {                     // the hit rule's x (reproject_kernel's association)
+                const double v = __dadd_rn(__dadd_rn(__dmul_rn(R[a], f0), __dmul_rn(R[a + 3], q1)), __dmul_rn(R[a + 6], q2));
+                e[a] = A.org[a] - __dadd_rn(v, mu[a]);
+            }
+            const double dot = (nr[0] * e[0] + nr[1] * e[1]) + nr[2] * e[2];
+            ok = ok && rn_finite(dot);
+            if (dot < 0.0) { nr[0] = -nr[0]; nr[1] = -nr[1]; nr[2] = -nr[2]; }
+        }
+        if (ok) { out[0] = nr[0]; out[1] = nr[1]; out[2] = nr[2]; }
+    }
+    A.normal[(size_t)i * 3] = out[0];
+    A.normal[(size_t)i * 3 + 1] = out[1];
+    A.normal[(size_t)i * 3 + 2] = out[2];
+}
+
 static RnGp rn_gp_of(const gpc_sparse* s)
 {
     RnGp G;
@@ -378,6 +434,70 @@ int gpc_patches_render(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* d
     st.down(range, d_range, nz);
     st.down(local, d_local, nz * 3);
     if (st.ok() && counts) memcpy(counts, got, sizeof(got));
+    return st.finish();
+}
+
+// what both attrs entries check before they touch a buffer (the caller holds ctx->mu)
+static int rn_attrs_check(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* depth, int n, const double* origin)
+{
+    if (!map || !depth) return gpc_fail(ctx, GPC_EINVAL, "map and depth must not be NULL");
+    if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "negative ray count");
+    for (int a = 0; origin && a < 3; ++a)
+        if (!std::isfinite(origin[a])) return gpc_fail(ctx, GPC_EINVAL, "the origin is not finite");
+    if (!gpc_child_listed(ctx, map) || !gpc_child_listed(ctx, depth))
+        return gpc_fail(ctx, GPC_EINVAL, "map and depth must be live objects of this context");
+    if (depth->ny != 1 || depth->P != map->v.P)
+        return gpc_fail(ctx, GPC_EINVAL, "depth must have ny == 1 and the map's P (%d), got ny %d, P %d", map->v.P, depth->ny, depth->P);
+    return GPC_OK;
+}
+
+int gpc_patches_render_attrs_dev(gpc_ctx* ctx, const gpc_patches* map, gpc_sparse* depth, int n, const int32_t* leaf, const double* local,
+                                 const double* origin, int conf, double* sigma, double* normal)
+{
+    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = rn_attrs_check(ctx, map, depth, n, origin)) return rc;
+    if (n > 0 && (!leaf || !local)) return gpc_fail(ctx, GPC_EINVAL, "leaf and local must not be NULL");
+    if (n == 0 || (!sigma && !normal)) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    if (sigma)
+        if (int rc = sp_scatter_launch(depth, n, leaf, local + 1, local + 2, 3, nullptr, sigma, conf, nullptr)) return rc;
+    if (normal) {
+        RnNormalArgs A;
+        memset(&A, 0, sizeof(A));
+        A.n = n; A.P = map->v.P;
+        A.leaf = leaf; A.local = local;
+        A.R = map->v.rotations; A.mean = map->v.means;
+        A.depth = rn_gp_of(depth);
+        A.has_org = origin ? 1 : 0;
+        for (int a = 0; origin && a < 3; ++a) A.org[a] = origin[a];
+        A.normal = normal;
+        hipLaunchKernelGGL(rn_normal_kernel, dim3((n + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, ctx->stream, A);
+        GPC_HIP(ctx, hipGetLastError());
+    }
+    return GPC_OK;
+}
+
+int gpc_patches_render_attrs(gpc_ctx* ctx, const gpc_patches* map, gpc_sparse* depth, int n, const int32_t* leaf, const double* local,
+                             const double* origin, int conf, double* sigma, double* normal)
+{
+    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (int rc = rn_attrs_check(ctx, map, depth, n, origin)) return rc;
+    }
+    if (n > 0 && (!leaf || !local)) return gpc_fail(ctx, GPC_EINVAL, "leaf and local must not be NULL");
+    if (n == 0 || (!sigma && !normal)) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)n;
+    GpcStaging st(ctx, "gpc_patches_render_attrs");
+    const int32_t* d_leaf = st.up(leaf, nz);
+    const double* d_local = st.up(local, nz * 3);
+    double *d_sigma = sigma ? st.out<double>(nz) : nullptr, *d_normal = normal ? st.out<double>(nz * 3) : nullptr;
+    if (st.ok()) st.rc = gpc_patches_render_attrs_dev(ctx, map, depth, n, d_leaf, d_local, origin, conf, d_sigma, d_normal);
+    st.down(sigma, d_sigma, nz);
+    st.down(normal, d_normal, nz * 3);
     return st.finish();
 }
 

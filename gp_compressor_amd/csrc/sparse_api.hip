@@ -220,6 +220,30 @@ int gpc_sparse_predict_points_dev(gpc_sparse* g, const int32_t* off, int n_total
     return sp_predict_launch(g, 0, off, n_total, x0, x1, f, sigma, conf, status, 4);
 }
 
+// what both scattered entries check (include/gpc.h)
+static int sp_scattered_check(gpc_ctx* ctx, int n, const int32_t* patch, const double* x0, const double* x1, int stride)
+{
+    if (n < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (stride < 1) return gpc_fail(ctx, GPC_EINVAL, "stride must be >= 1, got %d", stride);
+    if (n > 0 && (!patch || !x0 || !x1)) return gpc_fail(ctx, GPC_EINVAL, "patch/x0/x1 is NULL");
+    return GPC_OK;
+}
+
+// predict_measurements at (patch, point) pairs in any order: bucketed on the device, then the kernels of the entry above (sparse_scatter.hip)
+int gpc_sparse_predict_scattered_dev(gpc_sparse* g, int n, const int32_t* patch, const double* x0, const double* x1, int stride,
+                                     double* f, double* sigma, int conf, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_scattered_check(ctx, n, patch, x0, x1, stride)) return rc;
+    if (n == 0 && (!status || g->P == 0)) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_scatter_launch(g, n, patch, x0, x1, stride, f, sigma, conf, status);
+}
+
 int gpc_sparse_likelihood_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1,
                               const double* y, double* dX, double* l)
 {
@@ -395,6 +419,39 @@ int gpc_sparse_predict_points(gpc_sparse* g, const int32_t* off, const double* x
     st.down(f, d_f, N * ny);
     st.down(sigma, d_s, N);
     st.down(status, d_st, (size_t)P);
+    return st.finish();
+}
+
+int gpc_sparse_predict_scattered(gpc_sparse* g, int n, const int32_t* patch, const double* x0, const double* x1, int stride, double* f,
+                                 double* sigma, int conf, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_scattered_check(ctx, n, patch, x0, x1, stride)) return rc;
+    const size_t N = (size_t)n, ny = (size_t)g->ny, P = (size_t)g->P;
+    if (n == 0 && (!status || P == 0)) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_predict_scattered");
+    const int32_t* d_patch = st.up(patch, N);
+    // entry i reads x[i * stride]: (n - 1) * stride + 1 doubles each; interleaved coordinates (x1 inside the first stride of x0) go up once
+    const size_t span = N ? (N - 1) * (size_t)stride + 1 : 0;
+    const uintptr_t a0 = (uintptr_t)x0, a1 = (uintptr_t)x1;
+    const size_t gap = (N && a1 >= a0 && (a1 - a0) % sizeof(double) == 0) ? (size_t)(a1 - a0) / sizeof(double) : (size_t)stride;
+    const double *d_x0, *d_x1;
+    if (gap < (size_t)stride) {
+        d_x0 = st.up(x0, span + gap);
+        d_x1 = d_x0 ? d_x0 + gap : nullptr;
+    } else {
+        d_x0 = st.up(x0, span);
+        d_x1 = st.up(x1, span);
+    }
+    double *d_f = f ? st.out<double>(N * ny) : nullptr, *d_s = sigma ? st.out<double>(N) : nullptr;
+    int32_t* d_st = status ? st.out<int32_t>(P) : nullptr;
+    if (st.ok()) st.rc = gpc_sparse_predict_scattered_dev(g, n, d_patch, d_x0, d_x1, stride, d_f, d_s, conf, d_st);
+    st.down(f, d_f, N * ny);
+    st.down(sigma, d_s, N);
+    st.down(status, d_st, P);
     return st.finish();
 }
 

@@ -33,6 +33,11 @@ int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* 
 // xs0 / xs1 (m == 0, plane stride n_total).  max_blocks: cap on the resident workgroups per CU of the regular kernel.
 int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, const double* xs0, const double* xs1, double* f_star,
                       double* sigma, int conf, int32_t* status, int max_blocks);
+// sparse_scatter.hip: gpc_sparse_predict_scattered_dev behind its argument checks (n >= 0, stride >= 1) -- buckets the n entries by patch in
+// the context's workspace, runs sp_predict_launch on the bucketed batch and scatters the result back to entry order.  render.hip calls it
+// for the sigma of a render's hits.
+int sp_scatter_launch(gpc_sparse* g, int n, const int32_t* patch, const double* x0, const double* x1, int stride, double* f, double* sigma,
+                      int conf, int32_t* status);
 // raw != nullptr: the train_sigmaf pass (sigma_f^2 = 1, per-point sums only)
 int sp_likelihood_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
                          double* dX, double* l, double* raw);

@@ -217,6 +217,25 @@ int gpc_sparse_predict_points(gpc_sparse* g, const int32_t* off, const double* x
                               int conf, int32_t* status);
 int gpc_sparse_predict_points_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1,
                                   double* f, double* sigma, int conf, int32_t* status);
+/* predict_measurements at n UNBUCKETED (patch, point) pairs, in any order: entry i is the point (x0[i stride], x1[i stride]) under patch
+ * patch[i].  stride >= 1 counts doubles: 1 is the SoA layout of the entries above; (local + 1, local + 2, 3) reads the `local` output
+ * of gpc_patches_render in place.  f: ny planes of n in ENTRY order, sigma: n; either may be NULL.  status: P words or NULL; conf as in
+ * gpc_sparse_predict.
+ *   skipped  an entry with patch[i] < 0 or patch[i] >= P is skipped: its f (every plane) and sigma are NaN.  That is the miss
+ *            convention of gpc_patches_render and no error.
+ *   result   f, sigma and status are, bit for bit, those of gpc_sparse_predict_points_dev on the batch in which patch p owns the
+ *            entries with patch[i] == p in ascending i: the entries are bucketed on the device (keys, a stable radix sort over
+ *            ceil(log2(P + 1)) bits, a binary search per patch for `off`, a gather), the same kernels run on that batch, and the
+ *            result is scattered back.  No atomics: the same inputs give the same bits.
+ *   errors   n == 0: GPC_OK.  GPC_EINVAL: a NULL or dead object, n < 0, stride < 1, NULL patch / x0 / x1 with n > 0.  Outputs must
+ *            not overlap inputs.
+ * gpc_sparse_predict_scattered_dev takes DEVICE pointers, enqueues on the context's stream and never synchronises (the number of
+ * valid entries is never read back); the scratch is the context's workspace.  gpc_sparse_predict_scattered takes HOST pointers and is
+ * synchronous. */
+int gpc_sparse_predict_scattered(gpc_sparse* g, int n, const int32_t* patch, const double* x0, const double* x1, int stride, double* f,
+                                 double* sigma, int conf, int32_t* status);
+int gpc_sparse_predict_scattered_dev(gpc_sparse* g, int n, const int32_t* patch, const double* x0, const double* x1, int stride,
+                                     double* f, double* sigma, int conf, int32_t* status);
 /* Registration inner loop: sparse_gp::compute_derivatives + compute_likelihoods
  * (src/sparse_gp.h:44-45 -> src/sparse_gp.hpp:387-427, 463-508; field: src/sparse_gp_field.h:40-41 -> .hpp:322-392; call site
  * src/gp_registration.cpp:175-195), batched over patches: patch i evaluates its own rows off[i]..off[i+1]-1 of x0, x1 and
@@ -429,8 +448,8 @@ int gpc_occupancy_batch_dev(gpc_ctx* ctx, const gpc_patches* map, const uint8_t*
  *   counts   host int32[5] or NULL: rays; hits; rays that never met the grid (invalid directions included); surface tests run;
  *            tests with finite t, q, f, g and |g| > eps_rel res.
  * Deviations: only the leaves of the voxels a ray visits are tested (as train_classification does): the sliver of a patch that
- * protrudes into a neighbouring voxel that is no trained leaf is not seen.  The predictive sigma at the hit is not computed: leaf and
- * local let a caller bucket the hits by leaf and call gpc_sparse_predict_points_dev.
+ * protrudes into a neighbouring voxel that is no trained leaf is not seen.  The predictive sigma and the surface normal at the hits
+ * are a second call on the render's leaf and local outputs: gpc_patches_render_attrs below.
  * The same inputs give the same bits: integer atomics (the counters) only.  gpc_patches_render takes HOST dirs / cells / outputs and
  * is synchronous; gpc_patches_render_dev takes DEVICE dirs, cells and per-ray outputs (leaf, range, local may each be NULL), enqueues
  * on the context's stream and synchronises only when counts != NULL.  n == 0: GPC_OK.  GPC_EINVAL: a NULL or destroyed object, objects
@@ -449,6 +468,27 @@ int gpc_patches_render(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* d
 int gpc_patches_render_dev(gpc_ctx* ctx, const gpc_patches* map, const gpc_sparse* depth, const gpc_sparse* rgb, const uint8_t* cells,
                            const gpc_render_params* params, const double origin[3], const double* dirs, int n,
                            gpc_point_xyzrgb* cloud, int32_t* leaf, double* range, double* local, int32_t* counts);
+/* Confidence and surface normal at the hits of a render.  leaf (n) and local (n x 3) are the outputs of gpc_patches_render[_dev], or
+ * any arrays of that form: nothing is walked again.  Either output may be NULL.
+ *   sigma    [n]: gpc_sparse_predict_scattered_dev(depth, n, leaf, local + 1, local + 2, 3, NULL, sigma, conf, NULL) -- the
+ *            predictive sigma of the depth GP at the hit, sqrt(s20 + k* + k^T C k) (src/sparse_gp.hpp:299-351), or with conf != 0 the
+ *            0-100 confidence form.  NaN at a miss.
+ *   normal   [n][3], unit length, in the world.  With L = leaf[i], q = (local[3 i + 1], local[3 i + 2]) and R_L = (n, u, v):
+ *            (fx, fy) = (sum_j alpha_j k_j (BV_j - q)) / l_sq exactly as the surface test of the render forms it (j ascending over the
+ *            min(basis count, ld) basis vectors, the library's exp);  frame normal v = (1, -fx, -fy);  w_a = (R[a] + R[a + 3] v1) +
+ *            R[a + 6] v2 (gpc_reproject's association);  len = sqrt((w0 w0 + w1 w1) + w2 w2);  normal = w / len.
+ *            origin != NULL (host, 3 doubles, finite): x = R_L (local[3 i], q1, q2) + mean_L as the hit rule forms it, e = origin - x,
+ *            and when (normal_0 e_0 + normal_1 e_1) + normal_2 e_2 < 0 every component is negated: the normal faces the sensor.
+ *            origin == NULL: the normal keeps the sign of the frame's first column.
+ *            A miss (leaf outside [0, P)) or a non-finite intermediate gives three NaN.  An empty basis gives the normalised first
+ *            column of R_L.
+ * gpc_patches_render_attrs takes HOST arrays and is synchronous; gpc_patches_render_attrs_dev takes DEVICE arrays, enqueues on the
+ * context's stream and never synchronises.  n == 0: GPC_OK.  GPC_EINVAL: a NULL or destroyed object, objects of different contexts,
+ * depth with another P or ny != 1, a non-finite origin, n < 0, NULL leaf or local with n > 0. */
+int gpc_patches_render_attrs(gpc_ctx* ctx, const gpc_patches* map, gpc_sparse* depth, int n, const int32_t* leaf, const double* local,
+                             const double* origin, int conf, double* sigma, double* normal);
+int gpc_patches_render_attrs_dev(gpc_ctx* ctx, const gpc_patches* map, gpc_sparse* depth, int n, const int32_t* leaf,
+                                 const double* local, const double* origin, int conf, double* sigma, double* normal);
 /* Pinhole rays for gpc_patches_render_dev: pixel i = v width + u gets dir = R ((u - cx) / fx, (v - cy) / fy, 1), R host, column-major
  * (the camera's axes in the world).  Not normalised, so `range` is the depth along the optical axis, as a depth camera reports it.
  * dirs_dev: DEVICE, width * height x 3.  Enqueued on the context's stream.  GPC_EINVAL: negative sizes, fx or fy zero or not finite,

@@ -8,6 +8,10 @@ exit), plus one.  Prints one JSON line (and writes it to --out).
     python tools/bench_render.py --case c1             # BASELINE config 1: plane_cloud(10000), seen from above
     python tools/bench_render.py --case big            # 2.1 M points, ~8100 leaves, seen from above its centre
     python tools/bench_render.py --case deep           # four stacked sheets seen from the side, between the sheets: long walks
+    python tools/bench_render.py --case big --attrs --out-attrs profiles/render_attrs_bench.json
+        # ... and a second record: render alone, render + gpc_patches_render_attrs_dev (sigma and normal), and the route a caller had
+        # without that entry (D2H of leaf / local, NumPy stable argsort and CSR, H2D, predict_points_dev, host scatter) for the same
+        # image.  The three are timed in turn, alternating, each call ending in a synchronise; medians with min and max.
 """
 import argparse
 import json
@@ -29,6 +33,8 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--width", type=int, default=640)
 ap.add_argument("--height", type=int, default=480)
 ap.add_argument("--out")
+ap.add_argument("--attrs", action="store_true", help="also time render + attrs against render alone and the host-bucketed route")
+ap.add_argument("--out-attrs")
 a = ap.parse_args()
 
 res, sz = 0.15, 20
@@ -104,6 +110,84 @@ if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         f.write(line + "\n")
+if a.attrs:
+    P = int(v.P)
+
+    def render_only():
+        return pt.render(origin, dirs, gd, None, want=("leaf", "local"))
+
+    def render_attrs():
+        return pt.render(origin, dirs, gd, None, want=("leaf", "local", "sigma", "normal"))
+
+    def render_host_route():
+        """what a caller did for sigma before the attrs entry: download, bucket on the host, upload, predict_points_dev, scatter back"""
+        o = render_only()
+        leaf, local = o["leaf"].cpu().numpy(), o["local"].cpu().numpy()
+        valid = leaf >= 0
+        key = np.where(valid, leaf, P)
+        order = np.argsort(key, kind="stable")
+        nv = int(valid.sum())
+        off = np.concatenate([[0], np.cumsum(np.bincount(key[valid], minlength=P)[:P])]).astype(np.int32)
+        idx = order[:nv]
+        d_off = torch.from_numpy(off).cuda()
+        d_x0, d_x1 = torch.from_numpy(np.ascontiguousarray(local[idx, 1])).cuda(), torch.from_numpy(np.ascontiguousarray(local[idx, 2])).cuda()
+        d_f, d_s = torch.empty(max(nv, 1), dtype=torch.float64, device="cuda"), torch.empty(max(nv, 1), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        gd.predict_points_dev(d_off, nv, d_x0, d_x1, d_f, d_s)
+        ctx.synchronize()
+        sigma = np.full(n, np.nan)
+        sigma[idx] = d_s.cpu().numpy()[:nv]
+        return o, sigma
+
+    # ... and the device work of the sigma alone, on one render's outputs: the scattered entry (keys, sort, offsets, gather, predict,
+    # scatter) against predict_points_dev on the same entries already bucketed -- the difference is what the bucketing costs
+    base = render_only()
+    b_leaf, b_local = base["leaf"], base["local"]
+    h_leaf, h_local = b_leaf.cpu().numpy(), b_local.cpu().numpy()
+    h_key = np.where(h_leaf >= 0, h_leaf, P)
+    h_idx = np.argsort(h_key, kind="stable")[:int((h_leaf >= 0).sum())]
+    b_off = torch.from_numpy(np.concatenate([[0], np.cumsum(np.bincount(h_key[h_leaf >= 0], minlength=P)[:P])]).astype(np.int32)).cuda()
+    b_x0, b_x1 = (torch.from_numpy(np.ascontiguousarray(h_local[h_idx, c])).cuda() for c in (1, 2))
+    b_f, b_s, b_sig = (torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(3))
+    torch.cuda.synchronize()
+
+    def sigma_scattered():
+        gd.predict_scattered_dev(n, b_leaf, b_local.data_ptr() + 8, b_local.data_ptr() + 16, 3, None, b_sig)
+        ctx.synchronize()
+
+    def sigma_bucketed():
+        gd.predict_points_dev(b_off, len(h_idx), b_x0, b_x1, b_f, b_s)
+        ctx.synchronize()
+
+    routes = {"render": render_only, "render_attrs": render_attrs, "render_host_bucketed_sigma": render_host_route,
+              "sigma_scattered_dev": sigma_scattered, "sigma_prebucketed_dev": sigma_bucketed}
+    times = {k: [] for k in routes}
+    last = {}
+    for it in range(a.warmup + a.steps):
+        for k, fn in routes.items():                                             # alternating: the three see the same machine state
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            last[k] = fn()
+            torch.cuda.synchronize()
+            if it >= a.warmup:
+                times[k].append(time.perf_counter() - t0)
+    # the two routes to sigma agree bit for bit
+    same = last["render_attrs"]["sigma"].cpu().numpy().tobytes() == last["render_host_bucketed_sigma"][1].tobytes()
+    rec2 = {"workload": rec["workload"], "P": P, "rays": n, "hits": int(counts[1]), "steps_timed": a.steps, "warmup": a.warmup,
+            "protocol": "host clock around calls that end in a device synchronise; the routes alternate inside one loop; "
+                        "profiler off; one run on one MI355X; output allocation of the binding included in every route",
+            "sigma_bytes_equal_host_route": bool(same)}
+    for k, t in times.items():
+        rec2[k + "_ms"] = 1e3 * float(np.median(t))
+        rec2[k + "_ms_min_max"] = [1e3 * min(t), 1e3 * max(t)]
+    rec2["attrs_over_render"] = rec2["render_attrs_ms"] / rec2["render_ms"]
+    rec2["bucketing_ms"] = rec2["sigma_scattered_dev_ms"] - rec2["sigma_prebucketed_dev_ms"]
+    line2 = json.dumps(rec2)
+    print(line2)
+    if a.out_attrs:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out_attrs)), exist_ok=True)
+        with open(a.out_attrs, "w") as f:
+            f.write(line2 + "\n")
 for o in (gd, gc, pt):
     o.close()
 ctx.close()
