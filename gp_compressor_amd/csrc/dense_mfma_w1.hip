@@ -15,7 +15,8 @@
 //   * the forward solve rides on the sweep (the row operands L_(k+c)j are in registers there: four FMAs per lane give
 //     sum_j L_(k+c)j z_j), so the factor is read once per use and nowhere twice in a step except as the column operands of the
 //     row passes.
-//   * 64-thread workgroups, 15.6 KB of LDS (points, z / alpha, the four L_cc^-1 images), 256 VGPRs: eight workgroups per CU.
+//   * 64-thread workgroups, 16 KB of LDS (points, z / alpha, the four L_cc^-1 images, the diagonals of the paired L_kk^-T), 256 VGPRs:
+//     eight workgroups per CU.
 //
 // Layouts, lane maps and the diagonal factor are those of mfma_tile.h; tiles are kept TRANSPOSED in the C/D layout (see
 // dense_mfma.hip), so a TRSM result is directly the operand image of L_ik.
@@ -34,6 +35,12 @@
 #define W1_TRI_OF(npad) (W1_NT_OF(npad) * (W1_NT_OF(npad) + 1) / 2)  // images of a slot
 // offset (doubles) of tile (i, j), j <= i, in a slot
 #define W1_TILE(i, j) (((size_t)(i) * (size_t)((i) + 1) / 2 + (size_t)(j)) * MF_IMG)
+// The L_kk^-T images of the 256-point instance go out in PAIRS, two triangles per image (mf_tri_pack: tile 2 p on and above the diagonal,
+// tile 2 p + 1 reversed below it, its diagonal in LDS), and those of the last step not at all (the backward solve starts where the
+// factorization ends and reads them from the step's L_cc^-1 images in LDS).  The 512-point instance keeps one image per tile: the 2 KB of
+// diagonals would cost it its seventh workgroup per CU.
+#define W1_PACK_OF(npad) ((npad) <= 256)
+#define W1_LNV_OF(npad) (W1_PACK_OF(npad) ? W1_NT_OF(npad) / 2 : W1_NT_OF(npad))   // L_kk^-T images of a slot
 
 // Non-temporal hint on the one stream that is used once and gains by it, the backward solve's loads (mf_img_load_nt), so that the block
 // rows a step reads three times (sweep, column operands of two passes) have a better chance to stay in L2.  Measured on one box, C2: none
@@ -54,7 +61,7 @@ struct W1Params {
     double cs, noise_u, sfp, a_out;
     double* ws;         // factor slots, one per patch of the launch: W1_TRI images, the lower triangle packed row-major -- tile (i, j) at
                         // (i (i + 1) / 2 + j) * 256 -- which is the layout dense_variance_kernel<16> reads (dense_variance.hip)
-    double* linvt;      // the L_kk^-T images: [patch][16][256]
+    double* linvt;      // the L_kk^-T images: [slot][W1_LNV_OF][256]
     int export_factor;  // predictive variance: the L_kk^-1 images go to the diagonal positions of the slot
     unsigned long long* stamps;   // diagnostic build (-DW1_STAMPS, GPC_W1_STAMPS=1): [phase] s_memtime sums over all patches
 };
@@ -99,6 +106,15 @@ __host__ __device__ constexpr int w1_stream_col(int q)
     int kk = 0;
     while ((kk + 1) * (kk + 2) / 2 <= q) ++kk;
     return kk;
+}
+// The stream with paired L_kk^-T images, aligned at an EVEN column count: column pair pp from the end (columns kk = 2 pp and 2 pp + 1) takes
+// 4 pp + 2 positions -- the 2 pp tiles of column 2 pp, the pair's packed image, the 2 pp + 1 tiles of column 2 pp + 1 -- and starts at
+// position 2 pp^2.  Position -> pair: the largest pp with 2 pp^2 <= q.
+__host__ __device__ constexpr int w1_pstream_pair(int q)
+{
+    int pp = 0;
+    while (2 * (pp + 1) * (pp + 1) <= q) ++pp;
+    return pp;
 }
 #define W1_BW 20     // images in flight in the backward solve's ring (160 VGPRs)
 
@@ -177,6 +193,9 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
     __shared__ __attribute__((aligned(16))) double px0[W1_NPAD], px1[W1_NPAD], zv[W1_NPAD];     // zv: z, then alpha in place
     __shared__ __attribute__((aligned(16))) double rsbuf[32], wsc[32];
     __shared__ __attribute__((aligned(16))) double LinvC[W1_C * MF_IMG];
+    constexpr bool W1_PACK = W1_PACK_OF(W1_NPAD);
+    constexpr int W1_LNV = W1_LNV_OF(W1_NPAD);
+    __shared__ __attribute__((aligned(16))) double dgl[W1_PACK ? W1_LNV * MF_TS : 2];   // [pair][15 - i]: the diagonal of the pair's second L_kk^-1
 
     const DenseArgs& A = g.a;
     // The lane id goes through an empty asm at the head of every phase (W1_FRESH_LANE): hipcc hoists lane-dependent address arithmetic
@@ -197,7 +216,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
     // the body -- lane masks, addresses, grid constants -- in front of such a loop and then spills them: 350 VGPRs in that form)
     const int patch = blockIdx.x;
     double* Lt = g.ws + (size_t)patch * W1_TRI * MF_IMG;          // tiles (i, j): Lt + W1_TILE(i, j)
-    double* LinvTg = g.linvt + (size_t)patch * W1_NT * MF_IMG;    // L_kk^-T images
+    double* LinvTg = g.linvt + (size_t)patch * W1_LNV * MF_IMG;   // L_kk^-T images (`patch` is the slot: the index within the launch)
 
     gpc_exp_table_init(T);
     {
@@ -286,6 +305,31 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
         // k + 1 + t, then its L_kk^-T.  A tile adds its part of w_k = sum_{i>k} L_ik^T alpha_i on the VALU (the products contract over the
         // ROW index, which the image layout cannot feed to an MFMA); L_kk^-T closes the column: transposing DPP row reduction of w_k,
         // alpha_k = L_kk^-T (z_k - w_k) as four MFMAs, alpha_k into zv in place of z_k.
+        // REV: `img` is the image of J L_kk^-T J (mf_tri_pack's lower half): right-hand side and result with the index reversed.
+        auto bw_close = [&](auto HASW, auto REV, const int k, const d4 img, d4& pa) __attribute__((always_inline)) {
+            constexpr bool has_w = decltype(HASW)::value, rev = decltype(REV)::value;
+            d4 ub = d4{0.0, 0.0, 0.0, 0.0};
+            if constexpr (has_w) {
+                const double tot = mf_row_reduce4(pa, lr);       // lanes lr = 0, 4, 8, 12 hold components 0 .. 3
+                if ((lr & 3) == 0) wsc[lg + 4 * (lr >> 2)] = tot;
+                W1_LDS_SYNC();
+            }
+            if (lr == 0) {
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const int e = rev ? MF_TS - 1 - (lg + 4 * q4) : lg + 4 * q4;
+                    ub[q4] = has_w ? zv[MF_TS * k + e] - wsc[e] : zv[MF_TS * k + e];
+                }
+            }
+            const d4 al = w1_trsm(img, ub);                      // lanes lr = 0: alpha[16 k + (l >> 4) + 4 r]  (REV: 15 - ...)
+            W1_LDS_SYNC();
+            if (lr == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zv[MF_TS * k + (rev ? MF_TS - 1 - (lg + 4 * r) : lg + 4 * r)] = al[r];
+            }
+            W1_LDS_SYNC();
+            pa = d4{0.0, 0.0, 0.0, 0.0};
+        };
         auto bw_step = [&](auto P, const d4 img, d4& pa) __attribute__((always_inline)) {
             constexpr int q = decltype(P)::value;
             constexpr int kk = w1_stream_col(q), t = q - kk * (kk + 1) / 2;
@@ -295,29 +339,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                     const double a_ = zv[MF_TS * (k + 1 + t) + lr];
                     pa += img * a_;                                      // the image of L_ik: [l & 15][(l >> 4) + 4 s]
                 } else {
-                    d4 ub = d4{0.0, 0.0, 0.0, 0.0};
-                    if constexpr (kk > 0) {
-                        const double tot = mf_row_reduce4(pa, lr);       // lanes lr = 0, 4, 8, 12 hold components 0 .. 3
-                        if ((lr & 3) == 0) wsc[lg + 4 * (lr >> 2)] = tot;
-                        W1_LDS_SYNC();
-                        if (lr == 0) {
-#pragma unroll
-                            for (int q4 = 0; q4 < 4; ++q4) ub[q4] = zv[MF_TS * k + lg + 4 * q4] - wsc[lg + 4 * q4];
-                        }
-                    } else {
-                        if (lr == 0) {
-#pragma unroll
-                            for (int q4 = 0; q4 < 4; ++q4) ub[q4] = zv[MF_TS * k + lg + 4 * q4];
-                        }
-                    }
-                    const d4 al = w1_trsm(img, ub);                      // lanes lr = 0: alpha[16 k + (l >> 4) + 4 r]
-                    W1_LDS_SYNC();
-                    if (lr == 0) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) zv[MF_TS * k + lg + 4 * r] = al[r];
-                    }
-                    W1_LDS_SYNC();
-                    pa = d4{0.0, 0.0, 0.0, 0.0};
+                    bw_close(std::bool_constant<(kk > 0)>{}, std::false_type{}, k, img, pa);
                 }
             }
         };
@@ -354,11 +376,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
         for (int k = 0;; k += W1_C) {                                      // (left by `break` at the last step)
             const int nc = min(W1_C, nt - k);                              // tile columns of this step
             const int kl = k - 1;
-            // (not used, and not to be tidied away: a left-over of the removed resident-last-block variant.  Without this early k + W1_C
-            // hipcc emits other code for the kernel -- same registers, no spills, 8 bytes longer, schedule of the step moved (compiled both
-            // ways) -- so the line stays, and the kernel byte for byte the one that was measured)
             const bool last_step = k + W1_C >= nt;
-            (void)last_step;
             W1_FRESH_LANE();
             // ---- the diagonal block: T_(k+i)(k+c) = A - sum_{j<k} L_(k+i)j L_(k+c)j^T, tile d = i (i + 1) / 2 + c, one sweep over j;
             //      the forward-solve sums  part_c = sum_{j<k} L_(k+c)j z_j  from the same operands ----
@@ -399,7 +417,7 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
             d4 Lb[W1_C * (W1_C - 1) / 2];
 #pragma unroll
             for (int q = 0; q < W1_C * (W1_C - 1) / 2; ++q) Lb[q] = d4{0.0, 0.0, 0.0, 0.0};
-            bool ok = mf_diag_factor_c(tacc[0], rsbuf, LinvC, LinvTg + (size_t)k * MF_IMG, ptol, lane);
+            bool ok = mf_diag_factor_c(tacc[0], rsbuf, LinvC, W1_PACK ? nullptr : LinvTg + (size_t)k * MF_IMG, ptol, lane);
             W1_LDS_SYNC();
             if (g.export_factor) mf_img_store(Lt + W1_TILE(k, k), lane, mf_img_load(LinvC, lane));
 #pragma unroll
@@ -418,12 +436,26 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
                     d4 Dii = tacc[i * (i + 1) / 2 + i];
 #pragma unroll
                     for (int c = 0; c < i; ++c) Dii = w1_mfma4_neg(Lb[i * (i - 1) / 2 + c], Lb[i * (i - 1) / 2 + c], Dii);
-                    ok = mf_diag_factor_c(Dii, rsbuf, LinvC + i * MF_IMG, LinvTg + (size_t)(k + i) * MF_IMG, ptol, lane);
+                    ok = mf_diag_factor_c(Dii, rsbuf, LinvC + i * MF_IMG, W1_PACK ? nullptr : LinvTg + (size_t)(k + i) * MF_IMG, ptol, lane);
                     W1_LDS_SYNC();
                     if (g.export_factor) mf_img_store(Lt + W1_TILE(k + i, k + i), lane, mf_img_load(LinvC + i * MF_IMG, mf_opaque(lane)));
                 }
             }
             if (!ok) { bad = true; break; }
+            if constexpr (W1_PACK) {
+                // The step's L_cc^-T go out as two packed images, composed from the L_cc^-1 images in LDS (a step that is not the last has
+                // all four columns).  The last step writes none: its inverses stay in LinvC for the backward solve.
+                if (!last_step) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int lp = mf_opaque(lane), pr = (k >> 1) + h;
+                        const double* Lo = LinvC + (2 * h + 1) * MF_IMG;
+                        const d4 pk = mf_tri_pack(mf_img_load_t(LinvC + 2 * h * MF_IMG, lp), mf_img_load_tr(Lo, lp));
+                        mf_img_store(LinvTg + (size_t)pr * MF_IMG, lp, pk);
+                        if (lp < MF_TS) dgl[MF_TS * pr + lp] = Lo[mf_img_rc(MF_TS - 1 - lp, MF_TS - 1 - lp)];
+                    }
+                }
+            }
             W1_STAMP(3);
             W1_FRESH_LANE();
             // ---- forward solve of the step's columns: z_(k+c) = L_cc^-1 (y_(k+c) - part_c - sum_{c2<c} L_(k+c)(k+c2) z_(k+c2)) ----
@@ -608,7 +640,77 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
         // kernel for 2 % of its arithmetic: every column waited out an HBM round trip).  Everything is unrolled over the stream
         // positions of a 16-column factor, aligned at its last column: column kk from the end (k = nt-1-kk) has kk tiles, rows
         // k+1+t; positions of columns a smaller factor does not have are skipped, their requests clamped to the slot's first image.
-        {
+        // With paired images (W1_PACK) the stream is aligned at the EVEN column count nte >= nt instead (an odd factor gets a phantom
+        // last column: no tiles, and its half of the last pair is never used): NP^2 / 2 positions, one packed image per column pair -- it
+        // closes the pair's odd column from its lower half where it arrives, and its upper half waits in LDS (LinvC's last image, free by
+        // then; in registers across the even column's tiles it costs the ring a spill) for the even column's close behind that column's
+        // tiles.  The pairs of the last step (the first one or two of the stream) come from LinvC itself, read transposed; their stream
+        // positions request the slot's first image like every other skipped position.
+        if constexpr (W1_PACK) {
+            W1_FRESH_LANE();
+            constexpr int NP = W1_NT;
+            constexpr int SLEN = NP * NP / 2;                       // 128 stream positions
+            const int nte = (nt + 1) & ~1, kls = (nt - 1) & ~(W1_C - 1);      // kls: the last step's first column
+            d4 win[W1_BW];
+            auto stream_addr = [&](auto P) __attribute__((always_inline)) -> const double* {
+                constexpr int q = decltype(P)::value;
+                constexpr int pp = w1_pstream_pair(q), i = q - 2 * pp * pp;
+                if constexpr (i == 2 * pp) {
+                    const int k = nte - 1 - 2 * pp;                 // the pair (k - 1, k), k odd
+                    return (k >= 1 && k - 1 < kls) ? LinvTg + (size_t)(k >> 1) * MF_IMG : Lt;
+                } else {
+                    constexpr int kk = i < 2 * pp ? 2 * pp : 2 * pp + 1, t = i < 2 * pp ? i : i - 2 * pp - 1;
+                    const int k = nte - 1 - kk, kq = max(k, 0);
+                    return (k >= 0 && k + 1 + t < nt) ? Lt + W1_TILE(kq + 1 + t, kq) : Lt;
+                }
+            };
+            w1_static_for<0, W1_BW>([&](auto P) __attribute__((always_inline)) {
+                constexpr int q = decltype(P)::value;
+                win[q] = mf_img_load_nt(stream_addr(P), lane);
+            });
+            d4 pa = d4{0.0, 0.0, 0.0, 0.0};
+            double* const held = LinvC + (W1_C - 1) * MF_IMG;
+            w1_static_for<0, SLEN>([&](auto P) __attribute__((always_inline)) {
+                constexpr int q = decltype(P)::value;
+                constexpr int pp = w1_pstream_pair(q), i = q - 2 * pp * pp;
+                const d4 img = win[q % W1_BW];
+                if constexpr (i == 2 * pp) {
+                    const int k = nte - 1 - 2 * pp;
+                    if (k >= 1) {
+                        d4 lo;
+                        bool in_lds = false;
+                        if constexpr (pp < W1_C / 2) in_lds = k - 1 >= kls;
+                        if (in_lds) {
+                            const double* Lc = LinvC + (k - 1 - kls) * MF_IMG;
+                            lo = mf_img_load_tr(Lc + MF_IMG, lane);          // (k == nt: the phantom column's, not used)
+                        } else {
+                            mf_img_store(held, lane, mf_tri_upper(img));
+                            lo = mf_tri_lower(img, dgl[MF_TS * (k >> 1) + lr]);
+                            W1_LDS_SYNC();
+                        }
+                        if (k < nt) bw_close(std::bool_constant<(pp > 0)>{}, std::true_type{}, k, lo, pa);
+                    }
+                } else {
+                    constexpr int kk = i < 2 * pp ? 2 * pp : 2 * pp + 1, t = i < 2 * pp ? i : i - 2 * pp - 1;
+                    const int k = nte - 1 - kk;
+                    if (k >= 0 && k + 1 + t < nt) {
+                        const double a_ = zv[MF_TS * (k + 1 + t) + lr];
+                        pa += img * a_;
+                    }
+                    if constexpr (i == 4 * pp + 1) {
+                        if (k >= 0) {
+                            bool in_lds = false;
+                            if constexpr (pp < W1_C / 2) in_lds = k >= kls;
+                            const d4 up = in_lds ? mf_img_load_t(LinvC + (k - kls) * MF_IMG, lane) : mf_img_load(held, lane);
+                            bw_close(std::true_type{}, std::false_type{}, k, up, pa);
+                        }
+                    }
+                }
+                if constexpr (q + W1_BW < SLEN) {
+                    win[q % W1_BW] = mf_img_load_nt(stream_addr(std::integral_constant<int, q + W1_BW>{}), lane);
+                }
+            });
+        } else {
             W1_FRESH_LANE();
             constexpr int NP = W1_NPAD / MF_TS;                     // 16
             constexpr int SLEN = NP * (NP + 1) / 2;                 // 136 stream positions
@@ -748,7 +850,7 @@ bool dense_w1_supported(const DenseArgs& a)
     return a.n_max <= W1_NPAD_MAX && a.ny == 1 && !a.sel;
 }
 
-// One factor slot per patch of a launch (304 KB: 2.5 GB for the 8192 patches of BASELINE config 2 -- sized for 288 GB); a larger
+// One factor slot per patch of a launch (288 KB: 2.4 GB for the 8192 patches of BASELINE config 2 -- sized for 288 GB); a larger
 // batch goes through in launches of W1_MAX_SLOTS patches that reuse the slots (a launch of 8192 patches is four rounds of the 2048
 // resident workgroups: its ramp and tail are ~3 % of it).  `cap` > 0: the dispatcher's retry with fewer slots after GPC_ENOMEM.
 #define W1_MAX_SLOTS 8192
@@ -767,7 +869,7 @@ size_t dense_w1_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out, 
     if (grid_out) *grid_out = grid;
     // factor slots | L_kk^-T images | (variance without alpha_out: the weights the variance kernel forms the mean from)
     const int npad = w1_npad(a);
-    return sizeof(double) * ((size_t)(W1_TRI_OF(npad) + W1_NT_OF(npad)) * MF_IMG * (size_t)grid + (a.v_star ? (size_t)a.n_total : 0));
+    return sizeof(double) * ((size_t)(W1_TRI_OF(npad) + W1_LNV_OF(npad)) * MF_IMG * (size_t)grid + (a.v_star ? (size_t)a.n_total : 0));
 }
 
 int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, int grid)
@@ -793,7 +895,7 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, 
         // Predictive variance (gaussian_process::predict_measurements, /root/reference/src/gaussian_process.cpp:35-43): the slots are the
         // factor export dense_variance_kernel<16> reads, the fit predicts nothing (the solve forms the mean from the same K* tiles)
         a.m = 0;
-        if (!a.alpha_out) a.alpha_out = g.linvt + (size_t)W1_NT_OF(npad) * MF_IMG * (size_t)grid;
+        if (!a.alpha_out) a.alpha_out = g.linvt + (size_t)W1_LNV_OF(npad) * MF_IMG * (size_t)grid;
     }
     ctx->last_dense_kernel = v_star ? "dense_mfma_w1 + dense_variance" : npad == 256 ? "dense_mfma_w1" : "dense_mfma_w1_512";
 #ifdef W1_STAMPS

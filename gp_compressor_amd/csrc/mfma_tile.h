@@ -262,6 +262,64 @@ __device__ __forceinline__ static bool mf_diag_factor_c(d4 W, double* rsbuf, dou
     return ok;
 }
 
+// ---- two triangular images in one (the one-wave kernel's L_kk^-T pairs) --------------------------------------------------------------
+// Register s of lane l of an image is element (row l & 15, column (l >> 4) + 4 s).  An upper triangular matrix U (an L^-T) fills the
+// elements on and above the diagonal; a second one, V, fits into the 120 elements strictly below it once its rows AND columns are
+// reversed: V' = J V J is lower triangular, V'[r][c] = V[15 - r][15 - c], and its elements sit where an MFMA reads them -- V x = J (V' (J x)),
+// so the solve that uses V' reads its right-hand side and writes its result with the index reversed and is otherwise the same four MFMAs.
+// V''s diagonal (the sixteenth of its 136 elements that has no room) is kept apart by the caller.  Which lanes of register s lie on /
+// above / below the diagonal are constants: selects on SGPR-pair literals, as in mf_diag_factor_c.
+__host__ __device__ constexpr unsigned long long mf_tri_mask(int s, int kind)       // kind 0: row <= column, 1: row == column, 2: row > column
+{
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int r = l & 15, c = (l >> 4) + 4 * s;
+        if (kind == 0 ? r <= c : kind == 1 ? r == c : r > c) m |= 1ull << l;
+    }
+    return m;
+}
+__device__ static __forceinline__ int mf_mix32(int a, int b, unsigned long long mask)     // lanes in `mask` get a, the others b
+{
+    int r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(mask));
+    return r;
+}
+__device__ static __forceinline__ double mf_mix64(double a, double b, unsigned long long mask)
+{
+    return __hiloint2double(mf_mix32(__double2hiint(a), __double2hiint(b), mask), mf_mix32(__double2loint(a), __double2loint(b), mask));
+}
+// the packed image: `up` on and above the diagonal, `lo` strictly below it
+__device__ static __forceinline__ d4 mf_tri_pack(d4 up, d4 lo)
+{
+    constexpr unsigned long long u0 = mf_tri_mask(0, 0), u1 = mf_tri_mask(1, 0), u2 = mf_tri_mask(2, 0), u3 = mf_tri_mask(3, 0);
+    return d4{mf_mix64(up[0], lo[0], u0), mf_mix64(up[1], lo[1], u1), mf_mix64(up[2], lo[2], u2), mf_mix64(up[3], lo[3], u3)};
+}
+// ... and back: the upper image (zeros below the diagonal) | the lower image with its diagonal, `dg` = the diagonal value of this lane's row
+__device__ static __forceinline__ d4 mf_tri_upper(d4 p)
+{
+    constexpr unsigned long long u0 = mf_tri_mask(0, 0), u1 = mf_tri_mask(1, 0), u2 = mf_tri_mask(2, 0), u3 = mf_tri_mask(3, 0);
+    return d4{mf_sel64(p[0], u0), mf_sel64(p[1], u1), mf_sel64(p[2], u2), mf_sel64(p[3], u3)};
+}
+__device__ static __forceinline__ d4 mf_tri_lower(d4 p, double dg)
+{
+    constexpr unsigned long long l0 = mf_tri_mask(0, 2), l1 = mf_tri_mask(1, 2), l2 = mf_tri_mask(2, 2), l3 = mf_tri_mask(3, 2);
+    constexpr unsigned long long e0 = mf_tri_mask(0, 1), e1 = mf_tri_mask(1, 1), e2 = mf_tri_mask(2, 1), e3 = mf_tri_mask(3, 1);
+    return d4{mf_mix64(dg, mf_sel64(p[0], l0), e0), mf_mix64(dg, mf_sel64(p[1], l1), e1), mf_mix64(dg, mf_sel64(p[2], l2), e2),
+              mf_mix64(dg, mf_sel64(p[3], l3), e3)};
+}
+// From the image of a lower triangular L^-1 in LDS (zeros above the diagonal): the image of U = L^-T, element (r, c) = L^-1[c][r], and
+// the image of J U J, element (r, c) = L^-1[15 - c][15 - r] (diagonal included)
+__device__ static __forceinline__ d4 mf_img_load_t(const double* img, int l)
+{
+    const int lr = l & 15, lg = l >> 4;
+    return d4{img[mf_img_rc(lg, lr)], img[mf_img_rc(lg + 4, lr)], img[mf_img_rc(lg + 8, lr)], img[mf_img_rc(lg + 12, lr)]};
+}
+__device__ static __forceinline__ d4 mf_img_load_tr(const double* img, int l)
+{
+    const int lr = 15 - (l & 15), lg = 15 - (l >> 4);
+    return d4{img[mf_img_rc(lg, lr)], img[mf_img_rc(lg - 4, lr)], img[mf_img_rc(lg - 8, lr)], img[mf_img_rc(lg - 12, lr)]};
+}
+
 // out[mr] = sum_kk M[mr][kk] * v[kk] for a 16 x 16 matrix stored as an operand image, one thread per row
 __device__ static __forceinline__ double mf_row_dot(const double* img, int mr, const double* v)
 {
