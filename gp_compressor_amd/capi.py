@@ -153,6 +153,7 @@ PROTOTYPES = {
     "gpc_test_exp_host": (None, [_vp, _vp, _i]),
     "gpc_test_exp_small_host": (None, [_vp, _vp, _i]),
     "gpc_test_par_memcpy": (None, [_vp, _vp, C.c_size_t]),
+    "gpc_test_dense_route": (C.c_int, [_i] * 11 + [_vp, _i, _vp]),
 }
 
 _lib = None
@@ -1006,3 +1007,18 @@ def exp_host(x, small=False):
     out = np.zeros_like(x)
     (load().gpc_test_exp_small_host if small else load().gpc_test_exp_host)(_ptr(x), _ptr(out), x.size)
     return out
+
+
+ROUTE_KINDS = {-1: "no route", 0: "nothing", 1: "one-wave", 2: "register", 3: "tiled", 4: "generic", 5: "split"}
+ROUTE_SHAPE = ("w1_npad", "w1_slots", "nt", "export_factor", "waves", "npad", "per_cu", "nt17", "need_big")
+
+
+def dense_route(P, n_max, n_total=None, ny=1, m=16, variance=False, pointwise=False, alpha_out=False, num_cus=256, irls=False,
+                w1_refused=False):
+    """gpc_test_dense_route: (kind, name, shape) the dense dispatcher chooses for a batch with these facts under the GPC_* switches of
+    the environment -- the rule alone, no GPU.  n_total=None: a uniform batch (P * n_max)."""
+    name = C.create_string_buffer(96)
+    shape = np.zeros(len(ROUTE_SHAPE), dtype=np.int32)
+    kind = load().gpc_test_dense_route(P, n_max, P * n_max if n_total is None else n_total, ny, m, int(variance), int(pointwise),
+                                       int(alpha_out), num_cus, int(irls), int(w1_refused), name, len(name), _ptr(shape))
+    return ROUTE_KINDS[kind], name.value.decode(), dict(zip(ROUTE_SHAPE, shape.tolist()))

@@ -1,7 +1,6 @@
-// dense_api.hip -- the dense path on device pointers: argument checks, the dispatcher that chooses the kernels of a batch, the
-// dense and IRLS _dev entries and the host-pointer IRLS entry.  The pipelined host-pointer dense entries are in dense_host.hip.
-#include <cstdlib>
-
+// dense_api.hip -- the dense path on device pointers: argument checks, the dispatcher that executes the route of a batch (the rule
+// that chooses the kernels is dense_route, dense_route.h: nothing here decides), the dense and IRLS _dev entries and the host-pointer
+// IRLS entry.  The pipelined host-pointer dense entries are in dense_host.hip.
 #include "dense_internal.h"
 
 int dense_check(gpc_ctx* ctx, const gpc_params* prm, int P, const void* off, int n_max, int n_total,
@@ -57,151 +56,135 @@ extern "C" __global__ void dense_classify_kernel(int P, const int32_t* off, int 
     }
 }
 
-bool dense_w1_takes(const gpc_ctx* ctx, const DenseArgs& a)
+static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The size-class split of a ragged batch (DENSE_SPLIT): classify on the device, then one launch per class.  `hinted` sizes launches,
+// it does not choose kernels.
+static int dense_split(gpc_ctx* ctx, const DenseArgs& a, const DenseSite& site, const DenseRoute& route, bool no_hint)
 {
-    const char* mp = getenv("GPC_W1_MIN_P");
-    const int min_p = mp ? atoi(mp) : 4 * ctx->num_cus;
-    const bool force = getenv("GPC_FORCE_GENERIC") || getenv("GPC_FORCE_BIG");
-    // (round 4: the kernel's 512-point instance takes the depth plane of batches whose largest patch has 257 .. 512 points -- C3, and the
-    // ragged batches of a cloud cut for 256-point patches, which the size-class split used to deal to three kernels; GPC_NO_W1_512=1: as before)
-    if (a.n_max > 256 && getenv("GPC_NO_W1_512")) return false;
-    return !force && a.n_max <= 512 && a.P >= min_p && a.P > 1 && (a.n_max > 192 || !a.v_star) && dense_w1_supported(a) && !getenv("GPC_NO_W1");
+    const bool nt17 = route.nt17, need_big = route.need_big;
+    const DenseRoute big = dense_route_class(route, 2);
+    int grid_b = 0;
+    const size_t big_bytes = need_big ? al256(dense_big_ws_bytes(ctx, a, big, &grid_b)) : 0;
+    // Class sizes known on the host (the batch came from gpc_project_cloud on this context): the class launches get exactly that
+    // many workgroups.  The hint is matched by pointer and P only -- a caller that rewrites `off` IN PLACE keeps both -- so every
+    // hinted launch is followed by an OVERFLOW launch of the generic kernel (a few workgroups that stride over
+    // sel[hint .. count), count on the device: no patch when the hint was right, every patch the hint missed otherwise).
+    const bool hinted = ctx->hint_off == a.off && ctx->hint_P == a.P && !no_hint;
+    constexpr int OVF_GRID = 8;
+    const size_t ovf_slot = sizeof(double) * (size_t)(17 * 16 + a.ny) * (size_t)(17 * 16 + a.ny);
+    const size_t ovf_bytes = hinted ? al256(2 * OVF_GRID * ovf_slot) : 0;
+    int rc = gpc_ws_reserve(ctx, site, big_bytes + ovf_bytes + sizeof(int32_t) * (3 * (size_t)a.P + 64));
+    if (rc != GPC_OK) return rc;
+    double* ovf_ws = reinterpret_cast<double*>(dense_ws(ctx, site) + big_bytes);
+    int32_t* counts = reinterpret_cast<int32_t*>(dense_ws(ctx, site) + big_bytes + ovf_bytes);
+    int32_t* sel0 = counts + 64;
+    int32_t* sel1 = sel0 + a.P;
+    int32_t* sel2 = sel1 + a.P;
+    GPC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), site.stream));
+    hipLaunchKernelGGL(dense_classify_kernel, dim3((a.P + 255) / 256), dim3(256), 0, site.stream, a.P, a.off, 256, nt17 ? 17 * 16 : 256,
+                       sel0, sel1, sel2, counts);
+    GPC_HIP(ctx, hipGetLastError());
+    // The classes are independent: they run on three streams (forked from and joined to the site's), so that
+    // the tail of one kernel -- its last workgroups running on a mostly idle chip -- fills with the next one's work.
+    const hipStream_t main_s = site.stream;
+    const DenseSite on_in{ctx->s_in, site.ws_off, site.ws_len}, on_out{ctx->s_out, site.ws_off, site.ws_len};
+    // an error after the fork must not leave work (or the caller's buffers) in flight on the side streams
+    auto bail = [&](int code) {
+        (void)hipStreamSynchronize(ctx->s_in);
+        (void)hipStreamSynchronize(ctx->s_out);
+        return code;
+    };
+    GPC_HIP(ctx, hipEventRecord(ctx->ev[0][GPC_EV_CLASS_FORK], main_s));
+    GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_in, ctx->ev[0][GPC_EV_CLASS_FORK], 0));
+    GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_out, ctx->ev[0][GPC_EV_CLASS_FORK], 0));
+    // largest patches first: the tiled kernel's workgroups are the long ones
+    if (need_big) {
+        DenseArgs b = a;
+        b.sel = sel2; b.sel_count = counts + 2;
+        rc = dense_big_launch(ctx, on_out, b, big, grid_b);
+        if (rc != GPC_OK) return bail(rc);
+    }
+    // Class `which` (0: n <= 256, 1: the NT = 17 shape) on the register kernel, `cnt` workgroups at `at`.  Without a hint cnt is P: the
+    // workgroups beyond the class count leave at once, but each still waits for a CU with 158 KB of LDS free.  With one, the overflow
+    // launch follows on the same stream; a class the hint calls empty is its overflow launch alone, on the main stream.
+    auto run_class = [&](int which, int cnt, const DenseSite& at) -> int {
+        DenseArgs s = a;
+        s.n_max = which ? 17 * 16 : 256;       // the class bound: what the overflow launch sizes its LDS and its slots for
+        s.sel = which ? sel1 : sel0; s.sel_count = counts + which;
+        s.P = cnt;
+        const int rcl = cnt > 0 ? dense_mfma_launch(ctx, at, s, dense_route_class(route, which)) : GPC_OK;
+        if (rcl != GPC_OK || !hinted || cnt >= a.P) return rcl;
+        s.sel_base = cnt;
+        s.P = a.P;
+        return dense_generic_launch(ctx, cnt > 0 ? at : site, s, OVF_GRID, ovf_ws + (size_t)which * OVF_GRID * (ovf_slot / sizeof(double)));
+    };
+    const int c0 = hinted ? ctx->hint_le256 : a.P;
+    const int c1 = hinted ? ctx->hint_le272 - ctx->hint_le256 : a.P;
+    if (nt17 && (rc = run_class(1, c1, on_in)) != GPC_OK) return bail(rc);
+    if ((rc = run_class(0, c0, site)) != GPC_OK) return bail(rc);
+    GPC_HIP(ctx, hipEventRecord(ctx->ev[1][GPC_EV_CLASS_FORK], ctx->s_in));
+    GPC_HIP(ctx, hipEventRecord(ctx->ev[2][GPC_EV_CLASS_FORK], ctx->s_out));
+    GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][GPC_EV_CLASS_FORK], 0));
+    GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][GPC_EV_CLASS_FORK], 0));
+    return rc;
 }
 
-// the tiled kernel's workspace for `a`, reserved at the site; its grid comes back in *grid
-static int dense_big_reserve(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int* grid)
-{
-    return gpc_ws_reserve(ctx, site, (dense_big_ws_bytes(ctx, a, grid) + 255) & ~(size_t)255);
-}
-
-// Caller holds ctx->mu.
+// Executes the route of a batch: reserves what its kernel needs, launches it, records its name.  Caller holds ctx->mu.
 int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* seen_gen)
 {
-    if (a.P == 0 || (a.m == 0 && !a.alpha_out)) return GPC_OK;
+    const DenseSwitches sw = dense_switches_read();
+    const DenseFacts facts = dense_facts(ctx, a);
+    DenseRoute route = dense_route(facts, sw);
+    if (route.kind == DENSE_NOTHING) return GPC_OK;
     if (a.n_max < 1) a.n_max = 1;
     if (seen_gen)      // a chunk of the two-stream host pipeline
         if (int rco = gpc_pipe_chunk_order(ctx, site.stream, seen_gen)) return rco;
     GPC_HIP(ctx, hipSetDevice(ctx->device));
     if (!a.prm.want_variance) a.v_star = nullptr;
     if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
-    const bool force_generic = getenv("GPC_FORCE_GENERIC") != nullptr, force_big = getenv("GPC_FORCE_BIG") != nullptr;
-    const bool ny_ok = a.ny == 1 || a.ny == 3;
-    if (!force_generic && !force_big && ny_ok) {
-        const bool no_split = a.P == 1 || getenv("GPC_NO_SPLIT");
-        // Depth plane, n <= 256, a batch large enough to fill the chip: ONE wave per patch, eight patches per CU (dense_mfma_w1.hip) --
-        // no hand-over between waves at all.  Measured against the register-resident kernel at 8192 patches: 256 points 1.72 against
-        // 2.57 ms, 192: 0.98 / 1.70, 128: 0.48 / 1.06, 64: 0.20 / 0.62; at 512 patches the two are level, below that the register kernel's
-        // eight waves per patch win on latency (64 patches x 192 points: 0.066 against 0.134 ms) -- hence the batch-size rule
-        // (GPC_W1_MIN_P overrides it; the variance goes this way for 193 .. 256 points, where its solve kernel is the <16> shape).
-        if (dense_w1_takes(ctx, a)) {
-            // One factor slot (304 KB) per patch of a launch.  If the device cannot serve that, the batch goes
-            // through in smaller launches that reuse fewer slots, and below two launches' worth of resident patches it takes the
-            // register-resident kernel, which needs no workspace at all.
-            int grid_w1 = 0, rcw = GPC_ENOMEM;
-            DenseArgs aw = a;
-            for (int cap_w1 = 0;;) {
-                const size_t w1_bytes = (dense_w1_ws_bytes(ctx, aw, &grid_w1, cap_w1) + 255) & ~(size_t)255;
-                rcw = gpc_ws_reserve(ctx, site, w1_bytes);
-                if (rcw != GPC_ENOMEM) break;
-                cap_w1 = grid_w1 / 2;
-                if (cap_w1 < 4 * ctx->num_cus) break;             // (below the batch-size rule of this kernel)
-            }
-            if (rcw == GPC_OK) return dense_w1_launch(ctx, site, a, grid_w1);
-            if (rcw != GPC_ENOMEM || a.v_star) return rcw;
+    int grid = 0, rc = GPC_OK;
+    if (route.kind == DENSE_ONE_WAVE) {
+        // One factor slot (304 KB) per patch of a launch.  If the device cannot serve that, the batch goes
+        // through in smaller launches that reuse fewer slots, and below two launches' worth of resident patches it takes the
+        // route it would have had without this kernel -- the register-resident one needs no workspace at all.
+        for (int cap_w1 = 0;;) {
+            rc = gpc_ws_reserve(ctx, site, al256(dense_w1_ws_bytes(facts, route, &grid, cap_w1)));
+            if (rc != GPC_ENOMEM) break;
+            cap_w1 = grid / 2;
+            if (cap_w1 < 4 * ctx->num_cus) break;             // (below the batch-size rule of this kernel)
+        }
+        if (rc == GPC_ENOMEM) {
+            route = dense_route(facts, sw, true);
+            if (route.kind == DENSE_NO_ROUTE) return rc;
             (void)hipGetLastError();
-        }
-        // (GPC_W2=1: the two-wave shape of the tiled kernel, round 3's first headline kernel, kept as a cross-check)
-        if (a.n_max > 192 && a.n_max <= 256 && a.ny == 1 && !a.v_star && a.P > 1 && getenv("GPC_W2")) {
-            int grid_w2 = 0;
-            if (int rcw = dense_big_reserve(ctx, site, a, &grid_w2)) return rcw;
-            return dense_big_launch(ctx, site, a, grid_w2);
-        }
-        if (a.n_max <= 256 || (no_split && dense_mfma_supported(a) && !getenv("GPC_NO_NT17")))
-            return dense_mfma_launch(ctx, site, a);                                                         // one shape for the whole batch
-        // (a batch whose patches all have n_max points -- P n_max == n_total: every n_i <= n_max and they add up to n_total -- has one
-        // size class and the host knows it: no classification, no empty class launches waiting for a CU beside the tiled kernel)
-        const bool uniform = (long long)a.P * a.n_max == (long long)a.n_total;
-        if (!a.v_star && a.n_max <= GPC_MAX_POINTS && !no_split && !(uniform && a.n_max > 17 * 16)) {
-            const bool nt17 = a.ny == 1 && !getenv("GPC_NO_NT17");
-            const bool need_big = !(nt17 && a.n_max <= 17 * 16);
-            int grid_b = 0;
-            const size_t big_bytes = need_big ? (dense_big_ws_bytes(ctx, a, &grid_b) + 255) & ~(size_t)255 : 0;
-            // Class sizes known on the host (the batch came from gpc_project_cloud on this context): the class launches get exactly that
-            // many workgroups.  The hint is matched by pointer and P only -- a caller that rewrites `off` IN PLACE keeps both -- so every
-            // hinted launch is followed by an OVERFLOW launch of the generic kernel (a few workgroups that stride over
-            // sel[hint .. count), count on the device: no patch when the hint was right, every patch the hint missed otherwise).
-            const bool hinted = ctx->hint_off == a.off && ctx->hint_P == a.P && !getenv("GPC_NO_HINT");
-            constexpr int OVF_GRID = 8;
-            const size_t ovf_slot = sizeof(double) * (size_t)(17 * 16 + a.ny) * (size_t)(17 * 16 + a.ny);
-            const size_t ovf_bytes = hinted ? (2 * OVF_GRID * ovf_slot + 255) & ~(size_t)255 : 0;
-            int rc = gpc_ws_reserve(ctx, site, big_bytes + ovf_bytes + sizeof(int32_t) * (3 * (size_t)a.P + 64));
-            if (rc != GPC_OK) return rc;
-            double* ovf_ws = reinterpret_cast<double*>(dense_ws(ctx, site) + big_bytes);
-            int32_t* counts = reinterpret_cast<int32_t*>(dense_ws(ctx, site) + big_bytes + ovf_bytes);
-            int32_t* sel0 = counts + 64;
-            int32_t* sel1 = sel0 + a.P;
-            int32_t* sel2 = sel1 + a.P;
-            GPC_HIP(ctx, hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), site.stream));
-            hipLaunchKernelGGL(dense_classify_kernel, dim3((a.P + 255) / 256), dim3(256), 0, site.stream, a.P, a.off, 256, nt17 ? 17 * 16 : 256,
-                               sel0, sel1, sel2, counts);
-            GPC_HIP(ctx, hipGetLastError());
-            // The classes are independent: they run on three streams (forked from and joined to the site's), so that
-            // the tail of one kernel -- its last workgroups running on a mostly idle chip -- fills with the next one's work.
-            const hipStream_t main_s = site.stream;
-            const DenseSite on_in{ctx->s_in, site.ws_off, site.ws_len}, on_out{ctx->s_out, site.ws_off, site.ws_len};
-            // an error after the fork must not leave work (or the caller's buffers) in flight on the side streams
-            auto bail = [&](int code) {
-                (void)hipStreamSynchronize(ctx->s_in);
-                (void)hipStreamSynchronize(ctx->s_out);
-                return code;
-            };
-            GPC_HIP(ctx, hipEventRecord(ctx->ev[0][GPC_EV_CLASS_FORK], main_s));
-            GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_in, ctx->ev[0][GPC_EV_CLASS_FORK], 0));
-            GPC_HIP(ctx, hipStreamWaitEvent(ctx->s_out, ctx->ev[0][GPC_EV_CLASS_FORK], 0));
-            // largest patches first: the tiled kernel's workgroups are the long ones
-            if (need_big) {
-                DenseArgs b = a;
-                b.sel = sel2; b.sel_count = counts + 2;
-                rc = dense_big_launch(ctx, on_out, b, grid_b);
-                if (rc != GPC_OK) return bail(rc);
-            }
-            // Class `which` (0: n <= 256, 1: the NT = 17 shape) on the register kernel, `cnt` workgroups at `at`.  Without a hint cnt is P: the
-            // workgroups beyond the class count leave at once, but each still waits for a CU with 158 KB of LDS free.  With one, the overflow
-            // launch follows on the same stream; a class the hint calls empty is its overflow launch alone, on the main stream.
-            auto run_class = [&](int which, int cnt, const DenseSite& at) -> int {
-                DenseArgs s = a;
-                s.n_max = which ? 17 * 16 : 256;
-                s.sel = which ? sel1 : sel0; s.sel_count = counts + which;
-                s.P = cnt;
-                const int rcl = cnt > 0 ? dense_mfma_launch(ctx, at, s) : GPC_OK;
-                if (rcl != GPC_OK || !hinted || cnt >= a.P) return rcl;
-                s.sel_base = cnt;
-                s.P = a.P;
-                return dense_generic_launch(ctx, cnt > 0 ? at : site, s, OVF_GRID, ovf_ws + (size_t)which * OVF_GRID * (ovf_slot / sizeof(double)));
-            };
-            const int c0 = hinted ? ctx->hint_le256 : a.P;
-            const int c1 = hinted ? ctx->hint_le272 - ctx->hint_le256 : a.P;
-            if (nt17 && (rc = run_class(1, c1, on_in)) != GPC_OK) return bail(rc);
-            if ((rc = run_class(0, c0, site)) != GPC_OK) return bail(rc);
-            GPC_HIP(ctx, hipEventRecord(ctx->ev[1][GPC_EV_CLASS_FORK], ctx->s_in));
-            GPC_HIP(ctx, hipEventRecord(ctx->ev[2][GPC_EV_CLASS_FORK], ctx->s_out));
-            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[1][GPC_EV_CLASS_FORK], 0));
-            GPC_HIP(ctx, hipStreamWaitEvent(main_s, ctx->ev[2][GPC_EV_CLASS_FORK], 0));
-            ctx->last_dense_kernel = !need_big ? "dense_mfma_nt16 + dense_mfma_nt17" : nt17 ? "dense_mfma_nt16 + dense_mfma_nt17 + dense_mfma_big"
-                                                                                             : "dense_mfma_nt16 + dense_mfma_big";
+        } else if (rc != GPC_OK) {
             return rc;
         }
     }
-    if ((dense_big_supported(a) || (force_big && a.n_max <= 1024 && !a.v_star)) && !force_generic) {   // GPC_FORCE_BIG: diagnostic
-        int grid_b = 0;
-        if (int rcb = dense_big_reserve(ctx, site, a, &grid_b)) return rcb;
-        return dense_big_launch(ctx, site, a, grid_b);
+    switch (route.kind) {
+        case DENSE_ONE_WAVE:
+            rc = dense_w1_launch(ctx, site, a, route, grid);
+            break;
+        case DENSE_REGISTER:                                    // one shape for the whole batch
+            rc = dense_mfma_launch(ctx, site, a, route);
+            break;
+        case DENSE_TILED:
+            if ((rc = gpc_ws_reserve(ctx, site, al256(dense_big_ws_bytes(ctx, a, route, &grid)))) == GPC_OK)
+                rc = dense_big_launch(ctx, site, a, route, grid);
+            break;
+        case DENSE_SPLIT:
+            rc = dense_split(ctx, a, site, route, sw.no_hint);
+            break;
+        case DENSE_GENERIC:
+            if ((rc = gpc_ws_reserve(ctx, site, dense_generic_ws_bytes(ctx, a, &grid))) == GPC_OK)
+                rc = dense_generic_launch(ctx, site, a, grid);
+            break;
+        default:
+            return gpc_fail(ctx, GPC_EINVAL, "no route for this batch");
     }
-    int grid = 0;
-    size_t bytes = dense_generic_ws_bytes(ctx, a, &grid);
-    int rc = gpc_ws_reserve(ctx, site, bytes);
-    if (rc != GPC_OK) return rc;
-    return dense_generic_launch(ctx, site, a, grid);
+    if (rc == GPC_OK) ctx->last_dense_kernel = route.name;
+    return rc;
 }
 
 extern "C" {
@@ -264,9 +247,11 @@ int gpc_dense_irls_fit_predict_dev(gpc_ctx* ctx, const gpc_params* params, const
     const DenseSite site = dense_site_of(ctx);
     GPC_HIP(ctx, hipSetDevice(ctx->device));
     if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
+    const DenseRoute route = dense_route(dense_facts(ctx, a, true), dense_switches_read());
     int grid_b = 0;
-    if ((rc = dense_big_reserve(ctx, site, a, &grid_b))) return rc;
-    return dense_irls_launch(ctx, site, a, ir, grid_b);
+    if ((rc = gpc_ws_reserve(ctx, site, al256(dense_big_ws_bytes(ctx, a, route, &grid_b))))) return rc;
+    if ((rc = dense_irls_launch(ctx, site, a, route, ir, grid_b)) == GPC_OK) ctx->last_dense_kernel = route.name;
+    return rc;
 }
 
 int gpc_dense_irls_fit_predict(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
@@ -306,6 +291,20 @@ int gpc_dense_irls_fit_predict(gpc_ctx* ctx, const gpc_params* params, const gpc
     st.down(iters, d_it, Pz);
     st.down(status, d_st, Pz);
     return st.finish();
+}
+
+// host-only test hook: dense_route for the given facts under the switches of the environment (no HIP call: works without a GPU)
+int gpc_test_dense_route(int P, int n_max, int n_total, int ny, int m, int variance, int pointwise, int alpha_out, int num_cus, int irls,
+                         int w1_refused, char* name, int name_cap, int32_t* shape)
+{
+    const DenseFacts f{P, n_max, n_total, ny, m, variance != 0, pointwise != 0, alpha_out != 0, num_cus, irls != 0};
+    const DenseRoute r = dense_route(f, dense_switches_read(), w1_refused != 0);
+    if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s", r.name);
+    if (shape) {
+        const int32_t v[GPC_TEST_ROUTE_SHAPE] = {r.w1_npad, r.w1_slots, r.nt, r.export_factor, r.waves, r.npad, r.per_cu, r.nt17, r.need_big};
+        memcpy(shape, v, sizeof(v));
+    }
+    return (int)r.kind;
 }
 
 }  // extern "C"

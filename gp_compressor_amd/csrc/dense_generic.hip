@@ -374,6 +374,5 @@ int dense_generic_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL(dense_generic_kernel, dim3(grid), dim3(GEN_THREADS), lds, site.stream, g);
     GPC_HIP(ctx, hipGetLastError());
-    ctx->last_dense_kernel = "dense_generic";
     return GPC_OK;
 }

@@ -134,7 +134,8 @@ static int dense_host(gpc_ctx* ctx, const gpc_params* params, int P, const int32
     const bool want_v = !grid && params->want_variance && v_star;
     const size_t N = (size_t)n_total;
     // (chunks of at least 1024 patches: below four patches per CU the dense dispatch leaves the one-wave-per-patch kernel)
-    int C = getenv("GPC_HOST_NO_PIPELINE") ? 1 : P >= 4096 ? 4 : P >= 2048 ? 2 : 1;
+    const DenseSwitches sw = dense_switches_read();
+    int C = sw.host_no_pipeline ? 1 : P >= 4096 ? 4 : P >= 2048 ? 2 : 1;
     // Round 4: when the one-wave kernel takes the chunks, the kernels of consecutive chunks run on TWO streams, each in its own half of
     // the workspace (one factor slot per patch of a chunk), so that a chunk's draining workgroups and the next chunk's first ones share
     // the chip -- a chunk of 1024 .. 2048 patches is a single round of resident workgroups, i.e. all ramp and tail -- and the batch goes
@@ -154,30 +155,25 @@ static int dense_host(gpc_ctx* ctx, const gpc_params* params, int P, const int32
     } pipe{ctx, false};
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        DenseArgs probe{};
-        probe.prm = *params;
-        probe.P = P / 8; probe.n_max = n_max; probe.ny = ny; probe.m = m;
-        probe.n_total = n_total;                       // (upper bound of a chunk's: the variance path keeps one weight per point in its half)
-        probe.v_star = want_v ? v_star : nullptr;
-        probe.xs0 = grid ? nullptr : xs0;
+        // the facts of a chunk (n_total: an upper bound of a chunk's -- the variance path keeps one weight per point in its half)
+        DenseFacts chunk{(P + 7) / 8, n_max, n_total, ny, m, want_v, !grid && xs0, false, ctx->num_cus, false};
         // (measured on the C2 batch, same box: 1.95 against 2.12 ms per call, 4.2 against 3.87 M patches/s PCIe-inclusive; at 128 points per
         // patch the kernel is a third of the call and eight chunks only add transfers' fixed costs -- 1.09 against 0.96 ms -- hence n_max > 160)
         // EVERY chunk must go to the one-wave kernel: the halves are sized for its factor slots, and a chunk that reserved more (small
         // patches with the variance wanted go to the register kernel and its factor export) would move the workspace under the other
         // stream's chunk
-        bool all_w1 = C == 4 && P >= 8192 && n_max > 160 && !alpha_out && !getenv("GPC_HOST_ONE_STREAM") && ctx->own_stream != nullptr;
+        bool all_w1 = C == 4 && P >= 8192 && n_max > 160 && !alpha_out && !sw.host_one_stream && ctx->own_stream != nullptr;
         for (int c = 0; c < 8 && all_w1; ++c) {
             const int p0 = (int)((long long)P * c / 8), p1 = (int)((long long)P * (c + 1) / 8);
-            int nm = 1;
-            for (int i = p0; i < p1; ++i) nm = std::max(nm, off[i + 1] - off[i]);
-            DenseArgs pc = probe;
-            pc.P = p1 - p0;
-            pc.n_max = nm;
-            all_w1 = dense_w1_takes(ctx, pc);
+            DenseFacts fc = chunk;
+            fc.P = p1 - p0;
+            fc.n_max = 1;
+            for (int i = p0; i < p1; ++i) fc.n_max = std::max(fc.n_max, off[i + 1] - off[i]);
+            all_w1 = dense_route(fc, sw).kind == DENSE_ONE_WAVE;
         }
         if (all_w1) {
-            probe.P = (P + 7) / 8;
-            half = (dense_w1_ws_bytes(ctx, probe, nullptr) + 255) & ~(size_t)255;
+            // the halves: the one-wave kernel's workspace for the largest chunk ((P + 7) / 8 patches of up to n_max points)
+            half = (dense_w1_ws_bytes(chunk, dense_route(chunk, sw), nullptr) + 255) & ~(size_t)255;
             if (gpc_ws_reserve(ctx, 2 * half) == GPC_OK) {
                 two = true;
                 C = 8;

@@ -1,8 +1,10 @@
 // dense_internal.h -- host-side definitions of the dense path: the arguments of a batch, where a call runs, the dispatcher and the
-// launchers of the kernel translation units (not part of the C-ABI).
+// launchers of the kernel translation units (not part of the C-ABI).  Which kernel a batch runs on is decided in dense_route.h; the
+// dispatcher executes that route and every launcher takes its shape from it.
 #pragma once
 
 #include "gpc_internal.h"
+#include "dense_route.h"
 
 struct DenseArgs {
     gpc_params prm;
@@ -53,10 +55,14 @@ int dense_check(gpc_ctx* ctx, const gpc_params* prm, int P, const void* off, int
 // the device-pointer arguments shared by the dense and IRLS entries; the rest of DenseArgs stays zero
 DenseArgs dense_args(const gpc_params* prm, int P, const int32_t* off, int n_max, int n_total, const double* x0, const double* x1,
                      const double* y, int ny, int m, double* f_star, double* alpha_out, int32_t* status);
-// the one-wave kernel takes this batch (the rule of dense_dispatch, also asked by dense_host before it splits a batch over two streams)
-bool dense_w1_takes(const gpc_ctx* ctx, const DenseArgs& a);
-// Chooses the kernels of a batch and launches them at `site`; caller holds ctx->mu.  `seen_gen`: a chunk of the two-stream host-pointer
-// pipeline hands in gpc_ctx::foreign_gen as its compute stream last saw it (gpc_pipe_chunk_order); nullptr everywhere else.
+// what dense_route looks at, of a batch as its entry point received it
+static inline DenseFacts dense_facts(const gpc_ctx* ctx, const DenseArgs& a, bool irls = false)
+{
+    return DenseFacts{a.P, a.n_max, a.n_total, a.ny, a.m, a.prm.want_variance && a.v_star, a.xs0 != nullptr, a.alpha_out != nullptr,
+                      ctx->num_cus, irls};
+}
+// Asks dense_route for the kernels of a batch and launches them at `site`; caller holds ctx->mu.  `seen_gen`: a chunk of the two-stream
+// host-pointer pipeline hands in gpc_ctx::foreign_gen as its compute stream last saw it (gpc_pipe_chunk_order); nullptr everywhere else.
 int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* seen_gen = nullptr);
 
 // ---- launchers implemented in the kernel translation units -------------------------------------------------
@@ -66,12 +72,12 @@ size_t dense_generic_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_
 int dense_generic_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid, double* ws_override = nullptr);
 
 // register-tile MFMA kernel: n <= 256, trailing matrix resident in VGPRs (see dense_mfma.hip)
-bool dense_mfma_supported(const DenseArgs& a);
-int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a);
+int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r);
 
 // predictive variance from the exported factor of the register-tile kernel (dense_variance.hip): V* [P][m]
-int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int nt_max, const double* factor, const double* alpha,
-                          double* v_star);
+// (var_w4: DenseSwitches::var_w4)
+int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int nt_max, int var_w4, const double* factor,
+                          const double* alpha, double* v_star);
 
 // ... and from the tiled kernel's per-patch factor slots (n <= 1024); scratch: V blocks of the waves in flight
 size_t big_slot_doubles(int ntw);
@@ -80,13 +86,12 @@ int dense_variance_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseAr
                               const double* alpha, double* scratch, double* v_star);
 
 // tiled left-looking MFMA kernel: 256 < n <= 1024, factor in a global-memory workspace slot per workgroup (see dense_mfma_big.hip)
-bool dense_big_supported(const DenseArgs& a);
-size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out);
-int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid);
+size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, const DenseRoute& r, int* grid_out);
+int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, int grid);
 // one wave per patch, eight patches per CU: n <= 256, depth plane, mean only (see dense_mfma_w1.hip) -- the C2 headline kernel
-bool dense_w1_supported(const DenseArgs& a);
-size_t dense_w1_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out, int cap = 0);
-int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid);
+// (cap > 0: fewer factor slots than the route's, the dispatcher's retry after GPC_ENOMEM)
+size_t dense_w1_ws_bytes(const DenseFacts& f, const DenseRoute& r, int* grid_out, int cap = 0);
+int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, int grid);
 // the same kernel inside the Newton / IRLS loop of the probit variant (BASELINE config 5; any n <= 1024, ny == 1)
 struct IrlsArgs {
     int max_iter;
@@ -94,4 +99,4 @@ struct IrlsArgs {
     int32_t* iters;   // [P] or nullptr
     double* fhat;     // [n_total] or nullptr
 };
-int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const IrlsArgs& ir, int grid);
+int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, const IrlsArgs& ir, int grid);

@@ -873,15 +873,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void dense_mfma_kernel(MfmaParams g)
     } while (0);
 }
 
-bool dense_mfma_supported(const DenseArgs& a)
-{
-    // n <= 256 for depth and colour; n <= 272 for the depth plane alone (NT = 17, see the LDS carve); the variance path exports
-    // the factor of the n <= 256 shapes only
-    return (a.n_max <= MF_NPAD || (a.n_max <= 17 * MF_TS && a.ny == 1 && a.v_star == nullptr)) && (a.ny == 1 || a.ny == 3);
-}
-
 template <int NT, bool EXPORT = false>
-static int launch_nt(gpc_ctx* ctx, hipStream_t stream, const MfmaParams& g, int grid, const char* name)
+static int launch_nt(gpc_ctx* ctx, hipStream_t stream, const MfmaParams& g, int grid)
 {
     const size_t lds = sizeof(double) * (size_t)mf_l_total(NT);
     // per call: the attribute is per device, and a process may hold contexts on several GPUs (idempotent, host-side only)
@@ -889,19 +882,18 @@ static int launch_nt(gpc_ctx* ctx, hipStream_t stream, const MfmaParams& g, int 
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL((dense_mfma_kernel<NT, EXPORT>), dim3(grid), dim3(MF_THREADS), lds, stream, g);
     GPC_HIP(ctx, hipGetLastError());
-    ctx->last_dense_kernel = name;
     return GPC_OK;
 }
 
 // Predictive variance (gaussian_process::predict_measurements, /root/reference/src/gaussian_process.cpp:35-43): the fit runs as
 // usual and additionally writes its factor (operand images of every L_ik and of the L_ii^-1) into the context's workspace,
 // 272 KB per patch at NT = 16; dense_variance.hip then evaluates V* = k** - ||L^-1 k*||^2 from there.
-int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in)
+int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, const DenseRoute& r)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
     a.v_star = nullptr;
-    const int nt_max = a.n_max <= 64 ? 4 : a.n_max <= 128 ? 8 : a.n_max <= 192 ? 12 : 16;
+    const int nt_max = r.nt;      // (the factor is exported by the n <= 256 shapes only: 4 .. 16)
     size_t fbytes = 0;
     if (v_star) {
         if (a.sel) return gpc_fail(ctx, GPC_EINVAL, "variance + size-class dispatch is not supported");
@@ -1006,18 +998,20 @@ int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in
 #endif
     if (v_star) {
         int rc;
-        if (nt_max == 4) rc = launch_nt<4, true>(ctx, site.stream, g, grid, "dense_mfma_nt4 + dense_variance");
-        else if (nt_max == 8) rc = launch_nt<8, true>(ctx, site.stream, g, grid, "dense_mfma_nt8 + dense_variance");
-        else if (nt_max == 12) rc = launch_nt<12, true>(ctx, site.stream, g, grid, "dense_mfma_nt12 + dense_variance");
-        else rc = launch_nt<16, true>(ctx, site.stream, g, grid, "dense_mfma_nt16 + dense_variance");
+        if (nt_max == 4) rc = launch_nt<4, true>(ctx, site.stream, g, grid);
+        else if (nt_max == 8) rc = launch_nt<8, true>(ctx, site.stream, g, grid);
+        else if (nt_max == 12) rc = launch_nt<12, true>(ctx, site.stream, g, grid);
+        else rc = launch_nt<16, true>(ctx, site.stream, g, grid);
         if (rc != GPC_OK) return rc;
         DenseArgs av = a;
         av.m = a_in.m;
-        return dense_variance_launch(ctx, site, av, nt_max, g.export_L, a.alpha_out, v_star);
+        return dense_variance_launch(ctx, site, av, nt_max, r.var_w4, g.export_L, a.alpha_out, v_star);
     }
-    if (a.n_max <= 64) return launch_nt<4>(ctx, site.stream, g, grid, "dense_mfma_nt4");
-    if (a.n_max <= 128) return launch_nt<8>(ctx, site.stream, g, grid, "dense_mfma_nt8");
-    if (a.n_max <= 192) return launch_nt<12>(ctx, site.stream, g, grid, "dense_mfma_nt12");
-    if (a.n_max <= 256) return launch_nt<16>(ctx, site.stream, g, grid, "dense_mfma_nt16");
-    return launch_nt<17>(ctx, site.stream, g, grid, "dense_mfma_nt17");
+    switch (nt_max) {
+        case 4: return launch_nt<4>(ctx, site.stream, g, grid);
+        case 8: return launch_nt<8>(ctx, site.stream, g, grid);
+        case 12: return launch_nt<12>(ctx, site.stream, g, grid);
+        case 16: return launch_nt<16>(ctx, site.stream, g, grid);
+        default: return launch_nt<17>(ctx, site.stream, g, grid);
+    }
 }

@@ -950,39 +950,13 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
     }
 }
 
-bool dense_big_supported(const DenseArgs& a)
-{
-    // (with the variance: point-wise X* only -- the variance entry has no grid form)
-    return a.n_max > 256 && a.n_max <= 1024 && (a.v_star == nullptr || a.xs0 != nullptr) && (a.ny == 1 || a.ny == 3);
-}
-
 size_t big_slot_doubles(int ntw) { return ((size_t)(ntw + 1) * ntw + 2 * (size_t)ntw) * MF_IMG; }
 
-// <8 waves, 1024 points, 2 rows per pass, 2 waves/SIMD>: 103 KB of LDS, one workgroup per CU: 256 < n <= 1024.
-// <4 waves, 256 points, 2 rows per pass, 2 waves/SIMD>: 37 KB of LDS, two workgroups = two patches per CU: the cross-check
-// shape for n <= 256 (GPC_FORCE_BIG=1).  (A 1-row, <= 128-VGPR variant with FOUR patches per CU was measured slower, 2.45 M
-// against 2.68 M patches/s on C2: each workgroup runs 2.2x longer -- the shape is bound by the factor stream, not by latency.)
-static void big_shape(const DenseArgs& a, bool irls, int* waves, int* npad, int* per_cu)
+// (the instances and how many workgroups of each a CU holds: dense_route_tiled, dense_route.h)
+size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, const DenseRoute& r, int* grid_out)
 {
-    // depth plane, n <= 256: TWO waves per workgroup (the chain wave + one worker) and FOUR workgroups per CU (40 KB of LDS each)
-    if (a.n_max <= 256 && a.ny == 1 && !irls && !a.v_star && !getenv("GPC_BIG_NO_W2")) { *waves = 2; *npad = 256; *per_cu = 4; }
-    else if (a.n_max <= 256) { *waves = 4; *npad = 256; *per_cu = 2; }
-    // (the two-wave shape at 512 points, three workgroups per CU at 50 KB of LDS: 16.0 ms on C3 against 12.2 -- six waves per CU, and
-    // one worker cannot carry a step's 28 row passes)
-    // depth plane only, up to 512 points: four waves, two patches per CU (62 KB of LDS each).  Measured on the producer's own batches
-    // (273 .. 324 points): GP phase 3.29 against 3.42 ms.  At n = 512 (C3) the 8-wave shape used to win, 13.2 against 13.4 ms -- both
-    // chain waves sat on SIMD 0, which then idled; with the second workgroup's chain on SIMD 2 (HW_ID wave slot, see the kernel) the
-    // two-workgroup shape wins, 12.23 against 12.63 ms on the same box (round 3)
-    else if (a.n_max <= 512 && a.ny == 1 && !irls && !getenv("GPC_BIG_NO_W4")) { *waves = 4; *npad = 512; *per_cu = 2; }
-    else { *waves = 8; *npad = 1024; *per_cu = 1; }
-}
-
-size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out)
-{
-    int waves, npad, per_cu;
-    big_shape(a, false, &waves, &npad, &per_cu);
     const int ntw = (a.n_max + MF_TS - 1) / MF_TS;
-    const int cap = ctx->num_cus * per_cu;
+    const int cap = ctx->num_cus * r.per_cu;
     const int grid = a.P < cap ? a.P : cap;
     if (grid_out) *grid_out = grid;
     // with the variance requested the factor of every patch is kept (one slot per patch) + alpha + the per-wave V scratch of
@@ -1005,7 +979,7 @@ static int big_launch_t(gpc_ctx* ctx, hipStream_t stream, const BigParams& g, in
 }
 
 // BASELINE config 5: the Newton / IRLS loop around the tiled factorisation (any n <= 1024; the 4-wave shape for n <= 256)
-int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const IrlsArgs& ir, int grid)
+int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, const IrlsArgs& ir, int grid)
 {
     BigParams g;
     g.a = a;
@@ -1025,17 +999,11 @@ int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, c
     if (!ctx->tickets) GPC_HIP(ctx, hipMalloc(&ctx->tickets, 64 * sizeof(int32_t)));
     GPC_HIP(ctx, hipMemsetAsync(ctx->tickets, 0, sizeof(int32_t), site.stream));
     g.ticket = ctx->tickets;
-    int waves, npad, per_cu;
-    big_shape(a, true, &waves, &npad, &per_cu);
-    if (waves == 4) {
-        ctx->last_dense_kernel = "dense_mfma_big_w4_irls";
-        return big_launch_t<4, 256, 2, 2, true>(ctx, site.stream, g, grid);
-    }
-    ctx->last_dense_kernel = "dense_mfma_big_irls";
+    if (r.waves == 4) return big_launch_t<4, 256, 2, 2, true>(ctx, site.stream, g, grid);
     return big_launch_t<8, 1024, 2, 2, true>(ctx, site.stream, g, grid);
 }
 
-int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, int grid)
+int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, const DenseRoute& r, int grid)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
@@ -1056,8 +1024,7 @@ int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in,
     g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
     g.ntw = (a.n_max + MF_TS - 1) / MF_TS;
     g.slot = big_slot_doubles(g.ntw);
-    int waves, npad, per_cu;
-    big_shape(a, false, &waves, &npad, &per_cu);
+    const int waves = r.waves, npad = r.npad;
     g.stamps = nullptr;
     g.irls_model = 0; g.irls_max_iter = 0; g.irls_tol = 0.0; g.irls_f_init = 0.0; g.irls_iters = nullptr; g.irls_fhat = nullptr;
     g.ticket = nullptr;
@@ -1085,22 +1052,10 @@ int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in,
         GPC_HIP(ctx, hipMemsetAsync(g.stamps, 0, sizeof(unsigned long long) * BG_NPH * 8, site.stream));
         dump.d = g.stamps;
     }
-    if (waves == 2) {
-        ctx->last_dense_kernel = "dense_mfma_big_w2";
-        return big_launch_t<2, 256, 2, 2, false, 1>(ctx, site.stream, g, grid);
-    }
-    if (waves == 4 && npad == 256) {
-        ctx->last_dense_kernel = "dense_mfma_big_w4";
-        return big_launch_t<4, 256, 2, 2>(ctx, site.stream, g, grid);
-    }
-    int rc;
-    if (waves == 4) {
-        ctx->last_dense_kernel = v_star ? "dense_mfma_big + dense_variance_big" : "dense_mfma_big";      // (the shape is not part of the name)
-        rc = big_launch_t<4, 512, 2, 2, false, 1>(ctx, site.stream, g, grid);
-    } else {
-        ctx->last_dense_kernel = v_star ? "dense_mfma_big + dense_variance_big" : "dense_mfma_big";
-        rc = big_launch_t<8, 1024, 2, 2>(ctx, site.stream, g, grid);
-    }
+    if (waves == 2) return big_launch_t<2, 256, 2, 2, false, 1>(ctx, site.stream, g, grid);
+    if (waves == 4 && npad == 256) return big_launch_t<4, 256, 2, 2>(ctx, site.stream, g, grid);
+    const int rc = waves == 4 ? big_launch_t<4, 512, 2, 2, false, 1>(ctx, site.stream, g, grid)
+                              : big_launch_t<8, 1024, 2, 2>(ctx, site.stream, g, grid);
     if (rc != GPC_OK || !v_star) return rc;
     DenseArgs av = a;
     av.m = a_in.m;

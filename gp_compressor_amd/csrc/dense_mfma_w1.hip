@@ -840,39 +840,23 @@ __global__ __launch_bounds__(64, 2) void dense_w1_kernel(W1Params g)
     }
 }
 
-static int w1_npad(const DenseArgs& a) { return a.n_max <= 256 ? 256 : W1_NPAD_MAX; }
-
-bool dense_w1_supported(const DenseArgs& a)
-{
-    // (with the variance: point-wise X* only -- the variance entry has no grid form -- and n <= 256: the 512-point instance's slots
-    // are not the layout dense_variance_big_kernel reads)
-    if (a.v_star) return a.n_max <= 256 && a.ny == 1 && !a.sel && a.xs0 != nullptr;
-    return a.n_max <= W1_NPAD_MAX && a.ny == 1 && !a.sel;
-}
+static_assert(W1_NPAD_MAX == 512, "dense_route (dense_route.h) names the instances: 256 and 512 points");
 
 // One factor slot per patch of a launch (288 KB: 2.4 GB for the 8192 patches of BASELINE config 2 -- sized for 288 GB); a larger
-// batch goes through in launches of W1_MAX_SLOTS patches that reuse the slots (a launch of 8192 patches is four rounds of the 2048
-// resident workgroups: its ramp and tail are ~3 % of it).  `cap` > 0: the dispatcher's retry with fewer slots after GPC_ENOMEM.
-#define W1_MAX_SLOTS 8192
-static int w1_chunk(const DenseArgs& a, int cap_in)
+// batch goes through in launches of r.w1_slots patches (DENSE_W1_MAX_SLOTS unless GPC_W1_SLOTS says otherwise) that reuse the slots
+// (a launch of 8192 patches is four rounds of the 2048 resident workgroups: its ramp and tail are ~3 % of it).  `cap_in` > 0: the
+// dispatcher's retry with fewer slots after GPC_ENOMEM.
+size_t dense_w1_ws_bytes(const DenseFacts& f, const DenseRoute& r, int* grid_out, int cap_in)
 {
-    const char* e = getenv("GPC_W1_SLOTS");
-    int cap = e && atoi(e) > 0 ? atoi(e) : W1_MAX_SLOTS;
-    if (cap_in > 0 && cap_in < cap) cap = cap_in;
-    return a.P < cap ? a.P : cap;
-}
-
-size_t dense_w1_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_out, int cap)
-{
-    (void)ctx;
-    const int grid = w1_chunk(a, cap);
+    const int cap = cap_in > 0 && cap_in < r.w1_slots ? cap_in : r.w1_slots;
+    const int grid = f.P < cap ? f.P : cap;
     if (grid_out) *grid_out = grid;
     // factor slots | L_kk^-T images | (variance without alpha_out: the weights the variance kernel forms the mean from)
-    const int npad = w1_npad(a);
-    return sizeof(double) * ((size_t)(W1_TRI_OF(npad) + W1_LNV_OF(npad)) * MF_IMG * (size_t)grid + (a.v_star ? (size_t)a.n_total : 0));
+    const int npad = r.w1_npad;
+    return sizeof(double) * ((size_t)(W1_TRI_OF(npad) + W1_LNV_OF(npad)) * MF_IMG * (size_t)grid + (f.variance ? (size_t)f.n_total : 0));
 }
 
-int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, int grid)
+int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, const DenseRoute& r, int grid)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
@@ -880,7 +864,7 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, 
     W1Params g;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
-    const int npad = w1_npad(a);
+    const int npad = r.w1_npad;
     g.linvt = g.ws + (size_t)W1_TRI_OF(npad) * MF_IMG * (size_t)grid;
     g.export_factor = v_star ? 1 : 0;
     const double sf = a.prm.sigmaf_sq;
@@ -897,7 +881,6 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, 
         a.m = 0;
         if (!a.alpha_out) a.alpha_out = g.linvt + (size_t)W1_LNV_OF(npad) * MF_IMG * (size_t)grid;
     }
-    ctx->last_dense_kernel = v_star ? "dense_mfma_w1 + dense_variance" : npad == 256 ? "dense_mfma_w1" : "dense_mfma_w1_512";
 #ifdef W1_STAMPS
     if (getenv("GPC_W1_STAMPS")) {
         GPC_HIP(ctx, hipMalloc(&g.stamps, sizeof(unsigned long long) * W1_NPH));
@@ -919,7 +902,7 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, 
         if (v_star) {
             DenseArgs av = g.a;
             av.m = a_in.m;
-            const int rc = dense_variance_launch(ctx, site, av, W1_NT_OF(256), g.ws, a.alpha_out, v_star + (size_t)base * a_in.m);
+            const int rc = dense_variance_launch(ctx, site, av, W1_NT_OF(256), r.var_w4, g.ws, a.alpha_out, v_star + (size_t)base * a_in.m);
             if (rc != GPC_OK) return rc;
         }
     }

@@ -229,22 +229,22 @@ __global__ __launch_bounds__(64 * WV, 2) void dense_variance_kernel(VarParams g)
 }
 
 template <int NT>
-static int var_launch_t(gpc_ctx* ctx, hipStream_t stream, const VarParams& g, int grid)
+static int var_launch_t(gpc_ctx* ctx, hipStream_t stream, const VarParams& g, int grid, int var_w4)
 {
     // four waves per workgroup (two workgroups per CU) when that fills the rounds markedly better: m = 400 is 25 blocks -- 0.78 of
     // the wave slots in rounds of eight, 0.89 in rounds of four (C2 + variance 8.22 -> 8.06 ms; the factor is streamed 7 times
     // instead of 4, which eats most of the gain)
     const int nblk = (g.a.m + MF_TS - 1) / MF_TS;
     const double eff8 = (double)nblk / (8 * ((nblk + 7) / 8)), eff4 = (double)nblk / (4 * ((nblk + 3) / 4));
-    const bool w4 = getenv("GPC_VAR_W4") ? atoi(getenv("GPC_VAR_W4")) != 0 : eff4 > eff8 + 0.08;
+    const bool w4 = var_w4 >= 0 ? var_w4 != 0 : eff4 > eff8 + 0.08;       // (GPC_VAR_W4 = 0 / 1 overrides the rule)
     if (w4) hipLaunchKernelGGL((dense_variance_kernel<NT, 4>), dim3(grid), dim3(256), 0, stream, g);
     else hipLaunchKernelGGL((dense_variance_kernel<NT, 8>), dim3(grid), dim3(DV_THREADS), 0, stream, g);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }
 
-int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int nt_max, const double* factor, const double* alpha,
-                          double* v_star)
+int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int nt_max, int var_w4, const double* factor,
+                          const double* alpha, double* v_star)
 {
     if (a.P == 0 || a.m == 0) return GPC_OK;
     if (!a.xs0 || !a.xs1) return gpc_fail(ctx, GPC_EINVAL, "the predictive variance needs point-wise X*");
@@ -255,10 +255,10 @@ int dense_variance_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& 
     g.alpha = alpha;
     g.v_star = v_star;
     switch (nt_max) {
-        case 4: return var_launch_t<4>(ctx, site.stream, g, a.P);
-        case 8: return var_launch_t<8>(ctx, site.stream, g, a.P);
-        case 12: return var_launch_t<12>(ctx, site.stream, g, a.P);
-        default: return var_launch_t<16>(ctx, site.stream, g, a.P);
+        case 4: return var_launch_t<4>(ctx, site.stream, g, a.P, var_w4);
+        case 8: return var_launch_t<8>(ctx, site.stream, g, a.P, var_w4);
+        case 12: return var_launch_t<12>(ctx, site.stream, g, a.P, var_w4);
+        default: return var_launch_t<16>(ctx, site.stream, g, a.P, var_w4);
     }
 }
 

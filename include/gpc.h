@@ -597,6 +597,16 @@ void gpc_test_exp_host(const double* x, double* out, int n);
 void gpc_test_exp_small_host(const double* x, double* out, int n);
 /* the multi-threaded staging copy of the host-pointer entries (pageable caller buffers), callable without a GPU: concurrency test */
 void gpc_test_par_memcpy(void* dst, const void* src, size_t bytes);
+/* The rule that chooses the kernels of a dense batch, callable without a GPU.  The facts of the batch: its sizes, whether the
+ * variance is computed, point-wise (1) or grid (0) X*, whether the weights are wanted, the device's CU count, the IRLS entry (1) or
+ * the plain one (0); w1_refused: the route after the one-wave kernel's workspace was refused.  The GPC_* switches are read from the
+ * environment, as by the entry points.  Returns the kind (-1 no route, 0 nothing to do, 1 one-wave, 2 register, 3 tiled, 4 generic,
+ * 5 size-class split); name (if not NULL, name_cap bytes) receives what gpc_last_dense_kernel would report; shape (if not NULL,
+ * GPC_TEST_ROUTE_SHAPE entries): one-wave padding and slots per launch | register tile count, factor exported | tiled waves, padding,
+ * workgroups per CU | split: with the 257..272 class, with the tiled class. */
+#define GPC_TEST_ROUTE_SHAPE 9
+int gpc_test_dense_route(int P, int n_max, int n_total, int ny, int m, int variance, int pointwise, int alpha_out, int num_cus,
+                         int irls, int w1_refused, char* name, int name_cap, int32_t* shape);
 
 #ifdef __cplusplus
 }

@@ -67,7 +67,7 @@ def kernel_choice(request, monkeypatch):
     (its two-wave / four-workgroups-per-CU shape below 257 points for the depth plane), with the register-tile kernel for every
     n <= 256 ("reg": GPC_NO_W1), with the tiled kernel's four-wave shape ("big_w4"), and with the two-wave shape where round 3's first
     headline ran it ("w2": GPC_W2, depth plane of 193 .. 256 points).  The environment is read at every call."""
-    for e in ("GPC_FORCE_GENERIC", "GPC_FORCE_BIG", "GPC_NO_W2", "GPC_BIG_NO_W2", "GPC_NO_W1", "GPC_W2", "GPC_W1_MIN_P"):
+    for e in ("GPC_FORCE_GENERIC", "GPC_FORCE_BIG", "GPC_BIG_NO_W2", "GPC_NO_W1", "GPC_W2", "GPC_W1_MIN_P"):
         monkeypatch.delenv(e, raising=False)
     if request.param == "dispatch":
         monkeypatch.setenv("GPC_W1_MIN_P", "2")
@@ -338,6 +338,37 @@ def test_dense_batch_size_rule(gp, oracle, monkeypatch):
         fo, _, so = oracle.dense_fit_predict_batch(oracle.dense_params(), sub, x0[idx], x1[idx], y[:, idx], xs0, xs1)
         assert np.all(st == 0)
         _close(f[pick], fo, FTOL)
+
+
+ROUTE_SWITCHES = ("GPC_FORCE_GENERIC", "GPC_FORCE_BIG", "GPC_NO_W1", "GPC_NO_W1_512", "GPC_W2", "GPC_W1_MIN_P", "GPC_W1_SLOTS", "GPC_NO_SPLIT",
+                  "GPC_NO_NT17", "GPC_NO_HINT", "GPC_BIG_NO_W2", "GPC_BIG_NO_W4")
+
+
+@pytest.mark.parametrize("switch,P,n,ny,ragged,var", [
+    ("", 40, 17, 1, True, False), ("", 9, 64, 3, True, False), ("", 12, 200, 1, True, False), ("", 5, 256, 1, False, False),
+    ("", 8, 270, 1, True, False), ("", 6, 300, 1, True, False), ("", 6, 300, 3, True, False), ("", 2, 512, 1, False, False),
+    ("", 7, 200, 1, True, True), ("GPC_W1_MIN_P", 7, 256, 1, False, True),
+    ("GPC_W1_MIN_P", 2, 256, 1, False, False), ("GPC_W1_MIN_P", 9, 64, 1, True, False), ("GPC_W1_MIN_P", 3, 512, 1, False, False),
+    ("GPC_W1_MIN_P", 6, 300, 1, True, False), ("GPC_NO_W1", 5, 256, 1, True, False), ("GPC_NO_SPLIT", 6, 300, 1, True, False),
+    ("GPC_NO_SPLIT", 8, 270, 1, True, False), ("GPC_FORCE_BIG", 12, 200, 1, True, False), ("GPC_FORCE_BIG", 4, 300, 3, True, False)])
+def test_dense_route_is_what_launches(gp, monkeypatch, switch, P, n, ny, ragged, var):
+    """The rule that chooses the kernels of a batch is a pure function (csrc/dense_route.h; its edges: test_dense_route_cpu.py).  This ties
+    it to the dispatcher: for a real call, the kernel name the context reports is the name the function gives for the same facts under
+    the same environment."""
+    import torch
+    capi, ctx = gp
+    for e in ROUTE_SWITCHES:
+        monkeypatch.delenv(e, raising=False)
+    if switch:
+        monkeypatch.setenv(switch, "2" if switch == "GPC_W1_MIN_P" else "1")
+    off, x0, x1, y = synth.make_patches(P, n, seed=100 + P + n, ragged=ragged, ny=ny)
+    xs0, xs1 = synth.grid(0.15, 6)
+    f, v, st = ctx.dense_fit_predict(capi.default_params_dense(want_variance=int(var)), off, x0, x1, y, xs0, xs1)
+    assert np.all(st == 0) and np.all(np.isfinite(f)) and (not var or np.all(np.isfinite(v)))
+    kind, name, _ = capi.dense_route(P, int(np.max(np.diff(off))), n_total=int(off[-1]), ny=ny, m=xs0.shape[0], variance=var, pointwise=True,
+                                     num_cus=torch.cuda.get_device_properties(0).multi_processor_count)
+    assert name and kind not in ("nothing", "no route")
+    assert ctx.last_dense_kernel() == name, (ctx.last_dense_kernel(), kind, name)
 
 
 def test_dense_big_kernel_edge_cases(gp, oracle, monkeypatch):

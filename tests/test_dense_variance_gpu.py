@@ -33,7 +33,7 @@ def gp():
 
 @pytest.fixture(autouse=True)
 def _plain_dispatch(monkeypatch):
-    for e in ("GPC_FORCE_GENERIC", "GPC_FORCE_BIG", "GPC_NO_W2", "GPC_BIG_NO_W2", "GPC_BIG_NO_W4", "GPC_NO_W1", "GPC_NO_W1_512", "GPC_W2",
+    for e in ("GPC_FORCE_GENERIC", "GPC_FORCE_BIG", "GPC_BIG_NO_W2", "GPC_BIG_NO_W4", "GPC_NO_W1", "GPC_NO_W1_512", "GPC_W2",
               "GPC_W1_MIN_P", "GPC_W1_SLOTS", "GPC_VAR_W4", "GPC_NO_SPLIT", "GPC_HOST_NO_PIPELINE", "GPC_HOST_ONE_STREAM"):
         monkeypatch.delenv(e, raising=False)
 
