@@ -85,6 +85,10 @@ PROTOTYPES = {
                                              _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "gpc_dense_irls_fit_predict_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
                                                  _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_fit_predict_var": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
+                                                 _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_fit_predict_var_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
+                                                     _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpc_noise_eval": (C.c_int, [_vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_create": (C.c_int, [_vp, C.POINTER(Params), _i, _i, C.POINTER(_vp)]),
     "gpc_sparse_destroy": (None, [_vp]),
@@ -353,6 +357,40 @@ class Context:
         self._check(self.lib.gpc_dense_irls_fit_predict_dev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total,
                                                             _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz),
                                                             _ptr(f_star), _ptr(alpha_out), _ptr(fhat_out), _ptr(iters), _ptr(status)))
+
+    def dense_irls_fit_predict_var(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_p=True):
+        """Host-pointer entry (gpc_dense_irls_fit_predict_var): dense_irls_fit_predict with the latent predictive variance v* and the
+        occupancy probability p* = Phi(f* / sqrt(s20 + v*)) (noise_model 2 only).  Returns f_star, v_star, p_star (P, m) -- None where
+        not wanted --, alpha (N,), fhat (N,), iters (P,), status (P,)."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        if xs0 is not None:
+            xs0 = np.ascontiguousarray(xs0, dtype=np.float64)
+            xs1 = np.ascontiguousarray(xs1, dtype=np.float64)
+            m = xs0.shape[0]
+        else:
+            m = sz * sz
+        P = off.shape[0] - 1
+        f = np.full((P, m), np.nan)
+        v = np.full((P, m), np.nan) if want_v else None
+        p = np.full((P, m), np.nan) if want_p else None
+        al = np.full_like(y, np.nan)
+        fh = np.full_like(y, np.nan)
+        it = np.full(P, -1, dtype=np.int32)
+        st = np.full(P, -1, dtype=np.int32)
+        self._check(self.lib.gpc_dense_irls_fit_predict_var(self.h, C.byref(params), C.byref(irls), P, _ptr(off), _ptr(x0), _ptr(x1),
+                                                            _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz), _ptr(f), _ptr(v),
+                                                            _ptr(p), _ptr(al), _ptr(fh), _ptr(it), _ptr(st)))
+        return f, v, p, al, fh, it, st
+
+    def dense_irls_fit_predict_var_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
+                                       v_star=None, p_star=None, alpha_out=None, fhat_out=None, iters=None, status=None):
+        self._check(self.lib.gpc_dense_irls_fit_predict_var_dev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total,
+                                                                _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res),
+                                                                int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
+                                                                _ptr(fhat_out), _ptr(iters), _ptr(status)))
 
     def noise_eval(self, noise_model, s20, y, x, sigma_x):
         """gpc_noise_eval: the device's dx_ln / dx2_ln on arrays of (y, x, sigma_x) -> q, r"""
@@ -936,6 +974,26 @@ class Mapping:
                                             msz, None, None, pt.res, sz, f, status=st)
         self.ctx.synchronize()
         return f, st
+
+    def occupancy_probability(self, params, irls=None):
+        """The occupancy layer as a probability (dense_irls_fit_predict_var_dev; params: noise_model 2): per leaf, on its sz x sz grid,
+        p = P(occupied) = Phi(f / sqrt(s20 + v)) with the latent mean f and the latent predictive variance v of the probit GP trained
+        on the labelled cells.  Returns device tensors p, f, v (P, m) float64 and status (P,) int32; a leaf without an observed cell
+        has p = 0.5, f = 0, v = sigmaf_sq."""
+        import torch
+        pt = self.patches
+        if pt.res is None:
+            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
+        P, msz = pt.view.P, pt.view.m
+        sz = int(round(msz ** 0.5))
+        off, x0, x1, y, n_total, n_max = pt.occupancy_batch(self.cells)
+        p, f, v = (torch.zeros((P, msz), dtype=torch.float64, device=self.cells.device) for _ in range(3))
+        st = torch.full((P,), -1, dtype=torch.int32, device=self.cells.device)
+        torch.cuda.synchronize(self.cells.device)
+        self.ctx.dense_irls_fit_predict_var_dev(params, irls if irls is not None else default_params_irls(), P, off, n_max, n_total, x0, x1,
+                                                y, msz, None, None, pt.res, sz, f, v_star=v, p_star=p, status=st)
+        self.ctx.synchronize()
+        return p, f, v, st
 
 
 class Comm:

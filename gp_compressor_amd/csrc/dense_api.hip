@@ -293,6 +293,115 @@ int gpc_dense_irls_fit_predict(gpc_ctx* ctx, const gpc_params* params, const gpc
     return st.finish();
 }
 
+// ---- ... with the latent predictive variance and the occupancy probability (definition: include/gpc.h) ----
+
+int gpc_dense_irls_fit_predict_var_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                       int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
+                                       const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
+                                       double* p_star, double* alpha_out, double* fhat_out, int32_t* iters, int32_t* status)
+{
+    const bool grid = (xs0 == nullptr);
+    // neither asked for, or nothing to predict: the plain entry, same launches, same bits
+    if ((!v_star && !p_star) || (grid ? sz == 0 : m == 0))
+        return gpc_dense_irls_fit_predict_dev(ctx, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star, alpha_out,
+                                              fhat_out, iters, status);
+    if (ctx && grid && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
+    if (grid) m = sz * sz;
+    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
+    if (rc != GPC_OK) return rc;
+    if (!irls) return gpc_fail(ctx, GPC_EINVAL, "irls is NULL");
+    if (params->noise_model != 1 && params->noise_model != 2)
+        return gpc_fail(ctx, GPC_EINVAL, "the IRLS loop needs a probit noise_model (1 or 2), got %d", params->noise_model);
+    if (p_star && params->noise_model != 2)
+        return gpc_fail(ctx, GPC_EINVAL, "p_star needs noise_model 2: the \"Phi\" of model 1 is not a probability");
+    if (irls->max_iter < 1 || !(irls->tol >= 0.0) || !(irls->f_init == irls->f_init))
+        return gpc_fail(ctx, GPC_EINVAL, "irls parameters out of range");
+    if (!(params->noise > 0.0)) return gpc_fail(ctx, GPC_EINVAL, "s20 (params->noise) must be positive");
+    if (!grid && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
+    if (P == 0) return GPC_OK;
+    if (n_max < 1) n_max = 1;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const DenseSite site = dense_site_of(ctx);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
+    const DenseFacts facts{P, n_max, n_total, 1, m, true, true, alpha_out != nullptr, ctx->num_cus, true};
+    const DenseRoute route = dense_route(facts, dense_switches_read());
+    // the workspace: a factor slot per patch | a (when the caller does not take it) | s of the last solve | the variance kernel's
+    // per-wave V scratch | the grid as points | the status (when the caller does not take it)
+    const int ntw = (n_max + 15) / 16;
+    const size_t slot = big_slot_doubles(ntw);
+    const size_t o_al = al256(sizeof(double) * slot * (size_t)P), o_s = o_al + al256(sizeof(double) * (size_t)n_total),
+                 o_scr = o_s + al256(sizeof(double) * (size_t)n_total),
+                 o_xs = o_scr + al256(sizeof(double) * dense_variance_big_scratch_doubles(ctx, ntw)),
+                 o_st = o_xs + al256(sizeof(double) * 2 * (size_t)m), bytes = o_st + al256(sizeof(int32_t) * (size_t)P);
+    if ((rc = gpc_ws_reserve(ctx, site, bytes))) return rc;
+    char* ws = dense_ws(ctx, site);
+    double* d_al = alpha_out ? alpha_out : reinterpret_cast<double*>(ws + o_al);
+    double* d_s = reinterpret_cast<double*>(ws + o_s);
+    double* d_xs = reinterpret_cast<double*>(ws + o_xs);
+    int32_t* d_st = status ? status : reinterpret_cast<int32_t*>(ws + o_st);
+    if (grid && (rc = dense_grid_points_launch(ctx, site, res, sz, d_xs, d_xs + m))) return rc;
+    // the fit predicts nothing: the variance kernel forms the mean from the K* tiles it evaluates anyway
+    DenseArgs a = dense_args(params, P, off, n_max, n_total, x0, x1, y, 1, 0, f_star, d_al, d_st);
+    a.prm.want_variance = 0;
+    a.xs0 = grid ? d_xs : xs0; a.xs1 = grid ? d_xs + m : xs1;
+    const IrlsArgs ir{irls->max_iter, irls->tol, irls->f_init, iters, fhat_out, d_s};
+    const int cap = ctx->num_cus * route.per_cu, grid_b = P < cap ? P : cap;
+    if ((rc = dense_irls_launch(ctx, site, a, route, ir, grid_b))) return rc;
+    a.m = m;
+    rc = dense_variance_big_scaled_launch(ctx, site, a, ntw, reinterpret_cast<const double*>(ws), slot, d_al, d_s,
+                                          reinterpret_cast<double*>(ws + o_scr), v_star, p_star);
+    if (rc == GPC_OK) ctx->last_dense_kernel = route.name;
+    return rc;
+}
+
+int gpc_dense_irls_fit_predict_var(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                   const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
+                                   double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
+                                   double* fhat_out, int32_t* iters, int32_t* status)
+{
+    if (!v_star && !p_star)
+        return gpc_dense_irls_fit_predict(ctx, params, irls, P, off, x0, x1, y, m, xs0, xs1, res, sz, f_star, alpha_out, fhat_out, iters, status);
+    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
+    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    const bool grid = (xs0 == nullptr);
+    if (grid) {
+        if (sz < 0 || sz > 1024) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
+        m = sz * sz;
+    }
+    int n_max = 0, n_total = 0;
+    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
+    if (rc != GPC_OK) return rc;
+    rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
+    if (rc != GPC_OK) return rc;
+    if (!irls) return gpc_fail(ctx, GPC_EINVAL, "irls is NULL");
+    if (p_star && params->noise_model == 1)
+        return gpc_fail(ctx, GPC_EINVAL, "p_star needs noise_model 2: the \"Phi\" of model 1 is not a probability");
+    if (P == 0) return GPC_OK;
+    if (!grid && m && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)n_total, Pz = (size_t)P, Pm = Pz * (size_t)m;
+    GpcStaging st(ctx, "gpc_dense_irls_fit_predict_var");
+    const int32_t* d_off = st.up(off, Pz + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
+    const double *d_xs0 = grid ? nullptr : st.up(xs0, (size_t)m), *d_xs1 = grid ? nullptr : st.up(xs1, (size_t)m);
+    double *d_f = st.out<double>(Pm), *d_al = st.out<double>(N), *d_fh = st.out<double>(N);
+    double *d_v = v_star ? st.out<double>(Pm) : nullptr, *d_p = p_star ? st.out<double>(Pm) : nullptr;
+    int32_t *d_it = st.out<int32_t>(Pz), *d_st = st.out<int32_t>(Pz);
+    if (st.ok())
+        st.rc = gpc_dense_irls_fit_predict_var_dev(ctx, params, irls, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res, sz, d_f,
+                                                   d_v, d_p, d_al, d_fh, d_it, d_st);
+    st.down(f_star, d_f, Pm);
+    if (v_star) st.down(v_star, d_v, Pm);
+    if (p_star) st.down(p_star, d_p, Pm);
+    st.down(alpha_out, d_al, N);
+    st.down(fhat_out, d_fh, N);
+    st.down(iters, d_it, Pz);
+    st.down(status, d_st, Pz);
+    return st.finish();
+}
+
 // host-only test hook: dense_route for the given facts under the switches of the environment (no HIP call: works without a GPU)
 int gpc_test_dense_route(int P, int n_max, int n_total, int ny, int m, int variance, int pointwise, int alpha_out, int num_cus, int irls,
                          int w1_refused, char* name, int name_cap, int32_t* shape)

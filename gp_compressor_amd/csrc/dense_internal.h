@@ -85,6 +85,13 @@ size_t dense_variance_big_scratch_doubles(const gpc_ctx* ctx, int ntw);
 int dense_variance_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
                               const double* alpha, double* scratch, double* v_star);
 
+// ... and of the probit GP (row-scaled: v* = sigma_f^2 - |L^-1 (s o k*)|^2, L the factor of B = I + diag(s) K diag(s) that the IRLS
+// instances exported, any n <= 1024); v_star or p_star (the occupancy probability) may be nullptr
+int dense_variance_big_scaled_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
+                                     const double* alpha, const double* s, double* scratch, double* v_star, double* p_star);
+// the sz x sz grid of load_compressed as sz sz points (cell p = y sz + x) in xs0, xs1 on the device
+int dense_grid_points_launch(gpc_ctx* ctx, const DenseSite& site, double res, int sz, double* xs0, double* xs1);
+
 // tiled left-looking MFMA kernel: 256 < n <= 1024, factor in a global-memory workspace slot per workgroup (see dense_mfma_big.hip)
 size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, const DenseRoute& r, int* grid_out);
 int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, int grid);
@@ -98,5 +105,6 @@ struct IrlsArgs {
     double tol, f_init;
     int32_t* iters;   // [P] or nullptr
     double* fhat;     // [n_total] or nullptr
+    double* s_out;    // [n_total]: W^1/2 of the last solve, written when the route exports the factor (DenseRoute::export_factor)
 };
 int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, const IrlsArgs& ir, int grid);

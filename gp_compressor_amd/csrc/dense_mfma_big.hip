@@ -55,6 +55,7 @@ struct BigParams {
     double irls_tol, irls_f_init;
     int32_t* irls_iters;          // [P] solves performed, or nullptr
     double* irls_fhat;            // [n_total] latent mode at the training points, or nullptr
+    double* irls_s;               // [n_total] W^1/2 of the last solve (the row scale of the exported factor of B), or nullptr
 };
 // The backward solve reads the factor once -- its loads carry the non-temporal hint (mf_img_load_nt), so that they do not push the block
 // rows a step reads several times out of L2 (the one-wave kernel: 1.738 -> 1.680 ms with the same hint, dense_mfma_w1.hip)
@@ -86,7 +87,7 @@ struct BigParams {
 // LDS carve (doubles), for NPAD padded points and WAVES waves per workgroup:
 //   exp table 64 | x0, x1 2 NPAD | z, w, alpha 3 NYP NPAD (NYP = 1: depth plane only, 3: depth + colour, or the IRLS vectors) | rsqrt row 32 | flags 16 | C L^-1 images | C (C-1)/2 images of the strictly
 //   lower tiles of the step's diagonal block | hand-over of the C (C+1)/2 diagonal-block tiles (after the factorisation: the
-//   predict accumulation buffer 4 x 256, ds_add_f64 targets)
+//   per-wave partial sums of the backward solve, then the predict accumulation buffer 4 x 256)
 __host__ __device__ constexpr int bg_hand_doubles(int c) { return c * (c + 1) / 2 * 256 > 1024 ? c * (c + 1) / 2 * 256 : 1024; }
 // lalias (the two-wave shape): the images of the block's strictly lower tiles L_(k+i)(k+c) take the place of the hand-over tiles
 // they were computed from (wave 0 reads T_ic, solves, stores L_ic over it) -- 12 KB less, which is what lets FOUR workgroups share a CU
@@ -739,6 +740,8 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
         // column k-1 are issued before the products of column k (the factor sits in HBM / Infinity Cache, ~2k cycles away).
         {
             constexpr int BT = (BG_NPAD / MF_TS + BG_WAVES - 1) / BG_WAVES;      // tiles per wave and column, at most
+            double* const bpart = red;                                           // [BG_WAVES][3][16]
+            static_assert(BG_WAVES * 3 * MF_TS <= 1024, "per-wave partial sums of the backward solve in the reduction buffer");
             d4 cur[BT], nxt[BT], lt_cur = d4{0.0, 0.0, 0.0, 0.0}, lt_nxt = lt_cur;
 #pragma unroll
             for (int t = 0; t < BT; ++t) cur[t] = nxt[t] = d4{0.0, 0.0, 0.0, 0.0};
@@ -766,13 +769,15 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                         any = true;
                     }
                 }
-                if (any) {
+                // Every wave leaves its partial sums of the column in a slot of its own (bpart: the reduction buffer, idle between the
+                // factorisation and the predict phase) and wave 0 adds the slots in wave order: the same bits from call to call.  (They
+                // used to be added into one LDS vector with ds_add_f64, in the order the waves arrived: with three or more terms, from four
+                // tile rows on, two calls on the same patch differed in the last bits.)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        if (c < ny) {
-                            const double tot = mf_row_reduce4(pa[c], lr);     // lanes lr = 0, 4, 8, 12 hold components 0..3
-                            if ((lr & 3) == 0) atomicAdd(wv + c * BG_NPAD + MF_TS * k + lg + 4 * (lr >> 2), tot);
-                        }
+                for (int c = 0; c < 3; ++c) {
+                    if (c < ny) {
+                        const double tot = any ? mf_row_reduce4(pa[c], lr) : 0.0;     // lanes lr = 0, 4, 8, 12 hold components 0..3
+                        if ((lr & 3) == 0) bpart[(wave * 3 + c) * MF_TS + lg + 4 * (lr >> 2)] = tot;
                     }
                 }
                 __syncthreads();
@@ -782,7 +787,10 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
 #pragma unroll
                         for (int q4 = 0; q4 < 4; ++q4) {
                             const int q = lr * BG_NPAD + MF_TS * k + lg + 4 * q4;
-                            ub[q4] = zv[q] - wv[q];
+                            double sum = 0.0;
+#pragma unroll
+                            for (int w = 0; w < BG_WAVES; ++w) sum += bpart[(w * 3 + lr) * MF_TS + lg + 4 * q4];
+                            ub[q4] = zv[q] - sum;
                         }
                     }
                     const d4 z4 = d4{0.0, 0.0, 0.0, 0.0};
@@ -859,6 +867,9 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
             if (g.irls_fhat)
                 for (int i = tid; i < n; i += BG_THREADS) g.irls_fhat[o + i] = fv[i];
             if (tid == 0 && g.irls_iters) g.irls_iters[patch] = iter;
+            // the slot holds the factor of the last solve's B = I + diag(s) K diag(s): its s goes with it (dense_variance.hip)
+            if (g.irls_s)
+                for (int i = tid; i < n; i += BG_THREADS) g.irls_s[o + i] = sv[i];
         }
 
         BG_STAMP(3);
@@ -902,17 +913,22 @@ __global__ __launch_bounds__(BG_WAVES * 64, BG_OCC) void dense_big_kernel(BigPar
                                 P[mt][nl] = __builtin_amdgcn_mfma_f64_16x16x4f64(ea[mt], eb[nl], P[mt][nl], 0, 0, 0);
                     }
                 }
-                // cross-wave sum of the four 16 x 16 output tiles with ds_add_f64 into one 8 KB buffer
+                // cross-wave sum of the four 16 x 16 output tiles into one 8 KB buffer, wave after wave (a fixed order: the same bits
+                // from call to call; once per patch and channel, the barriers cost nothing measurable)
                 __syncthreads();   // previous channel's outputs are read; the hand-over scratch of the factorisation is dead
                 for (int oo = tid; oo < 1024; oo += BG_THREADS) red[oo] = 0.0;
                 __syncthreads();
+                for (int w = 0; w < BG_WAVES; ++w) {
+                    if (wave == w) {
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
+                        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                    for (int nl = 0; nl < 2; ++nl)
+                            for (int nl = 0; nl < 2; ++nl)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) atomicAdd(red + (mt * 2 + nl) * 256 + lane * 4 + r, P[mt][nl][r]);
-                __syncthreads();
+                                for (int r = 0; r < 4; ++r) red[(mt * 2 + nl) * 256 + lane * 4 + r] += P[mt][nl][r];
+                    }
+                    __syncthreads();
+                }
                 for (int oo = tid; oo < 1024; oo += BG_THREADS) {
                     const int tile = oo >> 8, e = oo & 255, l2 = e >> 2, r = e & 3;
                     const int py = 16 * (tile >> 1) + (l2 >> 4) + 4 * r, pxx = 16 * (tile & 1) + (l2 & 15);
@@ -989,7 +1005,9 @@ int dense_irls_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, c
     g.ntw = (a.n_max + MF_TS - 1) / MF_TS;
     g.slot = big_slot_doubles(g.ntw);
     g.stamps = nullptr;
-    g.export_factor = 0;
+    // with the export every Newton step overwrites the patch's own slot (slot = patch); the last solve's factor stays
+    g.export_factor = r.export_factor ? 1 : 0;
+    g.irls_s = r.export_factor ? ir.s_out : nullptr;
     g.irls_model = a.prm.noise_model;
     g.irls_max_iter = ir.max_iter;
     g.irls_tol = ir.tol;
@@ -1026,7 +1044,7 @@ int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in,
     g.slot = big_slot_doubles(g.ntw);
     const int waves = r.waves, npad = r.npad;
     g.stamps = nullptr;
-    g.irls_model = 0; g.irls_max_iter = 0; g.irls_tol = 0.0; g.irls_f_init = 0.0; g.irls_iters = nullptr; g.irls_fhat = nullptr;
+    g.irls_model = 0; g.irls_max_iter = 0; g.irls_tol = 0.0; g.irls_f_init = 0.0; g.irls_iters = nullptr; g.irls_fhat = nullptr; g.irls_s = nullptr;
     g.ticket = nullptr;
     struct StampDump {
         hipStream_t stream; unsigned long long* d; int P, waves;

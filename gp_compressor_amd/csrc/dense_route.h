@@ -73,7 +73,7 @@ struct DenseRoute {
     const char* name;             // what gpc_last_dense_kernel reports
     int w1_npad, w1_slots;        // one-wave: 256 or 512 points; at most this many patches (= factor slots) per launch
     int nt;                       // register: 4 / 8 / 12 / 16 / 17 tiles
-    bool export_factor;           //           ... and the factor exported for the variance kernel
+    bool export_factor;           //           ... and the factor exported for the variance kernel (also: the IRLS instances of the tiled kernel)
     int waves, npad, per_cu;      // tiled (and the split's third class): the instance and how many workgroups a CU holds
     bool nt17, need_big;          // split: with the 257 .. 272-point class; with patches beyond its last register class
     int var_w4;                   // DenseSwitches::var_w4, for the variance launcher
@@ -121,6 +121,12 @@ static inline DenseRoute dense_route_tiled(const DenseFacts& f, const DenseSwitc
         // workgroups per CU (above); the patches are handed out by ticket, so that only decides how many workgroups queue.
         if (f.n_max <= 256) { r.waves = 4; r.npad = 256; } else { r.waves = 8; r.npad = 1024; }
         r.name = r.waves == 4 ? "dense_mfma_big_w4_irls" : "dense_mfma_big_irls";
+        // with the latent variance (or the occupancy probability) wanted: the same instances with the export on -- one slot per patch,
+        // which keeps the factor of the last solve -- and the row-scaled variance kernel behind them, at every n <= 1024
+        if (f.variance) {
+            r.export_factor = true;
+            r.name = r.waves == 4 ? "dense_mfma_big_w4_irls + dense_variance_big" : "dense_mfma_big_irls + dense_variance_big";
+        }
     } else {
         r.name = r.waves == 2 ? "dense_mfma_big_w2" : r.npad == 256 ? "dense_mfma_big_w4"       // (beyond 256 points the shape is not part of the name)
                  : f.variance ? "dense_mfma_big + dense_variance_big" : "dense_mfma_big";

@@ -282,6 +282,23 @@ struct VarBigParams {
     double* scratch;        // [gridDim.x][8 waves][ntw][256]
     double* v_star;         // [P][m]
 };
+// SCALED (the probit occupancy read-out): the slots hold the factor of B = I + diag(s) K diag(s) that the last solve of the Newton /
+// IRLS loop left behind (dense_mfma_big.hip, IRLS instances with the export on), and v* = sigma_f^2 - |L^-1 (s o k*)|^2: the residual
+// tiles start from s_i k(x_i, x*), the mean still accumulates the unscaled k(x_i, x*) a_i.  GPC_STATUS_NOT_CONVERGED is a valid fit (the
+// last iterate), and the epilogue writes the occupancy probability p* = ef(f* / sqrt(s20 + max(v*, 0))) of the functor (gpc_device.h,
+// model GPC_NOISE_PROBIT_STD) next to v*; either output may be nullptr.  The unscaled instance takes VarBigParams and compiles to the
+// code it was before the template.
+struct VarBigScaledParams : VarBigParams {
+    const double* s;        // [n_total]: W^1/2 of the last solve
+    double* p_star;         // [P][m] or nullptr (v_star may be nullptr as well)
+};
+// (out of line, like the functor call of the IRLS loop: inlined, erfc's polynomial constants are live -- as spills -- across the solve)
+__device__ __attribute__((noinline)) static double dvb_probability(double s20, double f, double v)
+{
+    return gpc_probit_ef(GPC_NOISE_PROBIT_STD, f / sqrt(s20 + __builtin_fmax(v, 0.0)));
+}
+template <bool SCALED> struct VarBigSel { typedef VarBigParams type; };
+template <> struct VarBigSel<true> { typedef VarBigScaledParams type; };
 
 // super-row I holds rI = min(16, nt - 16 I) tile rows; its part of the stream: I off-diagonal blocks of 16 columns x rI rows
 // (column-major), then the diagonal block row-major with L_ii^-1 in the diagonal position
@@ -325,7 +342,8 @@ __device__ static __forceinline__ size_t dv_stream_tile(int p, int nt, int ntw)
 }
 
 #define DVB_NPAD 1024
-__global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(VarBigParams g)
+template <bool SCALED>
+__global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(typename VarBigSel<SCALED>::type g)
 {
     extern __shared__ __attribute__((aligned(16))) char dvb_smem[];
     double* T = reinterpret_cast<double*>(dvb_smem);        // 64
@@ -333,6 +351,7 @@ __global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(VarBi
     double* px1 = px0 + DVB_NPAD;
     double* al = px1 + DVB_NPAD;                            // 3 x DVB_NPAD
     double* Lbuf = al + 3 * DVB_NPAD;                       // 2 x DV_CH images
+    [[maybe_unused]] double* sl = Lbuf + 2 * DV_CH * MF_IMG;    // SCALED: DVB_NPAD
 
     const DenseArgs& A = g.a;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -352,7 +371,14 @@ __global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(VarBi
         double* fs = A.f_star + (size_t)patch * ny * m;
         const int st = A.status ? __builtin_amdgcn_readfirstlane(A.status[patch]) : GPC_STATUS_OK;
         __syncthreads();                                    // previous patch is done with the LDS vectors
-        if (n <= 0 || n > MF_TS * ntw || st != GPC_STATUS_OK) {
+        if (n <= 0 || n > MF_TS * ntw || (st != GPC_STATUS_OK && !(SCALED && st == GPC_STATUS_NOT_CONVERGED))) {
+            if constexpr (SCALED) {
+                // no training points: the prior, p* = ef(0) = 0.5; a failed fit: NaN
+                if (g.v_star)
+                    for (int p = tid; p < m; p += DV_THREADS) vst[p] = (n == 0) ? sf : __builtin_nan("");
+                if (g.p_star)
+                    for (int p = tid; p < m; p += DV_THREADS) g.p_star[(size_t)patch * m + p] = (n == 0) ? 0.5 : __builtin_nan("");
+            } else
             for (int p = tid; p < m; p += DV_THREADS) vst[p] = (n == 0) ? sf : __builtin_nan("");
             for (int p = tid; p < m * ny; p += DV_THREADS) fs[p] = (n == 0) ? 0.0 : __builtin_nan("");
             continue;
@@ -363,6 +389,7 @@ __global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(VarBi
             px1[i] = (i < n) ? A.x1[o + i] : 0.0;
 #pragma unroll
             for (int c = 0; c < 3; ++c) al[c * DVB_NPAD + i] = (c < ny && i < n) ? g.alpha[(size_t)c * A.n_total + o + i] : 0.0;
+            if constexpr (SCALED) sl[i] = (i < n) ? g.s[o + i] : 0.0;
         }
         const double* F = g.ws + (size_t)patch * g.slot;
         const int slen = __builtin_amdgcn_readfirstlane(dv_stream_len(nt));
@@ -416,7 +443,8 @@ __global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(VarBi
                         for (int r = 0; r < 4; ++r) {
                             const int pt = MF_TS * (16 * I + ii) + lg + 4 * r;
                             const double kv = (qv && pt < n) ? gpc_rbf_neg(sf, cexp, px0[pt], px1[pt], gx0, gx1, T) : 0.0;
-                            R[ii][r] = kv;
+                            if constexpr (SCALED) R[ii][r] = sl[pt] * kv;
+                            else R[ii][r] = kv;
 #pragma unroll
                             for (int c = 0; c < 3; ++c)
                                 if (c < ny) fm[c] = __builtin_fma(kv, al[c * DVB_NPAD + pt], fm[c]);
@@ -480,6 +508,11 @@ __global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(VarBi
                 fm[c] += __shfl_xor(fm[c], 32, 64);
             }
             if (qv && lg == 0) {
+                if constexpr (SCALED) {
+                    const double v = sf - nrm;
+                    if (g.v_star) vst[q] = v;
+                    if (g.p_star) g.p_star[(size_t)patch * m + q] = dvb_probability(A.prm.noise, fm[0], v);
+                } else
                 vst[q] = sf - nrm;
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
@@ -506,9 +539,47 @@ int dense_variance_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseAr
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.ws = ws; g.slot = slot; g.ntw = ntw; g.alpha = alpha; g.scratch = scratch; g.v_star = v_star;
     const size_t lds = sizeof(double) * (size_t)(64 + 5 * DVB_NPAD + 2 * DV_CH * MF_IMG);
-    GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_variance_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_variance_big_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      160 * 1024));
-    hipLaunchKernelGGL(dense_variance_big_kernel, dim3(dvb_grid(ctx, a.P)), dim3(DV_THREADS), lds, site.stream, g);
+    hipLaunchKernelGGL(dense_variance_big_kernel<false>, dim3(dvb_grid(ctx, a.P)), dim3(DV_THREADS), lds, site.stream, g);
+    GPC_HIP(ctx, hipGetLastError());
+    return GPC_OK;
+}
+
+// ... of the probit GP, from the slots and the s the IRLS instances of the tiled kernel exported (any n <= 1024: the four-wave shape's
+// slots have the same layout with fewer tile columns).  a.status: the fit's, on the device; a.prm.noise: s20 of the functor.
+int dense_variance_big_scaled_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
+                                     const double* alpha, const double* s, double* scratch, double* v_star, double* p_star)
+{
+    if (a.P == 0 || a.m == 0) return GPC_OK;
+    if (!a.xs0 || !a.xs1) return gpc_fail(ctx, GPC_EINVAL, "the predictive variance needs point-wise X*");
+    VarBigScaledParams g;
+    g.a = a;
+    g.c_exp = (double)(-0.5f) / a.prm.l_sq;
+    g.ws = ws; g.slot = slot; g.ntw = ntw; g.alpha = alpha; g.scratch = scratch; g.v_star = v_star;
+    g.s = s; g.p_star = p_star;
+    const size_t lds = sizeof(double) * (size_t)(64 + 6 * DVB_NPAD + 2 * DV_CH * MF_IMG);
+    GPC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(dense_variance_big_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     160 * 1024));
+    hipLaunchKernelGGL(dense_variance_big_kernel<true>, dim3(dvb_grid(ctx, a.P)), dim3(DV_THREADS), lds, site.stream, g);
+    GPC_HIP(ctx, hipGetLastError());
+    return GPC_OK;
+}
+
+// the sz x sz grid of gp_compressor::load_compressed as m = sz sz points, cell p = y sz + x (the variance kernels have no separable form)
+extern "C" __global__ void dense_grid_points_kernel(double res, int sz, double* xs0, double* xs1)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= sz * sz) return;
+    const int gx = p % sz, gy = p / sz;
+    xs0[p] = res * (((double)gx + 0.5) / (double)sz - 0.5);
+    xs1[p] = res * (((double)gy + 0.5) / (double)sz - 0.5);
+}
+
+int dense_grid_points_launch(gpc_ctx* ctx, const DenseSite& site, double res, int sz, double* xs0, double* xs1)
+{
+    if (sz <= 0) return GPC_OK;
+    hipLaunchKernelGGL(dense_grid_points_kernel, dim3((sz * sz + 255) / 256), dim3(256), 0, site.stream, res, sz, xs0, xs1);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }

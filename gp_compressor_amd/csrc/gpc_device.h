@@ -194,13 +194,19 @@ __device__ static inline void gpc_gaussian_q_r(double s20, double y, double x, d
 // is a float product upstream (the sqrt(float) overload), checked against the compiled reference object in
 // tests/golden/noise_ref.json; exp(-z*z/2) and sqrt(2.0f*M_PI) are double.  model == GPC_NOISE_PROBIT_STD swaps the
 // one expression that is wrong upstream (ef) and keeps the rest.
+// ef: the functor's "Phi"(z).  With model == GPC_NOISE_PROBIT_STD it is the probability P(y | x) at z = y x / sqrt(s20 + sigma_x) --
+// what the occupancy read-out reports at sigma_x = the latent predictive variance (dense_variance.hip).
+__device__ static inline double gpc_probit_ef(int model, double z)
+{
+    return (model == GPC_NOISE_PROBIT_STD) ? 0.5 * erfc(-z * 0.70710678118654752440) : erf(z) / (double)(2.0f * 1.41421354f);
+}
+
 __device__ static inline void gpc_probit_q_r(int model, double s20, double y, double x, double sigma_x, double* q, double* r)
 {
     const double sigma2 = s20 + sigma_x;
     const double sigma = sqrt(sigma2);
     const double z = y * x / sigma;
-    const double ef = (model == GPC_NOISE_PROBIT_STD) ? 0.5 * erfc(-z * 0.70710678118654752440)
-                                                      : erf(z) / (double)(2.0f * 1.41421354f);
+    const double ef = gpc_probit_ef(model, z);
     const double efprim = exp(-z * z / 2.0) / sqrt(2.0 * 3.14159265358979323846);
     *q = y / sigma * efprim / ef;                                 // :17
     const double efprimprim = -z * efprim;                        // :28

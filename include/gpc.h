@@ -175,6 +175,37 @@ int gpc_dense_irls_fit_predict_dev(gpc_ctx* ctx, const gpc_params* params, const
                                    int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
                                    const double* xs0, const double* xs1, double res, int sz, double* f_star, double* alpha_out,
                                    double* fhat_out, int32_t* iters, int32_t* status);
+/* ... with the latent predictive variance and the occupancy probability (Rasmussen & Williams 2006, Alg. 3.2).
+ * Definition.  For every patch the Newton / IRLS loop runs exactly as in gpc_dense_irls_fit_predict_dev: the same rule, the same a,
+ * fhat, iters and status.  Let W be the weights of the LAST SOLVE PERFORMED -- the functor's -r at the iterate the last step started
+ * from; no factorisation is run after the loop, and on a converged patch W differs from W(fhat) by O(tol).  Let s = W^1/2 and L the
+ * Cholesky factor of B = I + diag(s) K diag(s) that this solve left behind.  Then per prediction point
+ *     f* = k*^T a                                   (as in the plain entry)
+ *     v* = sigmaf_sq - | L^-1 (s o k*) |^2          (= k** - k*^T (K + W^-1)^-1 k*; not clamped: may be -O(eps) like the dense v_star)
+ *     p* = 0.5 erfc(-z / sqrt 2),  z = f* / sqrt(s20 + max(v*, 0))       (the functor's own ef of noise_model 2 at sigma_x = v*:
+ *                                                                          P(y = +1 | x*), the sigma_x slot of probit_noise::dx_ln)
+ * Per patch: an empty patch gives f* = 0, v* = sigmaf_sq, p* = 0.5; status GPC_STATUS_NAN (and NOT_SPD) gives NaN in f*, v*, p*;
+ * GPC_STATUS_NOT_CONVERGED gives the outputs of the last iterate, not NaN.
+ * v_star and p_star are [P][m]; each may be NULL, and with both NULL (or nothing to predict) the call IS gpc_dense_irls_fit_predict[_dev]:
+ * it forwards to it and gives the same bits.  p_star != NULL with noise_model == 1: GPC_EINVAL (the "Phi" of model 1 as written is
+ * not a probability); v_star works with both models.  Other errors as in gpc_dense_irls_fit_predict[_dev].
+ * With xs0 == NULL the sz x sz grid of load_compressed is used (res, sz; m = sz*sz, cell p = y*sz + x).  The variance kernel has no
+ * separable form, so the library then materialises the grid as m points in its workspace and evaluates point-wise throughout: f_star may
+ * differ from the grid form of gpc_dense_irls_fit_predict[_dev] by O(1 ulp) per kernel value.
+ * Workspace: one factor slot per patch, a and s (n_total doubles each), the variance kernel's per-wave scratch, the grid points, a
+ * status word per patch --
+ *     bytes = 8 (slot(ntw) P + 2 n_total + 2048 CUs ntw + 2 m) + 4 P,   slot(ntw) = 256 ((ntw + 1) ntw + 2 ntw),  ntw = ceil(n_max / 16)
+ * (each term rounded up to 256 bytes; n_max = 1024: 8.8 MB per patch).  A refusal returns GPC_ENOMEM; the batch is not chunked.
+ * The _dev form enqueues on the context's stream and never synchronises; the host form stages its arguments like
+ * gpc_dense_irls_fit_predict. */
+int gpc_dense_irls_fit_predict_var(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                   const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
+                                   double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
+                                   double* fhat_out, int32_t* iters, int32_t* status);
+int gpc_dense_irls_fit_predict_var_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                       int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
+                                       const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
+                                       double* p_star, double* alpha_out, double* fhat_out, int32_t* iters, int32_t* status);
 /* The Noise contract itself, evaluated on the DEVICE by the very functions the kernels inline (csrc/gpc_device.h):
  * q[i] = dx_ln(y[i], x[i], sigma_x[i]), r[i] = dx2_ln(...) for noise_model 0 (src/gaussian_noise.cpp:9-18), 1 or 2
  * (src/probit_noise.cpp:11-31).  Host pointers, n triples.  This is what pins the device functors to the compiled
