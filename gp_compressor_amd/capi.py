@@ -34,6 +34,11 @@ class IrlsParams(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double), ("f_init", C.c_double)]
 
 
+class Hyper(C.Structure):
+    """struct gpc_hyper (include/gpc.h): one candidate of gpc_dense_irls_select."""
+    _fields_ = [("sigmaf_sq", C.c_double), ("l_sq", C.c_double), ("noise", C.c_double)]
+
+
 class RegistrationParams(C.Structure):
     """struct gpc_registration_params (include/gpc.h)."""
     _fields_ = [("step", C.c_double), ("tol", C.c_double), ("min_steps", C.c_int32), ("max_steps", C.c_int32),
@@ -89,6 +94,14 @@ PROTOTYPES = {
                                                  _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpc_dense_irls_fit_predict_var_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
                                                      _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_fit_predict_ev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
+                                                _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_fit_predict_ev_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
+                                                    _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_select": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
+                                        _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_select_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i,
+                                            _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpc_noise_eval": (C.c_int, [_vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_create": (C.c_int, [_vp, C.POINTER(Params), _i, _i, C.POINTER(_vp)]),
     "gpc_sparse_destroy": (None, [_vp]),
@@ -391,6 +404,78 @@ class Context:
                                                                 _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res),
                                                                 int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
                                                                 _ptr(fhat_out), _ptr(iters), _ptr(status)))
+
+    def _irls_host_args(self, off, x0, x1, y, xs0, xs1, sz, want_v, want_p):
+        """The host arrays of the _ev and select entries: inputs made contiguous, outputs filled with NaN / -1."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        if xs0 is not None:
+            xs0 = np.ascontiguousarray(xs0, dtype=np.float64)
+            xs1 = np.ascontiguousarray(xs1, dtype=np.float64)
+            m = xs0.shape[0]
+        else:
+            m = sz * sz
+        P = off.shape[0] - 1
+        f = np.full((P, m), np.nan)
+        v = np.full((P, m), np.nan) if want_v else None
+        p = np.full((P, m), np.nan) if want_p else None
+        al, fh = np.full_like(y, np.nan), np.full_like(y, np.nan)
+        it, st = np.full(P, -1, dtype=np.int32), np.full(P, -1, dtype=np.int32)
+        lq = np.full(P, np.nan)
+        return (off, x0, x1, y, xs0, xs1), (P, m), (f, v, p, al, fh, it, st, lq)
+
+    def dense_irls_fit_predict_ev(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_p=True):
+        """Host-pointer entry (gpc_dense_irls_fit_predict_ev): dense_irls_fit_predict_var with the Laplace approximation of the log
+        marginal likelihood per patch.  Returns f_star, v_star, p_star (P, m) -- None where not wanted --, alpha (N,), fhat (N,),
+        iters (P,), status (P,), log_q (P,)."""
+        (off, x0, x1, y, xs0, xs1), (P, m), (f, v, p, al, fh, it, st, lq) = self._irls_host_args(off, x0, x1, y, xs0, xs1, sz, want_v, want_p)
+        self._check(self.lib.gpc_dense_irls_fit_predict_ev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), _ptr(x0), _ptr(x1),
+                                                           _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz), _ptr(f), _ptr(v),
+                                                           _ptr(p), _ptr(al), _ptr(fh), _ptr(it), _ptr(st), _ptr(lq)))
+        return f, v, p, al, fh, it, st, lq
+
+    def dense_irls_fit_predict_ev_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
+                                      v_star=None, p_star=None, alpha_out=None, fhat_out=None, iters=None, status=None, log_q=None):
+        self._check(self.lib.gpc_dense_irls_fit_predict_ev_dev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total,
+                                                               _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res),
+                                                               int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
+                                                               _ptr(fhat_out), _ptr(iters), _ptr(status), _ptr(log_q)))
+
+    @staticmethod
+    def hyper_array(candidates):
+        """A ctypes array of gpc_hyper from (sigmaf_sq, l_sq, noise) triples or Hyper objects."""
+        arr = (Hyper * max(len(candidates), 1))()
+        for i, c in enumerate(candidates):
+            arr[i] = c if isinstance(c, Hyper) else Hyper(*(float(x) for x in c))
+        return arr
+
+    def dense_irls_select(self, params, irls, candidates, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_p=True):
+        """Host-pointer entry (gpc_dense_irls_select): per patch the candidate (sigmaf_sq, l_sq, noise) of largest Laplace evidence and
+        its outputs.  Returns f_star, v_star, p_star (P, m) -- None where not wanted --, alpha (N,), fhat (N,), iters (P,), status (P,),
+        log_q (P,), best (P,) int32 (-1: no eligible candidate), log_q_all (H, P)."""
+        (off, x0, x1, y, xs0, xs1), (P, m), (f, v, p, al, fh, it, st, lq) = self._irls_host_args(off, x0, x1, y, xs0, xs1, sz, want_v, want_p)
+        H = len(candidates)
+        best = np.full(P, -2, dtype=np.int32)
+        lq_all = np.full((H, P), np.nan)
+        arr = self.hyper_array(candidates)
+        self._check(self.lib.gpc_dense_irls_select(self.h, C.byref(params), C.byref(irls), H, C.addressof(arr), P,
+                                                   _ptr(off), _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz),
+                                                   _ptr(f), _ptr(v), _ptr(p), _ptr(al), _ptr(fh), _ptr(lq), _ptr(best), _ptr(lq_all),
+                                                   _ptr(it), _ptr(st)))
+        return f, v, p, al, fh, it, st, lq, best, lq_all
+
+    def dense_irls_select_dev(self, params, irls, candidates, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star=None,
+                              v_star=None, p_star=None, alpha_out=None, fhat_out=None, log_q=None, best=None, log_q_all=None,
+                              iters=None, status=None):
+        """gpc_dense_irls_select_dev: device pointers throughout, except the candidates (host, read at call time)."""
+        arr = self.hyper_array(candidates)
+        self._check(self.lib.gpc_dense_irls_select_dev(self.h, C.byref(params), C.byref(irls), len(candidates), C.addressof(arr), P,
+                                                       _ptr(off), n_max, n_total, _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1),
+                                                       float(res), int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
+                                                       _ptr(fhat_out), _ptr(log_q), _ptr(best), _ptr(log_q_all), _ptr(iters),
+                                                       _ptr(status)))
 
     def noise_eval(self, noise_model, s20, y, x, sigma_x):
         """gpc_noise_eval: the device's dx_ln / dx2_ln on arrays of (y, x, sigma_x) -> q, r"""
@@ -994,6 +1079,30 @@ class Mapping:
                                                 y, msz, None, None, pt.res, sz, f, v_star=v, p_star=p, status=st)
         self.ctx.synchronize()
         return p, f, v, st
+
+    def occupancy_select(self, params, candidates, irls=None):
+        """Per-leaf hyper-parameter selection for the occupancy layer (dense_irls_select_dev on occupancy_batch; params: the base,
+        noise_model 2; candidates: (sigmaf_sq, l_sq, noise) triples): per leaf the candidate of largest Laplace evidence log q(y | X, theta)
+        and its read-out on the leaf's sz x sz grid.  Returns device tensors p, f, v (P, m) float64, best (P,) int32 (-1: no candidate's fit
+        converged with a finite evidence; the leaf's p, f, v and log_q are then NaN), log_q (P,) float64 and status (P,) int32; a leaf
+        without an observed cell has best = 0, p = 0.5, f = 0, v = candidates[0]'s sigmaf_sq and log_q = 0."""
+        import torch
+        pt = self.patches
+        if pt.res is None:
+            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
+        P, msz = pt.view.P, pt.view.m
+        sz = int(round(msz ** 0.5))
+        off, x0, x1, y, n_total, n_max = pt.occupancy_batch(self.cells)
+        dev = self.cells.device
+        p, f, v = (torch.zeros((P, msz), dtype=torch.float64, device=dev) for _ in range(3))
+        lq = torch.zeros((P,), dtype=torch.float64, device=dev)
+        best = torch.full((P,), -2, dtype=torch.int32, device=dev)
+        st = torch.full((P,), -1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.ctx.dense_irls_select_dev(params, irls if irls is not None else default_params_irls(), candidates, P, off, n_max, n_total, x0,
+                                       x1, y, msz, None, None, pt.res, sz, f_star=f, v_star=v, p_star=p, log_q=lq, best=best, status=st)
+        self.ctx.synchronize()
+        return p, f, v, best, lq, st
 
 
 class Comm:

@@ -92,6 +92,21 @@ int dense_variance_big_scaled_launch(gpc_ctx* ctx, const DenseSite& site, const 
 // the sz x sz grid of load_compressed as sz sz points (cell p = y sz + x) in xs0, xs1 on the device
 int dense_grid_points_launch(gpc_ctx* ctx, const DenseSite& site, double res, int sz, double* xs0, double* xs1);
 
+// the Laplace evidence log q(y | X, theta) of the probit GP from what such a fit left behind (dense_evidence.hip; definition:
+// include/gpc.h): a, fhat, the labels a.y, the fit's status a.status and the L_kk^-1 images of the slots; log_q [P]
+int dense_evidence_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
+                          const double* alpha, const double* fhat, double* log_q);
+// One candidate's outputs (gpc_dense_irls_select, include/gpc.h) and the keep-best step behind it: where candidate h wins a patch its rows
+// are copied from `cand` to `out`.  Any pointer of `out` may be nullptr; cur_best, cur_lq [P] hold the state between the candidates.
+struct SelectRows {
+    double *f, *v, *p;        // [P][m]
+    double *alpha, *fhat;     // [n_total]
+    double* log_q;            // [P]
+    int32_t *iters, *status;  // [P]
+};
+int dense_select_keep_launch(gpc_ctx* ctx, const DenseSite& site, int h, int P, int m, const int32_t* off, const SelectRows& cand,
+                             const SelectRows& out, int32_t* best, double* log_q_all_h, int32_t* cur_best, double* cur_lq);
+
 // tiled left-looking MFMA kernel: 256 < n <= 1024, factor in a global-memory workspace slot per workgroup (see dense_mfma_big.hip)
 size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, const DenseRoute& r, int* grid_out);
 int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r, int grid);

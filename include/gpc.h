@@ -206,6 +206,63 @@ int gpc_dense_irls_fit_predict_var_dev(gpc_ctx* ctx, const gpc_params* params, c
                                        int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
                                        const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
                                        double* p_star, double* alpha_out, double* fhat_out, int32_t* iters, int32_t* status);
+/* ... and with the Laplace approximation of the log marginal likelihood (Rasmussen & Williams 2006, Alg. 3.1 line 10, eq. 3.32): what
+ * tells whether sigmaf_sq, l_sq and s20 fit the labels of a patch.  noise_model 2 only.
+ * Definition.  The loop, a, fhat, iters, status, f*, v* and p* are exactly those of gpc_dense_irls_fit_predict_var[_dev]; L is the factor
+ * of the LAST SOLVE PERFORMED (R&W's own convention: the L of the last iteration with the updated f).  Per patch of n points
+ *     log_q = -0.5 sum_j a_j fhat_j  +  sum_j log ef(y_j fhat_j / sqrt(s20))  -  sum_{j<n} log L_jj,    ef(z) = 0.5 erfc(-z / sqrt 2)
+ * ef is the functor's own ef of noise_model 2 at sigma_x = 0; L_jj = 1 / (L_kk^-1)_jj is read from the L_kk^-1 image of tile k = j / 16
+ * that the fit exported (so -log L_jj is taken as log (L_kk^-1)_jj); the padding rows j >= n of the last tile are not summed.  Each of
+ * the three sums has a fixed order (point j goes to lane j mod 64 of one wave, then a fixed shuffle tree): two calls give the same bits.
+ * Per patch: an empty patch gives log_q = 0; status GPC_STATUS_NAN (and NOT_SPD) gives NaN; GPC_STATUS_NOT_CONVERGED gives the value at
+ * the last iterate; an ef that underflows gives -inf, a valid output.
+ * log_q is [P].  log_q == NULL: the call forwards to gpc_dense_irls_fit_predict_var[_dev] and gives the same bits.  log_q != NULL: every
+ * other output is bit for bit what that entry gives; noise_model == 1 is GPC_EINVAL (its "Phi" is not a probability).  v_star and p_star
+ * may both be NULL and m may be 0: the fit still runs with the factor export on (f_star is then the plain entry's), and the variance
+ * kernel is skipped.  Other errors as in gpc_dense_irls_fit_predict_var[_dev].
+ * Workspace: that of gpc_dense_irls_fit_predict_var[_dev] plus fhat (n_total doubles) when fhat_out == NULL --
+ *     bytes = 8 (slot(ntw) P + 3 n_total + 2048 CUs ntw + 2 m) + 4 P
+ * (each term rounded up to 256 bytes).  A refusal returns GPC_ENOMEM; the batch is not chunked.  The read-out re-runs nothing: it reads
+ * a, fhat, y and the diagonals of the L_kk^-1 images, 4 n doubles per patch. */
+int gpc_dense_irls_fit_predict_ev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                  const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
+                                  double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
+                                  double* fhat_out, int32_t* iters, int32_t* status, double* log_q);
+int gpc_dense_irls_fit_predict_ev_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
+                                      int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
+                                      const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
+                                      double* p_star, double* alpha_out, double* fhat_out, int32_t* iters, int32_t* status,
+                                      double* log_q);
+/* Model selection among H candidate hyper-parameter sets, per patch, by that evidence.  params is the base (noise_model must be 2); for
+ * candidate h its sigmaf_sq, l_sq and noise (= s20) are replaced by cand[h]'s.  cand is a HOST array of H >= 1 entries, read at call
+ * time, in the _dev form too.
+ * Rule per patch.  Candidate h is eligible iff its fit ended with GPC_STATUS_OK and its log_q is finite.  best is the lowest h that
+ * attains the maximum of log_q over the eligible candidates (the comparison is a strict >: ties and duplicates go to the lower index, a
+ * NaN never wins).  Every output of the patch is the winner's, bit for bit what gpc_dense_irls_fit_predict_ev[_dev] gives with that
+ * candidate's parameters and the same v_star / p_star requested.  With no eligible candidate best = -1, f*, v*, p*, alpha, fhat and log_q
+ * are NaN, and iters and status are those of candidate 0.  An empty patch has log_q = 0 under every candidate: best = 0 with candidate
+ * 0's outputs, f* = 0, v* = cand[0].sigmaf_sq, p* = 0.5.
+ * Outputs, each may be NULL: f_star, v_star, p_star [P][m]; alpha_out, fhat_out [N]; log_q [P]; best [P]; log_q_all [H][P] (every
+ * candidate's log_q); iters, status [P].
+ * The candidates run one after another on the context's stream into temporaries in the workspace, and after each a keep-best kernel
+ * copies the rows of the patches it won so far into the outputs.  Workspace: that of gpc_dense_irls_fit_predict_ev[_dev] plus the
+ * temporaries --
+ *     bytes = ev_bytes + 8 (3 P m + 2 n_total + 2 P) + 4 (3 P)
+ * (each term rounded up to 256 bytes); not chunked over patches, a refusal returns GPC_ENOMEM.  The _dev form never synchronises.
+ * Errors: GPC_EINVAL for H < 1, cand == NULL, a candidate with a non-positive or non-finite field, noise_model != 2; otherwise those of
+ * gpc_dense_irls_fit_predict_ev[_dev]. */
+typedef struct gpc_hyper {
+    double sigmaf_sq, l_sq, noise;
+} gpc_hyper;
+int gpc_dense_irls_select(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int H, const gpc_hyper* cand, int P,
+                          const int32_t* off, const double* x0, const double* x1, const double* y, int m, const double* xs0,
+                          const double* xs1, double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
+                          double* fhat_out, double* log_q, int32_t* best, double* log_q_all, int32_t* iters, int32_t* status);
+int gpc_dense_irls_select_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int H, const gpc_hyper* cand, int P,
+                              const int32_t* off, int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
+                              const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
+                              double* p_star, double* alpha_out, double* fhat_out, double* log_q, int32_t* best, double* log_q_all,
+                              int32_t* iters, int32_t* status);
 /* The Noise contract itself, evaluated on the DEVICE by the very functions the kernels inline (csrc/gpc_device.h):
  * q[i] = dx_ln(y[i], x[i], sigma_x[i]), r[i] = dx2_ln(...) for noise_model 0 (src/gaussian_noise.cpp:9-18), 1 or 2
  * (src/probit_noise.cpp:11-31).  Host pointers, n triples.  This is what pins the device functors to the compiled
