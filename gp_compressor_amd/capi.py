@@ -124,6 +124,8 @@ PROTOTYPES = {
     "gpc_sparse_ld": (C.c_int, [_vp]),
     "gpc_sparse_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_remap": (C.c_int, [_vp, _i, _vp, C.POINTER(_vp)]),
+    "gpc_sparse_prune": (C.c_int, [_vp, _i, _vp, _d, _vp, _vp, _vp, _vp]),
+    "gpc_sparse_prune_dev": (C.c_int, [_vp, _i, _vp, _d, _vp, _vp, _vp, _vp]),
     "gpc_reproject": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_reproject_dev": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_project_cloud": (C.c_int, [_vp, _vp, _i, _d, _i, C.POINTER(_vp)]),
@@ -881,6 +883,26 @@ class Sparse:
         self.ctx._check(self.lib.gpc_sparse_train_sigmaf_dev(self.h, _ptr(off), int(n_total), _ptr(x0), _ptr(x1), _ptr(y), float(step),
                                                              int(max_counter), _ptr(p0), _ptr(iters), _ptr(ls), _ptr(delta)))
 
+    def prune(self, keep=None, target=None, score_tol=0.0, want_trace=False):
+        """gpc_sparse_prune (host arrays): every patch keeps removing its lowest-score basis vector until it holds `keep` (or its entry
+        of `target`, (P,) int32) vectors, then while the lowest score is below score_tol.  In place; remap(P, arange(P)) is the copy to
+        prune from.  Returns removed (P,) int32, and with want_trace also order (P, ld) int32 and scores (P, ld): the first removed[p]
+        entries of a row are the removals in order, the others stay -1 / NaN."""
+        tg = None if target is None else np.ascontiguousarray(target, dtype=np.int32)
+        assert tg is None or tg.shape == (self.P,)
+        ld = self.ld()
+        rm = np.zeros(self.P, dtype=np.int32)
+        order = np.full((self.P, ld), -1, dtype=np.int32) if want_trace else None
+        scores = np.full((self.P, ld), np.nan) if want_trace else None
+        self.ctx._check(self.lib.gpc_sparse_prune(self.h, 0 if keep is None else int(keep), _ptr(tg), float(score_tol), _ptr(rm),
+                                                  _ptr(order), _ptr(scores), None))
+        return (rm, order, scores) if want_trace else rm
+
+    def prune_dev(self, keep=None, target=None, score_tol=0.0, removed=None, order=None, scores=None, status=None):
+        """gpc_sparse_prune_dev: device buffers (each may be None), enqueued on the context's stream"""
+        self.ctx._check(self.lib.gpc_sparse_prune_dev(self.h, 0 if keep is None else int(keep), _ptr(target), float(score_tol),
+                                                      _ptr(removed), _ptr(order), _ptr(scores), _ptr(status)))
+
     def sizes(self):
         b = np.zeros(self.P, dtype=np.int32)
         self.ctx._check(self.lib.gpc_sparse_sizes(self.h, _ptr(b)))
@@ -1035,6 +1057,13 @@ class Mapping:
             o.close()
         self.reg, self.patches, self.depth, self.rgb = reg, pt, gd, gc
         return steps, True
+
+    def prune(self, keep_depth, keep_rgb, score_tol_depth=0.0, score_tol_rgb=0.0):
+        """Bound the map: prune the depth and the colour GP of every leaf in place (Sparse.prune_dev).  The Registration object refers
+        to the same two objects and sees the pruned state; later add_cloud calls may grow the leaves again, up to their capacity."""
+        self.depth.prune_dev(keep=keep_depth, score_tol=score_tol_depth)
+        self.rgb.prune_dev(keep=keep_rgb, score_tol=score_tol_rgb)
+        self.ctx.synchronize()
 
     def render(self, origin, dirs, params=None, use_cells=True, want=("leaf", "range", "local")):
         """The map as a sensor at `origin` sees it along `dirs` (Context.camera_rays, or any (n, 3) float64 device tensor): Patches.render

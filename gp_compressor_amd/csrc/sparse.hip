@@ -14,7 +14,8 @@
 // = Eigen 2 x b column-major), b [P], total_count [P];  ld = capacity + 1 rounded up to 16 (a full update may hold capacity+1
 // basis vectors until the deletion that follows it), or GPC_MAX_BV when capacity == -1.
 //
-// The predict / likelihood / train kernels are in sparse_predict.hip, the gpc_sparse_* entry points in sparse_api.hip.
+// The prune kernel (gpc_sparse_prune: the capacity deletion as a step of its own) sits here too, beside sp_delete_bv and the arg-min it
+// reuses.  The predict / likelihood / train kernels are in sparse_predict.hip, the gpc_sparse_* entry points in sparse_api.hip.
 #include <algorithm>
 #include <cstdlib>
 
@@ -1533,6 +1534,84 @@ __global__ __launch_bounds__(64, 2) void sparse_add_rows_kernel(SpAddParams A)
     }
 }
 
+// ---- prune: the capacity deletion of the add path (:206-223 -> delete_bv :252-295 / field :219-263) as a step of its own ---------
+// A trained patch keeps removing the vector with the smallest score |alpha_i|^2 / (Q_ii + C_ii) until it holds max(1, target) vectors,
+// then goes on while the smallest score is below score_tol (include/gpc.h, gpc_sparse_prune_dev).  One workgroup per patch at a time;
+// the state stays in HBM and every removal is the full-matrix sp_delete_bv (TRI = false, PK = false) in every workgroup shape: states
+// loaded with gpc_sparse_set_state and states trained at capacity <= 64 are symmetric only to rounding, and the triangular passes would
+// read the other triangle.  The scan, the arg-min and the element updates do not depend on the shape, so 64, 128 and 256 threads leave
+// the same bits.  No atomics.
+struct SpPruneParams {
+    int P, ny, ld, keep, field_bug;
+    const int32_t* target;     // [P] or nullptr (every patch: keep)
+    double score_tol;
+    double *alpha, *C, *Q, *BV;
+    int32_t *b, *stat;
+    int32_t *removed, *order, *status_out;   // each may be nullptr
+    double* scores;                          // may be nullptr
+};
+
+__global__ __launch_bounds__(SP_THREADS) void sparse_prune_kernel(SpPruneParams A)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, ld = A.ld, ny = A.ny;
+    double* sval = reinterpret_cast<double*>(smem);     // 4
+    int* sidx = reinterpret_cast<int*>(sval + 4);       // 4 ints (2 doubles)
+    double* Cstar = sval + 6;                           // delete_bv scratch, [ld] each
+    double* Qstar = Cstar + ld;
+    double* Crep = Qstar + ld;
+    double* Qrep = Crep + ld;
+    for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
+        SpState S;
+        S.ld = ld; S.ny = ny; S.ldm = ld;
+        S.alpha = A.alpha + (size_t)patch * ny * ld;
+        S.C = A.C + (size_t)patch * ld * ld;
+        S.Q = A.Q + (size_t)patch * ld * ld;
+        S.BV = A.BV + (size_t)patch * ld * 2;
+        int b = A.b[patch];
+        if (b > ld) b = ld;                             // (gpc_sparse_set_state admits no more)
+        int st = A.stat[patch];
+        const int tp = A.target ? A.target[patch] : A.keep;
+        const int t = tp > 1 ? tp : 1;
+        int step = 0;
+        __syncthreads();                                // the scratch of the previous patch is free
+        while (b > 1) {
+            double best = 0.0;
+            int loc = 0x7fffffff;
+            bool have = false;
+            for (int i = tid; i < b; i += SP_NTH) {
+                double a2 = 0.0;
+                for (int c = 0; c < ny; ++c) { const double a = S.alpha[c * ld + i]; a2 += a * a; }
+                const double score = a2 / (S.Q[sp_at<false>(i, i, ld)] + S.C[sp_at<false>(i, i, ld)]);
+                if (!have || SP_TAKE(score, i, best, loc)) { best = score; loc = i; have = true; }
+            }
+            if (!have) best = __builtin_inf();
+            sp_block_argmin(best, loc, sval, sidx);
+            if (loc < 0 || loc >= b) loc = 0;
+            if (!(b > t || best < A.score_tol)) break;  // (a NaN minimum compares false: the score branch stops)
+            if (tid == 0) {
+                if (A.order) A.order[(size_t)patch * ld + step] = loc;
+                if (A.scores) A.scores[(size_t)patch * ld + step] = best;
+            }
+            b = sp_delete_bv<SP_RMW, false, false>(S, b, loc, A.field_bug, Cstar, Qstar, Crep, Qrep);
+            ++step;
+        }
+        // isnan(C(0,0)) -> "sparse_gp::C has become Nan" (:245), as after a point of the add path
+        if (step > 0) {
+            const double c00 = S.C[0];
+            if (c00 != c00 && st == GPC_STATUS_OK) st = GPC_STATUS_NAN;
+        }
+        if (tid == 0) {
+            if (step > 0) {
+                A.b[patch] = b;
+                A.stat[patch] = st;
+            }
+            if (A.removed) A.removed[patch] = step;
+            if (A.status_out) A.status_out[patch] = st;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 static size_t sp_add_lds_small(int bm = SP_BMAX) { return sizeof(double) * (size_t)(64 + 16 + 6 + 4 * (bm + 2) + 22 * (bm + 1) + 2 * bm * bm); }
@@ -1680,6 +1759,29 @@ int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* 
         hipLaunchKernelGGL((sparse_add_kernel<false, false, true, true>), dim3(grid), dim3(nth), lds, ctx->stream, A);
     } else if (tri) hipLaunchKernelGGL((sparse_add_kernel<false, false, true>), dim3(grid), dim3(nth), lds, ctx->stream, A);
     else hipLaunchKernelGGL((sparse_add_kernel<false, false>), dim3(grid), dim3(nth), lds, ctx->stream, A);
+    GPC_HIP(ctx, hipGetLastError());
+    return GPC_OK;
+}
+
+int sp_prune_launch(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order, double* scores,
+                    int32_t* status)
+{
+    gpc_ctx* ctx = g->ctx;
+    SpPruneParams A;
+    A.P = g->P; A.ny = g->ny; A.ld = g->ld; A.keep = keep; A.field_bug = g->prm.ref_field_delete_bug;
+    A.target = target;
+    A.score_tol = score_tol;
+    A.alpha = g->alpha; A.C = g->C; A.Q = g->Q; A.BV = g->BV;
+    A.b = g->b; A.stat = g->stat;
+    A.removed = removed; A.order = order; A.scores = scores; A.status_out = status;
+    // the workgroup shapes of sp_add_launch: a thread owns at most one basis row in each, and the shapes give the same bits
+    const int cap_ = g->prm.capacity;
+    const int nth = (cap_ <= 0 || getenv("GPC_SPARSE_WIDE")) ? SP_THREADS : cap_ <= 64 ? 64 : cap_ <= 100 ? 128 : SP_THREADS;
+    const size_t lds = sizeof(double) * (size_t)(6 + 4 * g->ld);
+    // a removal is a chain of short barrier-separated phases on one patch: as many patches in flight as a CU holds (the kernel's
+    // registers leave room for four waves per SIMD)
+    const int grid = std::min(g->P, ctx->num_cus * (1024 / nth));
+    hipLaunchKernelGGL(sparse_prune_kernel, dim3(grid), dim3(nth), lds, ctx->stream, A);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }

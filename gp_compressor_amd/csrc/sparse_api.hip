@@ -186,6 +186,28 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
     return sp_add_launch(g, off, n_total, x0, x1, y, perm, status);
 }
 
+// what both prune entries check (include/gpc.h)
+static int sp_prune_check(gpc_ctx* ctx, int keep, const int32_t* target, double score_tol)
+{
+    if (!target && keep < 1) return gpc_fail(ctx, GPC_EINVAL, "keep must be >= 1 when target is NULL, got %d", keep);
+    if (!(score_tol >= 0.0)) return gpc_fail(ctx, GPC_EINVAL, "score_tol must be >= 0 (+inf allowed), got %g", score_tol);
+    return GPC_OK;
+}
+
+int gpc_sparse_prune_dev(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order,
+                         double* scores, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_prune_check(ctx, keep, target, score_tol)) return rc;
+    if (g->P == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_prune_launch(g, keep, target, score_tol, removed, order, scores, status);
+}
+
 int gpc_sparse_predict_dev(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
                            int conf, int32_t* status)
 {
@@ -371,6 +393,31 @@ int gpc_sparse_add(gpc_sparse* g, const int32_t* off, const double* x0, const do
     int32_t* d_st = st.out<int32_t>((size_t)P);
     if (st.ok()) st.rc = gpc_sparse_add_dev(g, d_off, n_max, (int)N, d_x0, d_x1, d_y, d_perm, d_st);
     st.down(status, d_st, (size_t)P);
+    return st.finish();
+}
+
+int gpc_sparse_prune(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order, double* scores,
+                     int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_prune_check(ctx, keep, target, score_tol)) return rc;
+    const size_t P = (size_t)g->P, W = P * (size_t)g->ld;
+    if (P == 0) return GPC_OK;
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_prune");
+    const int32_t* d_target = target ? st.up(target, P) : nullptr;
+    int32_t* d_rm = removed ? st.out<int32_t>(P) : nullptr;
+    // the trace goes up first: the entries at and beyond removed[p] come back as the caller left them
+    int32_t* d_order = order ? st.up(order, W) : nullptr;
+    double* d_scores = scores ? st.up(scores, W) : nullptr;
+    int32_t* d_st = status ? st.out<int32_t>(P) : nullptr;
+    if (st.ok()) st.rc = gpc_sparse_prune_dev(g, keep, d_target, score_tol, d_rm, d_order, d_scores, d_st);
+    st.down(removed, d_rm, P);
+    st.down(order, d_order, W);
+    st.down(scores, d_scores, W);
+    st.down(status, d_st, P);
     return st.finish();
 }
 

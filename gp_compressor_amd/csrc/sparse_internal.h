@@ -1,4 +1,4 @@
-// sparse_internal.h -- what the translation units of the sparse path share: sparse.hip (the add kernels), sparse_predict.hip (the
+// sparse_internal.h -- what the translation units of the sparse path share: sparse.hip (the add and prune kernels), sparse_predict.hip (the
 // predict / likelihood / train kernels) and sparse_api.hip (the gpc_sparse_* C-ABI).
 #pragma once
 
@@ -29,6 +29,9 @@ __device__ static __forceinline__ double sp_kstar(double sf, double x0, double x
 // sparse.hip: the phases of one add call
 int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, const int32_t* perm,
                   int32_t* status);
+// sparse.hip: gpc_sparse_prune_dev behind its argument checks (removed / order / scores / status may be nullptr; target == nullptr: keep)
+int sp_prune_launch(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order, double* scores,
+                    int32_t* status);
 // sparse_predict.hip.  off == nullptr: every patch at the shared grid xs0 / xs1 [m]; else patch i at its own points off[i] .. off[i+1]-1 of
 // xs0 / xs1 (m == 0, plane stride n_total).  max_blocks: cap on the resident workgroups per CU of the regular kernel.
 int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, const double* xs0, const double* xs1, double* f_star,

@@ -916,7 +916,24 @@ gp_compressor* gp_compressor::load_model(const std::string& path, int device)
         check(gpc_sparse_set_state(g->rgb_gps_, bc.data(), ac.data(), nullptr, nullptr, bvc.data()), g->ctx_, "gpc_sparse_set_state(rgb)");
     }
     g->trained_ = true;
+    g->loaded_ = true;
     return g.release();
+}
+
+std::array<long long, 2> gp_compressor::prune(int keep_depth, int keep_rgb, double tol_depth, double tol_rgb)
+{
+    if (model_ != gp_model::sparse) throw std::runtime_error("prune: the sparse model only");
+    if (!devices_.empty()) throw std::runtime_error("prune: the single-device flow only (the sharded states live on their devices)");
+    if (loaded_) throw std::runtime_error("prune: a loaded model holds (BV, alpha) only; prune the trained object before save_model");
+    if (!trained_) { project_cloud(); train_processes(); }
+    const int P = batch_.patches();
+    std::array<long long, 2> total = {0, 0};
+    if (P <= 0) return total;
+    std::vector<int32_t> rd_((size_t)P), rc_((size_t)P);
+    check(gpc_sparse_prune(gps_, keep_depth, nullptr, tol_depth, rd_.data(), nullptr, nullptr, nullptr), ctx_, "gpc_sparse_prune(depth)");
+    check(gpc_sparse_prune(rgb_gps_, keep_rgb, nullptr, tol_rgb, rc_.data(), nullptr, nullptr, nullptr), ctx_, "gpc_sparse_prune(rgb)");
+    for (int i = 0; i < P; ++i) { total[0] += rd_[i]; total[1] += rc_[i]; }
+    return total;
 }
 
 }  // namespace gpc
@@ -1035,6 +1052,26 @@ long long gpc_host_save_model(void* h, const char* path, char* err, int errlen)
 {
     try {
         return (long long)static_cast<gpc::gp_compressor*>(h)->save_model(path);
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// rate control: gp_compressor::prune (trains first if needed); removed[2] = vectors removed {depth, colour}.  Returns 0, or < 0 on error.
+int gpc_host_prune(void* h, int keep_depth, int keep_rgb, double tol_depth, double tol_rgb, long long removed[2], char* err, int errlen)
+{
+    try {
+        const auto r = static_cast<gpc::gp_compressor*>(h)->prune(keep_depth, keep_rgb, tol_depth, tol_rgb);
+        if (removed) { removed[0] = r[0]; removed[1] = r[1]; }
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// load_compressed() of the object as it stands (trained, possibly pruned): the point count or < 0
+int gpc_host_load_compressed(void* h, float* out_xyz, uint8_t* out_rgb, int capacity_pts, char* err, int errlen)
+{
+    try {
+        return put_cloud(static_cast<gpc::gp_compressor*>(h)->load_compressed(), out_xyz, out_rgb, capacity_pts);
     } catch (const std::exception& e) {
         return fail(e, err, errlen);
     }

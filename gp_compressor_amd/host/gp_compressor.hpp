@@ -79,6 +79,12 @@ public:
     // Sparse model only.  Returns the number of bytes written.
     size_t save_model(const std::string& path);
     static gp_compressor* load_model(const std::string& path, int device = 0);
+    // Rate control: prune every patch's depth GP to keep_depth and its colour GP to keep_rgb basis vectors, then on while the lowest
+    // score |alpha_i|^2 / (Q_ii + C_ii) is below tol_depth / tol_rgb (gpc_sparse_prune: the reference's capacity deletion,
+    // src/sparse_gp.hpp:206-223, continued).  In place; trains first if needed.  save_model() then writes the smaller model (24 bytes
+    // less per depth vector, 40 per colour vector; same file format).  Sparse model, single-device flow, and an object that was
+    // trained here (a loaded model has no C and Q); anything else throws.  Returns the vectors removed {depth, colour}.
+    std::array<long long, 2> prune(int keep_depth, int keep_rgb, double tol_depth = 0.0, double tol_rgb = 0.0);
 
     // host-only part, usable without a GPU
     void project_cloud();                            // src/gp_compressor.cpp:177-249
@@ -117,6 +123,7 @@ protected:
     int device_;
     patch_batch batch_;
     bool projected_ = false, trained_ = false;
+    bool loaded_ = false;                     // load_model: (BV, alpha) only
     gpc_ctx* ctx_ = nullptr;
     gpc_sparse* gps_ = nullptr;
     gpc_sparse* rgb_gps_ = nullptr;

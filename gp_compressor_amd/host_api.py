@@ -45,6 +45,8 @@ def load():
         L.gpc_host_save_model.restype = C.c_longlong
         L.gpc_host_save_model.argtypes = [vp, C.c_char_p, vp, i]
         L.gpc_host_decompress_file.argtypes = [C.c_char_p, i, vp, vp, i, vp, i]
+        L.gpc_host_prune.argtypes = [vp, i, i, d, d, vp, vp, i]
+        L.gpc_host_load_compressed.argtypes = [vp, vp, vp, i, vp, i]
         L.gpc_host_shard.argtypes = [vp, i, i, i] + [vp] * 12 + [i]
         L.gpc_host_shard_scatter.argtypes = [vp, i, i, i, vp, vp, vp, i]
         _lib = L
@@ -146,6 +148,27 @@ class GpCompressor:
         if n < 0:
             raise RuntimeError(f"save_model failed: {err.value.decode()}")
         return int(n)
+
+    def prune(self, keep_depth, keep_rgb, tol_depth=0.0, tol_rgb=0.0):
+        """gp_compressor::prune: every patch's depth / colour GP down to keep_depth / keep_rgb basis vectors, then on while the lowest
+        score is below the tolerance; in place (trains first if needed).  Returns (removed_depth, removed_rgb), summed over the patches."""
+        err = C.create_string_buffer(512)
+        rm = np.zeros(2, dtype=np.int64)
+        if self.L.gpc_host_prune(self.h, int(keep_depth), int(keep_rgb), float(tol_depth), float(tol_rgb), rm.ctypes.data,
+                                 C.addressof(err), 512) != 0:
+            raise RuntimeError(f"prune failed: {err.value.decode()}")
+        return int(rm[0]), int(rm[1])
+
+    def load_compressed(self):
+        """load_compressed() of the object as it stands (trained, possibly pruned): (xyz float32 (M,3), rgb uint8 (M,3))"""
+        cap = self.L.gpc_host_patch_count(self.h) * self.sz * self.sz
+        oxyz = np.zeros((max(cap, 1), 3), dtype=np.float32)
+        orgb = np.zeros((max(cap, 1), 3), dtype=np.uint8)
+        err = C.create_string_buffer(512)
+        n = self.L.gpc_host_load_compressed(self.h, oxyz.ctypes.data, orgb.ctypes.data, cap, C.addressof(err), 512)
+        if n < 0:
+            raise RuntimeError(f"load_compressed failed ({n}): {err.value.decode()}")
+        return oxyz[:n], orgb[:n]
 
 
 def decompress_file(path, capacity_pts, device=0):

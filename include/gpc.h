@@ -351,6 +351,39 @@ int gpc_sparse_set_state(gpc_sparse* g, const int32_t* bv_count, const double* a
  * on the device -- and every other patch is empty, as after gpc_sparse_reset.  old_to_new: host, old's P entries, strictly
  * increasing, < P_new (else GPC_EINVAL).  old is untouched; the two objects are destroyed independently. */
 int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_sparse** out);
+/* Rate control: prune every patch's basis IN PLACE by continuing the reference's capacity deletion (src/sparse_gp.hpp:206-223 with
+ * delete_bv :252-295; field variant src/sparse_gp_field.hpp:219-263) as a step of its own.  Per patch, with b its basis count and
+ * t = max(1, target[p]) (target == NULL: t = keep):
+ *     loop:
+ *       if b <= 1: stop
+ *       scan i = 0 .. b-1 ascending:  s_i = (sum_c alpha[c][i]^2) / (Q_ii + C_ii)
+ *       (minscore, loc) = the reference's arg-min: `if (i == 0 || s_i < minscore)` -- a NaN score at index 0 sticks, a NaN score
+ *                         at any other index is never chosen, equal scores go to the lower index
+ *       if b > t:                      remove
+ *       else if minscore < score_tol:  remove              (a NaN minscore compares false: stop)
+ *       else:                          stop
+ *       order[p][step] = loc;  scores[p][step] = minscore;  delete_bv(loc);  b -= 1;  step += 1
+ * Afterwards the patch's basis count is b and removed[p] = step; its point counter is untouched.  If at least one vector was removed
+ * and C(0,0) is NaN the patch's sticky status becomes GPC_STATUS_NAN, as after an add.  An empty patch is left alone.  delete_bv runs
+ * on the full matrices in every workgroup shape and there are no atomics: the same state gives the same bits, whatever the shape.
+ *   keep      used when target == NULL; must then be >= 1 (else GPC_EINVAL)
+ *   target    [P] or NULL.  Entries below 1 count as 1 (a device array cannot be validated without a synchronisation)
+ *   score_tol >= 0; +inf prunes every patch down to one vector; NaN or a negative value is GPC_EINVAL.  0 removes by count only
+ *   removed   [P], may be NULL
+ *   order, scores  [P][ld] with ld = gpc_sparse_ld(g), each may be NULL: the removal trace.  `order` holds the index each removed
+ *             vector had when it went (delete_bv moves the last vector into its place).  Entries at and beyond removed[p] are left
+ *             as they were
+ *   status    [P], may be NULL: the sticky status of every patch after the call
+ * ny = 1 and ny = 3; params.ref_field_delete_bug applies as in the add path (with it set, the field variant multiplies by q* + c* where
+ * the derivation divides: a few removals per patch stay finite, a long chain diverges as it does while training).  The capacity of the object is unchanged, so later
+ * gpc_sparse_add calls may grow the basis again.  The call is destructive: gpc_sparse_remap with P_new = P and the identity table is
+ * the non-destructive copy to prune from (one trained object then gives every rate below it).
+ * gpc_sparse_prune_dev takes DEVICE pointers, enqueues on the context's stream and never synchronises; gpc_sparse_prune takes HOST
+ * pointers and is synchronous.  P == 0: GPC_OK.  GPC_EINVAL: a NULL or dead object, and the argument errors above. */
+int gpc_sparse_prune(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order, double* scores,
+                     int32_t* status);
+int gpc_sparse_prune_dev(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order,
+                         double* scores, int32_t* status);
 
 /* ---- hyper-parameter training: the live part of sparse_gp::train_parameters ---------------- */
 /* src/sparse_gp.hpp:586-640 up to the exit(0) at :640 (the call site is commented out upstream, src/gp_compressor.cpp:161):
