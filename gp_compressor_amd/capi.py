@@ -126,6 +126,8 @@ PROTOTYPES = {
     "gpc_sparse_remap": (C.c_int, [_vp, _i, _vp, C.POINTER(_vp)]),
     "gpc_sparse_prune": (C.c_int, [_vp, _i, _vp, _d, _vp, _vp, _vp, _vp]),
     "gpc_sparse_prune_dev": (C.c_int, [_vp, _i, _vp, _d, _vp, _vp, _vp, _vp]),
+    "gpc_sparse_prune_rd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _d, _vp] + [_vp] * 7),
+    "gpc_sparse_prune_rd_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _d, _vp] + [_vp] * 7),
     "gpc_reproject": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_reproject_dev": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_project_cloud": (C.c_int, [_vp, _vp, _i, _d, _i, C.POINTER(_vp)]),
@@ -903,6 +905,41 @@ class Sparse:
         self.ctx._check(self.lib.gpc_sparse_prune_dev(self.h, 0 if keep is None else int(keep), _ptr(target), float(score_tol),
                                                       _ptr(removed), _ptr(order), _ptr(scores), _ptr(status)))
 
+    def prune_rd(self, off, x0, x1, y, keep=None, target=None, max_mse=float("inf"), max_mse_p=None, want_trace=False):
+        """gpc_sparse_prune_rd (host arrays): the removals of prune, each taken only while the mean square error of the state it would
+        leave on the patch's own points -- patch p owns rows off[p] .. off[p+1]-1 of x0, x1 and y (ny, N) -- stays within max_mse (or its
+        entry of max_mse_p, (P,)); stops at the first look-ahead beyond the bound.  In place.  Returns removed (P,) int32, mse0 (P,) the
+        error before the call (NaN for a patch without points) and mse_next (P,) the look-ahead that stopped the patch (NaN when the
+        floor keep / target stopped it); with want_trace also order (P, ld) int32, scores (P, ld) and mse (P, ld): the first removed[p]
+        entries of a row are the removals in order and the error after each, the others stay -1 / NaN."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N = int(off[-1]) if len(off) else 0
+        assert off.shape[0] == self.P + 1 and x0.shape[0] == N and x1.shape[0] == N and y.size == self.ny * N
+        tg = None if target is None else np.ascontiguousarray(target, dtype=np.int32)
+        bp = None if max_mse_p is None else np.ascontiguousarray(max_mse_p, dtype=np.float64)
+        assert (tg is None or tg.shape == (self.P,)) and (bp is None or bp.shape == (self.P,))
+        ld = self.ld()
+        rm = np.zeros(self.P, dtype=np.int32)
+        mse0, nxt = np.full(self.P, np.nan), np.full(self.P, np.nan)
+        order = np.full((self.P, ld), -1, dtype=np.int32) if want_trace else None
+        scores = np.full((self.P, ld), np.nan) if want_trace else None
+        mse = np.full((self.P, ld), np.nan) if want_trace else None
+        self.ctx._check(self.lib.gpc_sparse_prune_rd(self.h, _ptr(off), _ptr(x0), _ptr(x1), _ptr(y), 0 if keep is None else int(keep),
+                                                     _ptr(tg), float(max_mse), _ptr(bp), _ptr(rm), _ptr(order), _ptr(scores), _ptr(mse),
+                                                     _ptr(mse0), _ptr(nxt), None))
+        return (rm, mse0, nxt, order, scores, mse) if want_trace else (rm, mse0, nxt)
+
+    def prune_rd_dev(self, off, n_total, x0, x1, y, keep=None, target=None, max_mse=float("inf"), max_mse_p=None, removed=None, order=None,
+                     scores=None, mse=None, mse0=None, mse_next=None, status=None):
+        """gpc_sparse_prune_rd_dev: device buffers (each output may be None), enqueued on the context's stream"""
+        self.ctx._check(self.lib.gpc_sparse_prune_rd_dev(self.h, _ptr(off), int(n_total), _ptr(x0), _ptr(x1), _ptr(y),
+                                                         0 if keep is None else int(keep), _ptr(target), float(max_mse), _ptr(max_mse_p),
+                                                         _ptr(removed), _ptr(order), _ptr(scores), _ptr(mse), _ptr(mse0), _ptr(mse_next),
+                                                         _ptr(status)))
+
     def sizes(self):
         b = np.zeros(self.P, dtype=np.int32)
         self.ctx._check(self.lib.gpc_sparse_sizes(self.h, _ptr(b)))
@@ -1064,6 +1101,20 @@ class Mapping:
         self.depth.prune_dev(keep=keep_depth, score_tol=score_tol_depth)
         self.rgb.prune_dev(keep=keep_rgb, score_tol=score_tol_rgb)
         self.ctx.synchronize()
+
+    def prune_to_error(self, max_mse_depth, max_mse_rgb, keep_depth=1, keep_rgb=1):
+        """Bound the map by distortion: prune the depth and the colour GP of every leaf in place (Sparse.prune_rd_dev) while the mean
+        square error on the points of the map's current batch -- the last inserted scan -- stays within max_mse_depth / max_mse_rgb.
+        Leaves the scan did not touch have no points there and are left alone.  Returns removed (P,) int32 per GP: (depth, colour)."""
+        import torch
+        v = self.patches.view
+        rm = torch.zeros((2, max(v.P, 1)), dtype=torch.int32, device=self.cells.device)
+        torch.cuda.synchronize(rm.device)
+        self.depth.prune_rd_dev(v.off, v.n_total, v.x0, v.x1, v.y, keep=keep_depth, max_mse=max_mse_depth, removed=rm[0])
+        self.rgb.prune_rd_dev(v.off, v.n_total, v.x0, v.x1, v.rgb, keep=keep_rgb, max_mse=max_mse_rgb, removed=rm[1])
+        self.ctx.synchronize()
+        out = rm.cpu().numpy()
+        return out[0, :v.P], out[1, :v.P]
 
     def render(self, origin, dirs, params=None, use_cells=True, want=("leaf", "range", "local")):
         """The map as a sensor at `origin` sees it along `dirs` (Context.camera_rays, or any (n, 3) float64 device tensor): Patches.render

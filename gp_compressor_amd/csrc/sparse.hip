@@ -1612,6 +1612,194 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_prune_kernel(SpPruneParams 
     }
 }
 
+// ---- prune to a distortion bound (include/gpc.h, gpc_sparse_prune_rd_dev) -----------------------------------------------------------
+// The removals of sparse_prune_kernel -- same scan, same arg-min, the unchanged full-matrix sp_delete_bv -- but before a vector goes the
+// kernel LOOKS AHEAD: it forms the alpha and BV that delete_bv(loc) would leave (O(b): column loc of C and Q, nothing of the O(b^2)
+// downdate), evaluates the mean square error of that state on the patch's own points, and removes only if the error stays within the
+// patch's bound.  A look-ahead instead of remove-and-undo: delete_bv is not invertible in floating point (the downdate of C and Q loses
+// the removed row), so an undo would need a copy of the 16 b^2 bytes of state per step, where the look-ahead writes nothing.
+// Summation order of the error (fixed, independent of the workgroup shape): f_ci over j ascending in the post-removal index order, e_i
+// over c ascending, point i into class i mod 64, each class in ascending i (one wave walks the chunks of per-point errors that the
+// workgroup leaves in LDS), the 64 classes by the xor tree 32, 16, .. 1 (gpc_wave_sum).  No atomics.
+// The kernel values k_ij are recomputed at every step: keeping the patch's n x b table in a per-workgroup region of the workspace and
+// reading it back was measured and lost (40.9 against 23.0 ms), and is not kept.
+struct SpPruneRdParams {
+    int P, ny, ld, keep, field_bug, n_total;
+    const int32_t* target;     // [P] or nullptr (every patch: keep)
+    const int32_t* off;
+    const double *x0, *x1, *y;
+    double max_mse;
+    const double* max_mse_p;   // [P] or nullptr (every patch: max_mse)
+    double sf, c_exp;
+    double *alpha, *C, *Q, *BV;
+    int32_t *b, *stat;
+    int32_t *removed, *order, *status_out;   // each may be nullptr
+    double *scores, *mse, *mse0, *mse_next;  // each may be nullptr
+};
+
+// mean square error of the state (al [NY][ld], bv [ld][2], both in LDS, nb vectors) on the n points of the patch; every thread calls and
+// gets the result.
+template <int NY>
+__device__ static double sp_rd_mse(const double* al, const double* bv, int nb, int ld, const double* x0, const double* x1, const double* y,
+                                   int n, int n_total, double sf, double c_exp, const double* T, double* ebuf, double* sres)
+{
+    const int tid = threadIdx.x, nth = SP_NTH;
+    double acc = 0.0;                                   // wave 0: lane l holds class l
+    __syncthreads();                                    // al / bv are written, ebuf / sres of the previous call are free
+    for (int i0 = 0; i0 < n; i0 += nth) {
+        const int i = i0 + tid;
+        double e = 0.0;
+        if (i < n) {
+            const double px0 = x0[i], px1 = x1[i];
+            double f[NY];
+#pragma unroll
+            for (int c = 0; c < NY; ++c) f[c] = 0.0;
+            for (int j = 0; j < nb; ++j) {
+                const double k = gpc_rbf_neg(sf, c_exp, px0, px1, bv[2 * j], bv[2 * j + 1], T);
+#pragma unroll
+                for (int c = 0; c < NY; ++c) f[c] += al[c * ld + j] * k;
+            }
+#pragma unroll
+            for (int c = 0; c < NY; ++c) {
+                const double d = y[(size_t)c * n_total + i] - f[c];
+                e += d * d;
+            }
+        }
+        ebuf[tid] = e;
+        __syncthreads();
+        if (tid < 64)
+            for (int q = 0; q < nth; q += 64)
+                if (i0 + q + tid < n) acc += ebuf[q + tid];       // i0 and q are multiples of 64: class tid, ascending i
+        __syncthreads();
+    }
+    if (tid < 64) {
+        acc = gpc_wave_sum(acc);
+        if (tid == 0) sres[0] = acc;
+    }
+    __syncthreads();
+    return sres[0] / (double)(n * NY);
+}
+
+template <int NY>
+__global__ __launch_bounds__(SP_THREADS) void sparse_prune_rd_kernel(SpPruneRdParams A)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, ld = A.ld, ny = A.ny;  // (ny == NY)
+    double* sval = reinterpret_cast<double*>(smem);     // 4
+    int* sidx = reinterpret_cast<int*>(sval + 4);       // 4 ints (2 doubles)
+    double* sres = sval + 6;                           // 2 (the base of what follows stays 16-byte aligned)
+    double* T = sval + 8;                               // 64
+    double* Cstar = T + GPC_EXP_TABLE_SIZE;             // delete_bv scratch, [ld] each; the look-ahead reads the first two
+    double* Qstar = Cstar + ld;
+    double* Crep = Qstar + ld;
+    double* Qrep = Crep + ld;
+    double* al = Qrep + ld;                             // [NY][ld]: alpha of the state whose error is taken
+    double* bv = al + NY * ld;                          // [ld][2]
+    double* ebuf = bv + 2 * ld;                         // [SP_NTH]: per-point errors of a chunk
+    gpc_exp_table_init(T);
+    for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
+        SpState S;
+        // (S.ny from the kernel argument, not NY: sp_delete_bv is then compiled as it is in sparse_prune_kernel.  With the constant the
+        // compiler drops the select between its two alpha updates and fuses the ny = 1 one into an FMA: other bits than the prune's)
+        S.ld = ld; S.ny = ny; S.ldm = ld;
+        S.alpha = A.alpha + (size_t)patch * NY * ld;
+        S.C = A.C + (size_t)patch * ld * ld;
+        S.Q = A.Q + (size_t)patch * ld * ld;
+        S.BV = A.BV + (size_t)patch * ld * 2;
+        int b = A.b[patch];
+        if (b > ld) b = ld;                             // (gpc_sparse_set_state admits no more)
+        int st = A.stat[patch];
+        const int tp = A.target ? A.target[patch] : A.keep;
+        const int t = tp > 1 ? tp : 1;
+        const int o = A.off[patch], n = A.off[patch + 1] - o;
+        const double bound = A.max_mse_p ? A.max_mse_p[patch] : A.max_mse;
+        const double *x0 = A.x0 + o, *x1 = A.x1 + o, *y = A.y + o;
+        const double nan = __builtin_nan("");
+        int step = 0;
+        double e0 = nan, enext = nan;
+        __syncthreads();                                // the scratch of the previous patch is free
+        if (n > 0) {
+            for (int i = tid; i < b; i += SP_NTH) {
+                bv[2 * i] = S.BV[2 * i];
+                bv[2 * i + 1] = S.BV[2 * i + 1];
+#pragma unroll
+                for (int c = 0; c < NY; ++c) al[c * ld + i] = S.alpha[c * ld + i];
+            }
+            e0 = sp_rd_mse<NY>(al, bv, b, ld, x0, x1, y, n, A.n_total, A.sf, A.c_exp, T, ebuf, sres);
+            while (b > 1 && b > t) {
+                double best = 0.0;
+                int loc = 0x7fffffff;
+                bool have = false;
+                for (int i = tid; i < b; i += SP_NTH) {
+                    // (ny from the kernel argument, not NY: the loop of sparse_prune_kernel as it stands there -- unrolled over a
+                    // constant, the compiler may fuse another product of the sum, and the scores are promised bit for bit)
+                    double a2 = 0.0;
+                    for (int c = 0; c < ny; ++c) { const double a = S.alpha[c * ld + i]; a2 += a * a; }
+                    const double score = a2 / (S.Q[sp_at<false>(i, i, ld)] + S.C[sp_at<false>(i, i, ld)]);
+                    if (!have || SP_TAKE(score, i, best, loc)) { best = score; loc = i; have = true; }
+                }
+                if (!have) best = __builtin_inf();
+                sp_block_argmin(best, loc, sval, sidx);
+                if (loc < 0 || loc >= b) loc = 0;
+                // the look-ahead: alpha and BV as sp_delete_bv(loc) would leave them, into LDS
+                const int last = b - 1, nb = b - 1;
+                double alphastar[3];
+                for (int c = 0; c < ny; ++c) alphastar[c] = S.alpha[c * ld + loc];
+                const double cstar = S.C[sp_at<false>(loc, loc, ld)];
+                const double qstar = S.Q[sp_at<false>(loc, loc, ld)];
+                __syncthreads();                        // (the previous look-ahead's readers of Cstar / Qstar / al / bv are through)
+                for (int i = tid; i < b; i += SP_NTH) {
+                    Cstar[i] = S.C[i + (size_t)loc * ld];
+                    Qstar[i] = S.Q[i + (size_t)loc * ld];
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    Cstar[loc] = Cstar[last];
+                    Qstar[loc] = Qstar[last];
+                }
+                __syncthreads();
+                const double qc_den = qstar + cstar;
+                for (int i = tid; i < nb; i += SP_NTH) {
+                    const int src = i == loc ? last : i;
+                    const double qc = Qstar[i] + Cstar[i];
+                    bv[2 * i] = S.BV[2 * src];
+                    bv[2 * i + 1] = S.BV[2 * src + 1];
+                    for (int c = 0; c < ny; ++c) {                       // (the loop of sp_delete_bv, in its form)
+                        double a = S.alpha[c * ld + src];
+                        if (ny == 1) a -= alphastar[0] / qc_den * qc;
+                        else a -= alphastar[c] * (A.field_bug ? qc_den * qc : qc / qc_den);
+                        al[c * ld + i] = a;
+                    }
+                }
+                const double e = sp_rd_mse<NY>(al, bv, nb, ld, x0, x1, y, n, A.n_total, A.sf, A.c_exp, T, ebuf, sres);
+                if (!(e <= bound)) { enext = e; break; }       // (a NaN error or a NaN bound compares false: stop)
+                if (tid == 0) {
+                    if (A.order) A.order[(size_t)patch * ld + step] = loc;
+                    if (A.scores) A.scores[(size_t)patch * ld + step] = best;
+                    if (A.mse) A.mse[(size_t)patch * ld + step] = e;
+                }
+                b = sp_delete_bv<SP_RMW, false, false>(S, b, loc, A.field_bug, Cstar, Qstar, Crep, Qrep);
+                ++step;
+            }
+        }
+        // isnan(C(0,0)) -> "sparse_gp::C has become Nan" (:245), as after a point of the add path
+        if (step > 0) {
+            const double c00 = S.C[0];
+            if (c00 != c00 && st == GPC_STATUS_OK) st = GPC_STATUS_NAN;
+        }
+        if (tid == 0) {
+            if (step > 0) {
+                A.b[patch] = b;
+                A.stat[patch] = st;
+            }
+            if (A.removed) A.removed[patch] = step;
+            if (A.mse0) A.mse0[patch] = e0;
+            if (A.mse_next) A.mse_next[patch] = enext;
+            if (A.status_out) A.status_out[patch] = st;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 static size_t sp_add_lds_small(int bm = SP_BMAX) { return sizeof(double) * (size_t)(64 + 16 + 6 + 4 * (bm + 2) + 22 * (bm + 1) + 2 * bm * bm); }
@@ -1782,6 +1970,38 @@ int sp_prune_launch(gpc_sparse* g, int keep, const int32_t* target, double score
     // registers leave room for four waves per SIMD)
     const int grid = std::min(g->P, ctx->num_cus * (1024 / nth));
     hipLaunchKernelGGL(sparse_prune_kernel, dim3(grid), dim3(nth), lds, ctx->stream, A);
+    GPC_HIP(ctx, hipGetLastError());
+    return GPC_OK;
+}
+
+int sp_prune_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
+                       const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order, double* scores,
+                       double* mse, double* mse0, double* mse_next, int32_t* status)
+{
+    gpc_ctx* ctx = g->ctx;
+    SpPruneRdParams A;
+    A.P = g->P; A.ny = g->ny; A.ld = g->ld; A.keep = keep; A.field_bug = g->prm.ref_field_delete_bug; A.n_total = n_total;
+    A.target = target;
+    A.off = off; A.x0 = x0; A.x1 = x1; A.y = y;
+    A.max_mse = max_mse; A.max_mse_p = max_mse_p;
+    A.sf = g->prm.sigmaf_sq;
+    A.c_exp = (double)(-0.5f) / g->prm.l_sq;
+    A.alpha = g->alpha; A.C = g->C; A.Q = g->Q; A.BV = g->BV;
+    A.b = g->b; A.stat = g->stat;
+    A.removed = removed; A.order = order; A.scores = scores; A.status_out = status;
+    A.mse = mse; A.mse0 = mse0; A.mse_next = mse_next;
+    // the workgroup shapes of sp_prune_launch; the error sum is laid out so that they give the same bits
+    const int cap_ = g->prm.capacity;
+    const int nth = (cap_ <= 0 || getenv("GPC_SPARSE_WIDE")) ? SP_THREADS : cap_ <= 64 ? 64 : cap_ <= 100 ? 128 : SP_THREADS;
+    const size_t lds = sizeof(double) * (size_t)(8 + GPC_EXP_TABLE_SIZE + (6 + g->ny) * g->ld + nth);
+    // as many workgroups as the device holds at once: the kernel's registers admit fewer waves per SIMD than sparse_prune_kernel's, and
+    // workgroups beyond the resident ones would only queue behind them (asked of the runtime per call: host-side only, no synchronisation)
+    void (*const kernel)(SpPruneRdParams) = g->ny == 1 ? sparse_prune_rd_kernel<1> : sparse_prune_rd_kernel<3>;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nth, lds) != hipSuccess || per_cu < 1) per_cu = 768 / nth;
+    per_cu = std::min(per_cu, 1024 / nth);
+    const int grid = std::min(g->P, ctx->num_cus * per_cu);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(nth), lds, ctx->stream, A);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }

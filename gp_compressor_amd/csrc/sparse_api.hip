@@ -208,6 +208,36 @@ int gpc_sparse_prune_dev(gpc_sparse* g, int keep, const int32_t* target, double 
     return sp_prune_launch(g, keep, target, score_tol, removed, order, scores, status);
 }
 
+// what both distortion-bounded prune entries check before they look at the batch (include/gpc.h)
+static int sp_prune_rd_check(gpc_sparse* g, int keep, const int32_t* target, double max_mse, const double* max_mse_p)
+{
+    gpc_ctx* ctx = g->ctx;
+    if (g->prm.noise_model != GPC_NOISE_GAUSSIAN)
+        return gpc_fail(ctx, GPC_EINVAL, "prune_rd: the error is taken against the Gaussian read-out (noise_model 0), got %d", g->prm.noise_model);
+    if (!target && keep < 1) return gpc_fail(ctx, GPC_EINVAL, "keep must be >= 1 when target is NULL, got %d", keep);
+    if (!max_mse_p && !(max_mse >= 0.0)) return gpc_fail(ctx, GPC_EINVAL, "max_mse must be >= 0 (+inf allowed), got %g", max_mse);
+    return GPC_OK;
+}
+
+int gpc_sparse_prune_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
+                            const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order,
+                            double* scores, double* mse, double* mse0, double* mse_next, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_prune_rd_check(g, keep, target, max_mse, max_mse_p)) return rc;
+    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (g->P == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_prune_rd_launch(g, off, n_total, x0, x1, y, keep, target, max_mse, max_mse_p, removed, order, scores, mse, mse0, mse_next,
+                              status);
+}
+
 int gpc_sparse_predict_dev(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
                            int conf, int32_t* status)
 {
@@ -417,6 +447,47 @@ int gpc_sparse_prune(gpc_sparse* g, int keep, const int32_t* target, double scor
     st.down(removed, d_rm, P);
     st.down(order, d_order, W);
     st.down(scores, d_scores, W);
+    st.down(status, d_st, P);
+    return st.finish();
+}
+
+int gpc_sparse_prune_rd(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y, int keep,
+                        const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order, double* scores,
+                        double* mse, double* mse0, double* mse_next, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_prune_rd_check(g, keep, target, max_mse, max_mse_p)) return rc;
+    const size_t P = (size_t)g->P, W = P * (size_t)g->ld, ny = (size_t)g->ny;
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (P == 0) return GPC_OK;
+    if (int rc = gpc_check_host_off(ctx, (int)P, off, nullptr, nullptr)) return rc;
+    const size_t N = (size_t)off[P];
+    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_prune_rd");
+    const int32_t* d_off = st.up(off, P + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N * ny);
+    const int32_t* d_target = target ? st.up(target, P) : nullptr;
+    const double* d_bound = max_mse_p ? st.up(max_mse_p, P) : nullptr;
+    int32_t* d_rm = removed ? st.out<int32_t>(P) : nullptr;
+    // the traces go up first: the entries at and beyond removed[p] come back as the caller left them
+    int32_t* d_order = order ? st.up(order, W) : nullptr;
+    double* d_scores = scores ? st.up(scores, W) : nullptr;
+    double* d_mse = mse ? st.up(mse, W) : nullptr;
+    double* d_mse0 = mse0 ? st.out<double>(P) : nullptr;
+    double* d_next = mse_next ? st.out<double>(P) : nullptr;
+    int32_t* d_st = status ? st.out<int32_t>(P) : nullptr;
+    if (st.ok())
+        st.rc = gpc_sparse_prune_rd_dev(g, d_off, (int)N, d_x0, d_x1, d_y, keep, d_target, max_mse, d_bound, d_rm, d_order, d_scores, d_mse,
+                                        d_mse0, d_next, d_st);
+    st.down(removed, d_rm, P);
+    st.down(order, d_order, W);
+    st.down(scores, d_scores, W);
+    st.down(mse, d_mse, W);
+    st.down(mse0, d_mse0, P);
+    st.down(mse_next, d_next, P);
     st.down(status, d_st, P);
     return st.finish();
 }

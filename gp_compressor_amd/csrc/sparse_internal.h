@@ -32,6 +32,10 @@ int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* 
 // sparse.hip: gpc_sparse_prune_dev behind its argument checks (removed / order / scores / status may be nullptr; target == nullptr: keep)
 int sp_prune_launch(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order, double* scores,
                     int32_t* status);
+// sparse.hip: gpc_sparse_prune_rd_dev behind its argument checks (every output may be nullptr; max_mse_p == nullptr: max_mse)
+int sp_prune_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
+                       const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order, double* scores,
+                       double* mse, double* mse0, double* mse_next, int32_t* status);
 // sparse_predict.hip.  off == nullptr: every patch at the shared grid xs0 / xs1 [m]; else patch i at its own points off[i] .. off[i+1]-1 of
 // xs0 / xs1 (m == 0, plane stride n_total).  max_blocks: cap on the resident workgroups per CU of the regular kernel.
 int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, const double* xs0, const double* xs1, double* f_star,

@@ -936,6 +936,26 @@ std::array<long long, 2> gp_compressor::prune(int keep_depth, int keep_rgb, doub
     return total;
 }
 
+std::array<long long, 2> gp_compressor::prune_to_error(double max_mse_depth, double max_mse_rgb, int keep_depth, int keep_rgb)
+{
+    if (model_ != gp_model::sparse) throw std::runtime_error("prune_to_error: the sparse model only");
+    if (!devices_.empty()) throw std::runtime_error("prune_to_error: the single-device flow only (the sharded states live on their devices)");
+    if (loaded_) throw std::runtime_error("prune_to_error: a loaded model holds (BV, alpha) only; prune the trained object before save_model");
+    if (!trained_) { project_cloud(); train_processes(); }
+    const int P = batch_.patches();
+    std::array<long long, 2> total = {0, 0};
+    if (P <= 0) return total;
+    std::vector<int32_t> rd_((size_t)P), rc_((size_t)P);
+    check(gpc_sparse_prune_rd(gps_, batch_.off.data(), batch_.x0.data(), batch_.x1.data(), batch_.y.data(), keep_depth, nullptr, max_mse_depth,
+                              nullptr, rd_.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+          ctx_, "gpc_sparse_prune_rd(depth)");
+    check(gpc_sparse_prune_rd(rgb_gps_, batch_.off.data(), batch_.x0.data(), batch_.x1.data(), batch_.rgb.data(), keep_rgb, nullptr, max_mse_rgb,
+                              nullptr, rc_.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+          ctx_, "gpc_sparse_prune_rd(rgb)");
+    for (int i = 0; i < P; ++i) { total[0] += rd_[i]; total[1] += rc_[i]; }
+    return total;
+}
+
 }  // namespace gpc
 
 // ---- C doors for the Python test-suite -----------------------------------------------------------------------------
@@ -991,6 +1011,12 @@ void gpc_host_set_sparse_kernel(void* h, double sigmaf_sq, double l_sq, double s
     g->depth_params.noise = s20_depth;
     g->rgb_params.noise = s20_rgb;
     g->depth_params.capacity = g->rgb_params.capacity = capacity;
+}
+// rgb_params.ref_field_delete_bug (the class's default is the reference's multiply, 1): 0 lets the colour field delete as its derivation
+// says, which is what pruning colour below a few vectors needs (include/gpc.h, gpc_sparse_prune).  Before training.
+void gpc_host_set_field_delete_bug(void* h, int on)
+{
+    static_cast<gpc::gp_compressor*>(h)->rgb_params.ref_field_delete_bug = on ? 1 : 0;
 }
 int gpc_host_project(void* h)
 {
@@ -1061,6 +1087,18 @@ int gpc_host_prune(void* h, int keep_depth, int keep_rgb, double tol_depth, doub
 {
     try {
         const auto r = static_cast<gpc::gp_compressor*>(h)->prune(keep_depth, keep_rgb, tol_depth, tol_rgb);
+        if (removed) { removed[0] = r[0]; removed[1] = r[1]; }
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// rate control against a distortion bound: gp_compressor::prune_to_error (trains first if needed); removed[2] as above.  0, or < 0 on error.
+int gpc_host_prune_to_error(void* h, double max_mse_depth, double max_mse_rgb, int keep_depth, int keep_rgb, long long removed[2], char* err,
+                            int errlen)
+{
+    try {
+        const auto r = static_cast<gpc::gp_compressor*>(h)->prune_to_error(max_mse_depth, max_mse_rgb, keep_depth, keep_rgb);
         if (removed) { removed[0] = r[0]; removed[1] = r[1]; }
         return 0;
     } catch (const std::exception& e) {

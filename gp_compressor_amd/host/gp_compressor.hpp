@@ -85,6 +85,11 @@ public:
     // less per depth vector, 40 per colour vector; same file format).  Sparse model, single-device flow, and an object that was
     // trained here (a loaded model has no C and Q); anything else throws.  Returns the vectors removed {depth, colour}.
     std::array<long long, 2> prune(int keep_depth, int keep_rgb, double tol_depth = 0.0, double tol_rgb = 0.0);
+    // Rate control against a distortion bound: every patch's depth / colour GP sheds vectors by the same rule while the mean square error
+    // on the patch's own training points stays within max_mse_depth / max_mse_rgb, and never below keep_depth / keep_rgb vectors
+    // (gpc_sparse_prune_rd on the projected batch; it stops at the first removal that would exceed the bound).  Same preconditions and
+    // exceptions as prune(); save_model() then writes the smaller model.  Returns the vectors removed {depth, colour}.
+    std::array<long long, 2> prune_to_error(double max_mse_depth, double max_mse_rgb, int keep_depth = 1, int keep_rgb = 1);
 
     // host-only part, usable without a GPU
     void project_cloud();                            // src/gp_compressor.cpp:177-249

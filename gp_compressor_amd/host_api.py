@@ -33,6 +33,7 @@ def load():
         L.gpc_host_destroy.argtypes = [vp]
         L.gpc_host_seed.argtypes = [vp, C.c_uint]
         L.gpc_host_set_sparse_kernel.argtypes = [vp, d, d, d, d, i]
+        L.gpc_host_set_field_delete_bug.argtypes = [vp, i]
         L.gpc_host_project.argtypes = [vp]
         L.gpc_host_project_device.argtypes = [vp, vp, i]
         L.gpc_host_set_gpu_producer.argtypes = [vp, i]
@@ -46,6 +47,7 @@ def load():
         L.gpc_host_save_model.argtypes = [vp, C.c_char_p, vp, i]
         L.gpc_host_decompress_file.argtypes = [C.c_char_p, i, vp, vp, i, vp, i]
         L.gpc_host_prune.argtypes = [vp, i, i, d, d, vp, vp, i]
+        L.gpc_host_prune_to_error.argtypes = [vp, d, d, i, i, vp, vp, i]
         L.gpc_host_load_compressed.argtypes = [vp, vp, vp, i, vp, i]
         L.gpc_host_shard.argtypes = [vp, i, i, i] + [vp] * 12 + [i]
         L.gpc_host_shard_scatter.argtypes = [vp, i, i, i, vp, vp, vp, i]
@@ -82,6 +84,11 @@ class GpCompressor:
 
     def set_sparse_kernel(self, sigmaf_sq, l_sq, s20_depth, s20_rgb, capacity):
         self.L.gpc_host_set_sparse_kernel(self.h, sigmaf_sq, l_sq, s20_depth, s20_rgb, capacity)
+
+    def set_field_delete_bug(self, on):
+        """ref_field_delete_bug of the colour GP (default 1, the reference's multiply); 0: the field deletes as its derivation says, which
+        pruning colour deeply needs.  Before training."""
+        self.L.gpc_host_set_field_delete_bug(self.h, int(bool(on)))
 
     def project_cloud(self, device=False):
         """project_cloud() on the host, or (device=True) the same batch cut on the GPU"""
@@ -157,6 +164,17 @@ class GpCompressor:
         if self.L.gpc_host_prune(self.h, int(keep_depth), int(keep_rgb), float(tol_depth), float(tol_rgb), rm.ctypes.data,
                                  C.addressof(err), 512) != 0:
             raise RuntimeError(f"prune failed: {err.value.decode()}")
+        return int(rm[0]), int(rm[1])
+
+    def prune_to_error(self, max_mse_depth, max_mse_rgb, keep_depth=1, keep_rgb=1):
+        """gp_compressor::prune_to_error: every patch's depth / colour GP sheds vectors while the mean square error on its own training
+        points stays within max_mse_depth / max_mse_rgb, never below keep_depth / keep_rgb vectors; in place (trains first if needed).
+        Returns (removed_depth, removed_rgb), summed over the patches."""
+        err = C.create_string_buffer(512)
+        rm = np.zeros(2, dtype=np.int64)
+        if self.L.gpc_host_prune_to_error(self.h, float(max_mse_depth), float(max_mse_rgb), int(keep_depth), int(keep_rgb), rm.ctypes.data,
+                                          C.addressof(err), 512) != 0:
+            raise RuntimeError(f"prune_to_error failed: {err.value.decode()}")
         return int(rm[0]), int(rm[1])
 
     def load_compressed(self):

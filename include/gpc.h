@@ -384,6 +384,43 @@ int gpc_sparse_prune(gpc_sparse* g, int keep, const int32_t* target, double scor
                      int32_t* status);
 int gpc_sparse_prune_dev(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order,
                          double* scores, int32_t* status);
+/* Rate control against a distortion bound: the removals of gpc_sparse_prune, each taken only if the mean square error of the state it
+ * would leave, on the patch's own points, stays within the patch's bound ("the smallest model whose error stays below X").  IN PLACE.
+ * The batch is ragged like gpc_sparse_predict_points: patch p owns rows off[p] .. off[p+1]-1 of x0, x1 and of the ny planes of y (plane c
+ * at y + c * n_total) -- normally the points the object was trained on.  With n = off[p+1] - off[p], b the patch's basis count,
+ * t = max(1, target ? target[p] : keep) and B = max_mse_p ? max_mse_p[p] : max_mse:
+ *     mse0[p] = mse(current state)            (n == 0: NaN, and the patch is left alone: removed = 0, not a byte of its state moves)
+ *     loop:
+ *       if b <= 1 or b <= t: stop              (mse_next[p] = NaN)
+ *       (minscore, loc) = the arg-min of gpc_sparse_prune, exactly
+ *       alpha' = the alpha that delete_bv(loc) would write;  BV' = BV with vector b-1 moved to loc
+ *       e = mse(alpha', BV', b-1)              (a look-ahead: nothing has been written yet)
+ *       if !(e <= B): mse_next[p] = e; stop    (a NaN e, or a NaN entry of max_mse_p, compares false: stop)
+ *       order[p][step] = loc; scores[p][step] = minscore; mse[p][step] = e; delete_bv(loc); b -= 1; step += 1
+ * mse of a state (alpha, BV, b), in a summation order that is fixed and does not depend on the workgroup shape:
+ *     k_ij = sigmaf_sq * exp(c_exp * ((x0_i-BV_j0)^2 + (x1_i-BV_j1)^2)), c_exp = (double)(-0.5f) / l_sq, the library's exp
+ *     f_ci = sum_j alpha_cj k_ij, j ascending in the state's own index order;   e_i = sum_c (y_ci - f_ci)^2, c ascending
+ *     point i goes to class i mod 64, each class sums its e_i in ascending i, the 64 class sums are added by the xor-shuffle tree
+ *     d = 32, 16, .. 1;   mse = sse / (double)(n * ny)
+ * Afterwards removed[p] = step; the basis count, the sticky status, the untouched point counter and the untouched trace entries at and
+ * beyond removed[p] follow gpc_sparse_prune.  Every output pointer may be NULL; order, scores and mse are [P][ld], mse0 and mse_next [P].
+ *   - The loop stops at the FIRST look-ahead that exceeds the bound.  The error is not monotone along the chain (removing a vector can
+ *     lower it), so a later state might have been inside the bound again; the call does not search for it.
+ *   - With max_mse = +inf and max_mse_p == NULL the call leaves, bit for bit, the state, removed, order and scores of
+ *     gpc_sparse_prune(keep, target, score_tol = 0), and mse is the patch's rate-distortion curve.  Run it on a gpc_sparse_remap identity
+ *     copy to get the curve without touching the model.
+ *   - target >= b removes nothing and still returns mse0: that is how a caller forms relative bounds such as max_mse_p = 2 * mse0.
+ *   - The same inputs give the same bits in every workgroup shape; there are no atomics.
+ * GPC_EINVAL: a NULL or dead object; keep < 1 with target == NULL; max_mse NaN or negative with max_mse_p == NULL; n_total < 0; NULL off
+ * with P > 0; NULL x0, x1 or y with n_total > 0; an object whose noise_model is not 0.  P == 0: GPC_OK.
+ * gpc_sparse_prune_rd_dev takes DEVICE pointers, enqueues on the context's stream and never synchronises; gpc_sparse_prune_rd takes HOST
+ * pointers (n_total = off[P]) and is synchronous. */
+int gpc_sparse_prune_rd(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y, int keep,
+                        const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order, double* scores,
+                        double* mse, double* mse0, double* mse_next, int32_t* status);
+int gpc_sparse_prune_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
+                            const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order,
+                            double* scores, double* mse, double* mse0, double* mse_next, int32_t* status);
 
 /* ---- hyper-parameter training: the live part of sparse_gp::train_parameters ---------------- */
 /* src/sparse_gp.hpp:586-640 up to the exit(0) at :640 (the call site is commented out upstream, src/gp_compressor.cpp:161):
