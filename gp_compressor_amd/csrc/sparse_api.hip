@@ -128,6 +128,12 @@ int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_
         e = hipSetDevice(ctx->device);
         if (e == hipSuccess) e = hipMalloc(&d_map, 4 * (size_t)P);
         if (e == hipSuccess) e = hipMemcpyAsync(d_map, old_to_new, 4 * (size_t)P, hipMemcpyHostToDevice, st);
+        // the patches no old one moves into: a zero state, not what the allocation happened to hold (gpc_sparse_get_state reads it back)
+        const size_t ldz = (size_t)g->ld, Pn = (size_t)P_new;
+        if (e == hipSuccess) e = hipMemsetAsync(g->alpha, 0, 8 * Pn * (size_t)g->ny * ldz, st);
+        if (e == hipSuccess) e = hipMemsetAsync(g->C, 0, 8 * Pn * ldz * ldz, st);
+        if (e == hipSuccess) e = hipMemsetAsync(g->Q, 0, 8 * Pn * ldz * ldz, st);
+        if (e == hipSuccess) e = hipMemsetAsync(g->BV, 0, 8 * Pn * ldz * 2, st);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(sp_remap_kernel, dim3(P), dim3(256), 0, st, old->alpha, old->C, old->Q, old->BV, old->b, old->count, old->stat,
                                (const int32_t*)d_map, old->ny, old->ld, g->alpha, g->C, g->Q, g->BV, g->b, g->count, g->stat);

@@ -348,7 +348,7 @@ int gpc_sparse_set_state(gpc_sparse* g, const int32_t* bv_count, const double* a
                          const double* BV);
 /* The map grew (gpc_patches_insert_cloud): a NEW object of P_new patches with old's parameters, ny and leading dimension, in which
  * patch old_to_new[i] holds the state of old's patch i -- alpha, C, Q, BV, basis count and the per-patch counters, copied exactly
- * on the device -- and every other patch is empty, as after gpc_sparse_reset.  old_to_new: host, old's P entries, strictly
+ * on the device -- and every other patch is empty, as after gpc_sparse_reset, its state zero.  old_to_new: host, old's P entries, strictly
  * increasing, < P_new (else GPC_EINVAL).  old is untouched; the two objects are destroyed independently. */
 int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_sparse** out);
 /* Rate control: prune every patch's basis IN PLACE by continuing the reference's capacity deletion (src/sparse_gp.hpp:206-223 with

@@ -145,6 +145,39 @@ def test_registration_step_matches_the_restatement(gp, kind):
     m.close()
 
 
+def test_reduce_loop_wraps_over_identical_copies(gp):
+    """rg_reduce_kernel runs at most 8 workgroups per CU and strides over the used points: with more than 8 * CUs * 256 of them its loop
+    takes a second trip.  The scan is k copies of one 10 000-point scan, so the restatement is evaluated on ONE copy: every copy's points
+    get the same owners, n_used is k times the copy's, and the means over k identical copies are the copy's means -- a dropped or doubled
+    stride moves n_used or a mean by at least 1 / k of itself."""
+    import torch
+    capi, ctx = gp
+    xyz, rgb = synth.plane_cloud(10000, seed=1)
+    m = Model(capi, ctx, xyz, rgb, untrained=(3, 7, 20))
+    lik_d, lik_c = m.callbacks()
+    one = _perturbed(xyz)
+    ow, lw = ref.assign(one, m.b, m.grid, m.trained)
+    want = ref.reduce_step(rgb, ow, lw, m.b, lik_d, lik_c)
+    assert want["n_used"] > 0.5 * len(xyz) and np.max(np.abs(want["delta"])) > 0
+    wrap = 8 * torch.cuda.get_device_properties(0).multi_processor_count * 256
+    k = wrap // want["n_used"] + 2
+    assert (k - 1) * want["n_used"] > wrap                                             # the last copy lies wholly in the second trip
+    reg = m.registration()
+    reg.set_cloud(ctx.make_cloud(np.tile(one, (k, 1)), np.tile(rgb, (k, 1))))
+    out = reg.step(capi.default_params_registration(step=0.0))
+    owner, local = reg.assignment()
+    owner, local = owner.reshape(k, len(one)), local.reshape(k, len(one), 3)
+    assert np.array_equal(owner[0], ow) and np.max(np.abs(local[0] - lw)) <= 1e-12 * RES
+    for j in range(1, k):
+        assert np.array_equal(owner[j], owner[0]) and local[j].tobytes() == local[0].tobytes(), j
+    assert out[8] == k * want["n_used"]
+    _close_rel(out[:6], want["delta"], want["gabs"], 1e-8)
+    _close_rel(out[6], want["ls"], abs(want["ls"]), 1e-8)
+    _close_rel(out[7], want["cls"], abs(want["cls"]), 1e-8)
+    reg.close()
+    m.close()
+
+
 def test_registration_step_end_to_end_against_the_oracle(gp, oracle):
     capi, ctx = gp
     xyz, rgb = synth.plane_cloud(10000, seed=1)
