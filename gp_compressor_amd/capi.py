@@ -64,6 +64,15 @@ class GpcError(RuntimeError):
 
 # every symbol include/gpc.h declares, with its prototype (the CPU test-suite checks the library exports all of them)
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
+# the eight probit IRLS entries: ctx, params, irls, [H, cand,] P, off, [n_max, n_total,] x0, x1, y, m, xs0, xs1, res, sz, then the outputs
+_IRLS_HOST = [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _i]
+_IRLS_DEV = _IRLS_HOST[:5] + [_i, _i] + _IRLS_HOST[5:]
+
+
+def _irls_proto(head, outputs, select=False):
+    return (C.c_int, head[:3] + ([_i, _vp] if select else []) + head[3:] + [_vp] * outputs)
+
+
 PROTOTYPES = {
     "gpc_version": (C.c_int, []),
     "gpc_default_params_dense": (None, [C.POINTER(Params)]),
@@ -86,22 +95,14 @@ PROTOTYPES = {
     "gpc_dense_fit_predict_grid_dev": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _i, _i, _vp, _vp, _vp, _i, _d, _i,
                                                  _vp, _vp, _vp]),
     "gpc_default_params_irls": (None, [C.POINTER(IrlsParams)]),
-    "gpc_dense_irls_fit_predict": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
-                                             _d, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_fit_predict_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
-                                                 _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_fit_predict_var": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
-                                                 _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_fit_predict_var_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
-                                                     _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_fit_predict_ev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
-                                                _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_fit_predict_ev_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _i, _vp, _vp, _vp, _i,
-                                                    _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_select": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp,
-                                        _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gpc_dense_irls_select_dev": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(IrlsParams), _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i,
-                                            _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpc_dense_irls_fit_predict": _irls_proto(_IRLS_HOST, 5),
+    "gpc_dense_irls_fit_predict_dev": _irls_proto(_IRLS_DEV, 5),
+    "gpc_dense_irls_fit_predict_var": _irls_proto(_IRLS_HOST, 7),
+    "gpc_dense_irls_fit_predict_var_dev": _irls_proto(_IRLS_DEV, 7),
+    "gpc_dense_irls_fit_predict_ev": _irls_proto(_IRLS_HOST, 8),
+    "gpc_dense_irls_fit_predict_ev_dev": _irls_proto(_IRLS_DEV, 8),
+    "gpc_dense_irls_select": _irls_proto(_IRLS_HOST, 10, select=True),
+    "gpc_dense_irls_select_dev": _irls_proto(_IRLS_DEV, 10, select=True),
     "gpc_noise_eval": (C.c_int, [_vp, _i, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "gpc_sparse_create": (C.c_int, [_vp, C.POINTER(Params), _i, _i, C.POINTER(_vp)]),
     "gpc_sparse_destroy": (None, [_vp]),
@@ -345,72 +346,10 @@ class Context:
         return (f, st, al) if want_alpha else (f, st)
 
     # ---- dense GP + probit functor, Newton / IRLS loop (BASELINE config 5) ---------------------------------------------
-    def dense_irls_fit_predict(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0):
-        """Host-pointer entry (gpc_dense_irls_fit_predict).  y: (N,) labels +-1.  X* point-wise (xs0, xs1) or the sz x sz grid.
-        Returns f_star (P, m), alpha (N,), fhat (N,), iters (P,), status (P,)."""
-        off = np.ascontiguousarray(off, dtype=np.int32)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        if xs0 is not None:
-            xs0 = np.ascontiguousarray(xs0, dtype=np.float64)
-            xs1 = np.ascontiguousarray(xs1, dtype=np.float64)
-            m = xs0.shape[0]
-        else:
-            m = sz * sz
-        P = off.shape[0] - 1
-        f = np.full((P, m), np.nan)
-        al = np.full_like(y, np.nan)
-        fh = np.full_like(y, np.nan)
-        it = np.full(P, -1, dtype=np.int32)
-        st = np.full(P, -1, dtype=np.int32)
-        self._check(self.lib.gpc_dense_irls_fit_predict(self.h, C.byref(params), C.byref(irls), P, _ptr(off), _ptr(x0), _ptr(x1), _ptr(y),
-                                                        m, _ptr(xs0), _ptr(xs1), float(res), int(sz), _ptr(f), _ptr(al), _ptr(fh),
-                                                        _ptr(it), _ptr(st)))
-        return f, al, fh, it, st
-
-    def dense_irls_fit_predict_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
-                                   alpha_out=None, fhat_out=None, iters=None, status=None):
-        self._check(self.lib.gpc_dense_irls_fit_predict_dev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total,
-                                                            _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz),
-                                                            _ptr(f_star), _ptr(alpha_out), _ptr(fhat_out), _ptr(iters), _ptr(status)))
-
-    def dense_irls_fit_predict_var(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_p=True):
-        """Host-pointer entry (gpc_dense_irls_fit_predict_var): dense_irls_fit_predict with the latent predictive variance v* and the
-        occupancy probability p* = Phi(f* / sqrt(s20 + v*)) (noise_model 2 only).  Returns f_star, v_star, p_star (P, m) -- None where
-        not wanted --, alpha (N,), fhat (N,), iters (P,), status (P,)."""
-        off = np.ascontiguousarray(off, dtype=np.int32)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        x1 = np.ascontiguousarray(x1, dtype=np.float64)
-        if xs0 is not None:
-            xs0 = np.ascontiguousarray(xs0, dtype=np.float64)
-            xs1 = np.ascontiguousarray(xs1, dtype=np.float64)
-            m = xs0.shape[0]
-        else:
-            m = sz * sz
-        P = off.shape[0] - 1
-        f = np.full((P, m), np.nan)
-        v = np.full((P, m), np.nan) if want_v else None
-        p = np.full((P, m), np.nan) if want_p else None
-        al = np.full_like(y, np.nan)
-        fh = np.full_like(y, np.nan)
-        it = np.full(P, -1, dtype=np.int32)
-        st = np.full(P, -1, dtype=np.int32)
-        self._check(self.lib.gpc_dense_irls_fit_predict_var(self.h, C.byref(params), C.byref(irls), P, _ptr(off), _ptr(x0), _ptr(x1),
-                                                            _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz), _ptr(f), _ptr(v),
-                                                            _ptr(p), _ptr(al), _ptr(fh), _ptr(it), _ptr(st)))
-        return f, v, p, al, fh, it, st
-
-    def dense_irls_fit_predict_var_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
-                                       v_star=None, p_star=None, alpha_out=None, fhat_out=None, iters=None, status=None):
-        self._check(self.lib.gpc_dense_irls_fit_predict_var_dev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total,
-                                                                _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res),
-                                                                int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
-                                                                _ptr(fhat_out), _ptr(iters), _ptr(status)))
-
-    def _irls_host_args(self, off, x0, x1, y, xs0, xs1, sz, want_v, want_p):
-        """The host arrays of the _ev and select entries: inputs made contiguous, outputs filled with NaN / -1."""
+    def _irls_host_args(self, params, irls, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_p):
+        """What the four host entries share: the leading arguments of the C call (ctx .. sz), the contiguous inputs behind their
+        addresses (the caller keeps them alive over the call), P, and the outputs f, v, p, alpha, fhat, iters, status, log_q filled
+        with NaN / -1 (v, p: None where not wanted)."""
         off = np.ascontiguousarray(off, dtype=np.int32)
         y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
@@ -428,24 +367,53 @@ class Context:
         al, fh = np.full_like(y, np.nan), np.full_like(y, np.nan)
         it, st = np.full(P, -1, dtype=np.int32), np.full(P, -1, dtype=np.int32)
         lq = np.full(P, np.nan)
-        return (off, x0, x1, y, xs0, xs1), (P, m), (f, v, p, al, fh, it, st, lq)
+        keep = (off, x0, x1, y, xs0, xs1)
+        head = [self.h, C.byref(params), C.byref(irls), P, _ptr(off), _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz)]
+        return head, keep, P, (f, v, p, al, fh, it, st, lq)
+
+    def _irls_dev_args(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz):
+        """The leading arguments of the four _dev entries (ctx .. sz)."""
+        return [self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total, _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1),
+                float(res), int(sz)]
+
+    def dense_irls_fit_predict(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0):
+        """Host-pointer entry (gpc_dense_irls_fit_predict).  y: (N,) labels +-1.  X* point-wise (xs0, xs1) or the sz x sz grid.
+        Returns f_star (P, m), alpha (N,), fhat (N,), iters (P,), status (P,)."""
+        head, keep, P, (f, _, _, al, fh, it, st, _) = self._irls_host_args(params, irls, off, x0, x1, y, xs0, xs1, res, sz, False, False)
+        self._check(self.lib.gpc_dense_irls_fit_predict(*head, *map(_ptr, (f, al, fh, it, st))))
+        return f, al, fh, it, st
+
+    def dense_irls_fit_predict_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
+                                   alpha_out=None, fhat_out=None, iters=None, status=None):
+        head = self._irls_dev_args(params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz)
+        self._check(self.lib.gpc_dense_irls_fit_predict_dev(*head, *map(_ptr, (f_star, alpha_out, fhat_out, iters, status))))
+
+    def dense_irls_fit_predict_var(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_p=True):
+        """Host-pointer entry (gpc_dense_irls_fit_predict_var): dense_irls_fit_predict with the latent predictive variance v* and the
+        occupancy probability p* = Phi(f* / sqrt(s20 + v*)) (noise_model 2 only).  Returns f_star, v_star, p_star (P, m) -- None where
+        not wanted --, alpha (N,), fhat (N,), iters (P,), status (P,)."""
+        head, keep, P, (f, v, p, al, fh, it, st, _) = self._irls_host_args(params, irls, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_p)
+        self._check(self.lib.gpc_dense_irls_fit_predict_var(*head, *map(_ptr, (f, v, p, al, fh, it, st))))
+        return f, v, p, al, fh, it, st
+
+    def dense_irls_fit_predict_var_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
+                                       v_star=None, p_star=None, alpha_out=None, fhat_out=None, iters=None, status=None):
+        head = self._irls_dev_args(params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz)
+        self._check(self.lib.gpc_dense_irls_fit_predict_var_dev(*head, *map(_ptr, (f_star, v_star, p_star, alpha_out, fhat_out, iters, status))))
 
     def dense_irls_fit_predict_ev(self, params, irls, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_p=True):
         """Host-pointer entry (gpc_dense_irls_fit_predict_ev): dense_irls_fit_predict_var with the Laplace approximation of the log
         marginal likelihood per patch.  Returns f_star, v_star, p_star (P, m) -- None where not wanted --, alpha (N,), fhat (N,),
         iters (P,), status (P,), log_q (P,)."""
-        (off, x0, x1, y, xs0, xs1), (P, m), (f, v, p, al, fh, it, st, lq) = self._irls_host_args(off, x0, x1, y, xs0, xs1, sz, want_v, want_p)
-        self._check(self.lib.gpc_dense_irls_fit_predict_ev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), _ptr(x0), _ptr(x1),
-                                                           _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz), _ptr(f), _ptr(v),
-                                                           _ptr(p), _ptr(al), _ptr(fh), _ptr(it), _ptr(st), _ptr(lq)))
+        head, keep, P, (f, v, p, al, fh, it, st, lq) = self._irls_host_args(params, irls, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_p)
+        self._check(self.lib.gpc_dense_irls_fit_predict_ev(*head, *map(_ptr, (f, v, p, al, fh, it, st, lq))))
         return f, v, p, al, fh, it, st, lq
 
     def dense_irls_fit_predict_ev_dev(self, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star,
                                       v_star=None, p_star=None, alpha_out=None, fhat_out=None, iters=None, status=None, log_q=None):
-        self._check(self.lib.gpc_dense_irls_fit_predict_ev_dev(self.h, C.byref(params), C.byref(irls), P, _ptr(off), n_max, n_total,
-                                                               _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res),
-                                                               int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
-                                                               _ptr(fhat_out), _ptr(iters), _ptr(status), _ptr(log_q)))
+        head = self._irls_dev_args(params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz)
+        self._check(self.lib.gpc_dense_irls_fit_predict_ev_dev(*head, *map(_ptr, (f_star, v_star, p_star, alpha_out, fhat_out, iters, status,
+                                                                                  log_q))))
 
     @staticmethod
     def hyper_array(candidates):
@@ -459,15 +427,13 @@ class Context:
         """Host-pointer entry (gpc_dense_irls_select): per patch the candidate (sigmaf_sq, l_sq, noise) of largest Laplace evidence and
         its outputs.  Returns f_star, v_star, p_star (P, m) -- None where not wanted --, alpha (N,), fhat (N,), iters (P,), status (P,),
         log_q (P,), best (P,) int32 (-1: no eligible candidate), log_q_all (H, P)."""
-        (off, x0, x1, y, xs0, xs1), (P, m), (f, v, p, al, fh, it, st, lq) = self._irls_host_args(off, x0, x1, y, xs0, xs1, sz, want_v, want_p)
+        head, keep, P, (f, v, p, al, fh, it, st, lq) = self._irls_host_args(params, irls, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_p)
         H = len(candidates)
         best = np.full(P, -2, dtype=np.int32)
         lq_all = np.full((H, P), np.nan)
         arr = self.hyper_array(candidates)
-        self._check(self.lib.gpc_dense_irls_select(self.h, C.byref(params), C.byref(irls), H, C.addressof(arr), P,
-                                                   _ptr(off), _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1), float(res), int(sz),
-                                                   _ptr(f), _ptr(v), _ptr(p), _ptr(al), _ptr(fh), _ptr(lq), _ptr(best), _ptr(lq_all),
-                                                   _ptr(it), _ptr(st)))
+        self._check(self.lib.gpc_dense_irls_select(*head[:3], H, C.addressof(arr), *head[3:], *map(_ptr, (f, v, p, al, fh, lq, best, lq_all,
+                                                                                                       it, st))))
         return f, v, p, al, fh, it, st, lq, best, lq_all
 
     def dense_irls_select_dev(self, params, irls, candidates, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star=None,
@@ -475,11 +441,10 @@ class Context:
                               iters=None, status=None):
         """gpc_dense_irls_select_dev: device pointers throughout, except the candidates (host, read at call time)."""
         arr = self.hyper_array(candidates)
-        self._check(self.lib.gpc_dense_irls_select_dev(self.h, C.byref(params), C.byref(irls), len(candidates), C.addressof(arr), P,
-                                                       _ptr(off), n_max, n_total, _ptr(x0), _ptr(x1), _ptr(y), m, _ptr(xs0), _ptr(xs1),
-                                                       float(res), int(sz), _ptr(f_star), _ptr(v_star), _ptr(p_star), _ptr(alpha_out),
-                                                       _ptr(fhat_out), _ptr(log_q), _ptr(best), _ptr(log_q_all), _ptr(iters),
-                                                       _ptr(status)))
+        head = self._irls_dev_args(params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz)
+        self._check(self.lib.gpc_dense_irls_select_dev(*head[:3], len(candidates), C.addressof(arr), *head[3:],
+                                                       *map(_ptr, (f_star, v_star, p_star, alpha_out, fhat_out, log_q, best, log_q_all, iters,
+                                                                   status))))
 
     def noise_eval(self, noise_model, s20, y, x, sigma_x):
         """gpc_noise_eval: the device's dx_ln / dx2_ln on arrays of (y, x, sigma_x) -> q, r"""
@@ -1121,22 +1086,25 @@ class Mapping:
         on the map's current batch, depth and colour GPs; use_cells: cells a scan saw through (CELL_FREE) do not stop a ray."""
         return self.patches.render(origin, dirs, self.depth, self.rgb, self.cells if use_cells else None, params, want)
 
+    def _occupancy_args(self):
+        """What the occupancy calls share: P, m, sz of the leaf grids and the labelled batch (off, x0, x1, y, n_total, n_max)."""
+        pt = self.patches
+        if pt.res is None:
+            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
+        P, msz = pt.view.P, pt.view.m
+        return P, msz, int(round(msz ** 0.5)), pt.occupancy_batch(self.cells)
+
     def occupancy(self, params, irls=None):
         """The occupancy layer of the map: the probit GP (dense_irls_fit_predict_dev; params: noise_model 1 or 2) trained per leaf on the
         labelled cells, evaluated on the leaf's sz x sz grid.  Returns device tensors f_star (P, m) float64 -- the latent mean, > 0
         towards occupied, 0 for a leaf without an observed cell -- and status (P,) int32."""
         import torch
-        pt = self.patches
-        if pt.res is None:
-            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
-        P, msz = pt.view.P, pt.view.m
-        sz = int(round(msz ** 0.5))
-        off, x0, x1, y, n_total, n_max = pt.occupancy_batch(self.cells)
+        P, msz, sz, (off, x0, x1, y, n_total, n_max) = self._occupancy_args()
         f = torch.zeros((P, msz), dtype=torch.float64, device=self.cells.device)
         st = torch.full((P,), -1, dtype=torch.int32, device=self.cells.device)
         torch.cuda.synchronize(self.cells.device)
         self.ctx.dense_irls_fit_predict_dev(params, irls if irls is not None else default_params_irls(), P, off, n_max, n_total, x0, x1, y,
-                                            msz, None, None, pt.res, sz, f, status=st)
+                                            msz, None, None, self.patches.res, sz, f, status=st)
         self.ctx.synchronize()
         return f, st
 
@@ -1146,17 +1114,12 @@ class Mapping:
         on the labelled cells.  Returns device tensors p, f, v (P, m) float64 and status (P,) int32; a leaf without an observed cell
         has p = 0.5, f = 0, v = sigmaf_sq."""
         import torch
-        pt = self.patches
-        if pt.res is None:
-            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
-        P, msz = pt.view.P, pt.view.m
-        sz = int(round(msz ** 0.5))
-        off, x0, x1, y, n_total, n_max = pt.occupancy_batch(self.cells)
+        P, msz, sz, (off, x0, x1, y, n_total, n_max) = self._occupancy_args()
         p, f, v = (torch.zeros((P, msz), dtype=torch.float64, device=self.cells.device) for _ in range(3))
         st = torch.full((P,), -1, dtype=torch.int32, device=self.cells.device)
         torch.cuda.synchronize(self.cells.device)
         self.ctx.dense_irls_fit_predict_var_dev(params, irls if irls is not None else default_params_irls(), P, off, n_max, n_total, x0, x1,
-                                                y, msz, None, None, pt.res, sz, f, v_star=v, p_star=p, status=st)
+                                                y, msz, None, None, self.patches.res, sz, f, v_star=v, p_star=p, status=st)
         self.ctx.synchronize()
         return p, f, v, st
 
@@ -1167,12 +1130,7 @@ class Mapping:
         converged with a finite evidence; the leaf's p, f, v and log_q are then NaN), log_q (P,) float64 and status (P,) int32; a leaf
         without an observed cell has best = 0, p = 0.5, f = 0, v = candidates[0]'s sigmaf_sq and log_q = 0."""
         import torch
-        pt = self.patches
-        if pt.res is None:
-            raise ValueError("the map's Patches object does not know its res (create it through Context.project_cloud)")
-        P, msz = pt.view.P, pt.view.m
-        sz = int(round(msz ** 0.5))
-        off, x0, x1, y, n_total, n_max = pt.occupancy_batch(self.cells)
+        P, msz, sz, (off, x0, x1, y, n_total, n_max) = self._occupancy_args()
         dev = self.cells.device
         p, f, v = (torch.zeros((P, msz), dtype=torch.float64, device=dev) for _ in range(3))
         lq = torch.zeros((P,), dtype=torch.float64, device=dev)
@@ -1180,7 +1138,8 @@ class Mapping:
         st = torch.full((P,), -1, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         self.ctx.dense_irls_select_dev(params, irls if irls is not None else default_params_irls(), candidates, P, off, n_max, n_total, x0,
-                                       x1, y, msz, None, None, pt.res, sz, f_star=f, v_star=v, p_star=p, log_q=lq, best=best, status=st)
+                                       x1, y, msz, None, None, self.patches.res, sz, f_star=f, v_star=v, p_star=p, log_q=lq, best=best,
+                                       status=st)
         self.ctx.synchronize()
         return p, f, v, best, lq, st
 

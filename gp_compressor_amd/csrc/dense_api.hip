@@ -1,6 +1,6 @@
 // dense_api.hip -- the dense path on device pointers: argument checks, the dispatcher that executes the route of a batch (the rule
-// that chooses the kernels is dense_route, dense_route.h: nothing here decides), the dense and IRLS _dev entries and the host-pointer
-// IRLS entry.  The pipelined host-pointer dense entries are in dense_host.hip.
+// that chooses the kernels is dense_route, dense_route.h: nothing here decides), the two Gaussian _dev entries and the route test hook.
+// The pipelined host-pointer dense entries are in dense_host.hip, the probit / IRLS entries in dense_irls_api.hip.
 #include "dense_internal.h"
 
 int dense_check(gpc_ctx* ctx, const gpc_params* prm, int P, const void* off, int n_max, int n_total,
@@ -216,397 +216,6 @@ int gpc_dense_fit_predict_grid_dev(gpc_ctx* ctx, const gpc_params* params, int P
     a.grid_res = res; a.grid_sz = sz;
     std::lock_guard<std::mutex> lk(ctx->mu);
     return dense_dispatch(ctx, a, dense_site_of(ctx));
-}
-
-// ------------------------------------------------------------------------------------------------ probit / IRLS (config 5)
-
-int gpc_dense_irls_fit_predict_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                                   int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
-                                   const double* xs0, const double* xs1, double res, int sz, double* f_star, double* alpha_out,
-                                   double* fhat_out, int32_t* iters, int32_t* status)
-{
-    const bool grid = (xs0 == nullptr);
-    if (ctx && grid && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-    if (grid) m = sz * sz;
-    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
-    if (rc != GPC_OK) return rc;
-    if (!irls) return gpc_fail(ctx, GPC_EINVAL, "irls is NULL");
-    if (params->noise_model != 1 && params->noise_model != 2)
-        return gpc_fail(ctx, GPC_EINVAL, "the IRLS loop needs a probit noise_model (1 or 2), got %d", params->noise_model);
-    if (irls->max_iter < 1 || !(irls->tol >= 0.0) || !(irls->f_init == irls->f_init))
-        return gpc_fail(ctx, GPC_EINVAL, "irls parameters out of range");
-    if (!(params->noise > 0.0)) return gpc_fail(ctx, GPC_EINVAL, "s20 (params->noise) must be positive");
-    if (!grid && m > 0 && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
-    if (P == 0) return GPC_OK;
-    DenseArgs a = dense_args(params, P, off, n_max < 1 ? 1 : n_max, n_total, x0, x1, y, 1, m, f_star, alpha_out, status);
-    a.prm.want_variance = 0;
-    a.xs0 = xs0; a.xs1 = xs1;
-    a.grid_res = grid ? res : 0.0; a.grid_sz = grid ? sz : 0;
-    IrlsArgs ir{irls->max_iter, irls->tol, irls->f_init, iters, fhat_out};
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const DenseSite site = dense_site_of(ctx);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
-    const DenseRoute route = dense_route(dense_facts(ctx, a, true), dense_switches_read());
-    int grid_b = 0;
-    if ((rc = gpc_ws_reserve(ctx, site, al256(dense_big_ws_bytes(ctx, a, route, &grid_b))))) return rc;
-    if ((rc = dense_irls_launch(ctx, site, a, route, ir, grid_b)) == GPC_OK) ctx->last_dense_kernel = route.name;
-    return rc;
-}
-
-int gpc_dense_irls_fit_predict(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                               const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
-                               double res, int sz, double* f_star, double* alpha_out, double* fhat_out, int32_t* iters,
-                               int32_t* status)
-{
-    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
-    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    const bool grid = (xs0 == nullptr);
-    if (grid) {
-        if (sz < 0 || sz > 1024) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-        m = sz * sz;
-    }
-    int n_max = 0, n_total = 0;
-    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
-    if (rc != GPC_OK) return rc;
-    rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
-    if (rc != GPC_OK) return rc;
-    if (P == 0) return GPC_OK;
-    if (!grid && m && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t N = (size_t)n_total, Pz = (size_t)P, Pm = Pz * (size_t)m;
-    GpcStaging st(ctx, "gpc_dense_irls_fit_predict");
-    const int32_t* d_off = st.up(off, Pz + 1);
-    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
-    const double *d_xs0 = grid ? nullptr : st.up(xs0, (size_t)m), *d_xs1 = grid ? nullptr : st.up(xs1, (size_t)m);
-    double *d_f = st.out<double>(Pm), *d_al = st.out<double>(N), *d_fh = st.out<double>(N);
-    int32_t *d_it = st.out<int32_t>(Pz), *d_st = st.out<int32_t>(Pz);
-    if (st.ok())
-        st.rc = gpc_dense_irls_fit_predict_dev(ctx, params, irls, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res, sz, d_f, d_al,
-                                               d_fh, d_it, d_st);
-    st.down(f_star, d_f, Pm);
-    st.down(alpha_out, d_al, N);
-    st.down(fhat_out, d_fh, N);
-    st.down(iters, d_it, Pz);
-    st.down(status, d_st, Pz);
-    return st.finish();
-}
-
-// ---- ... with the latent predictive variance and the occupancy probability, and with the Laplace evidence (definitions: include/gpc.h) ----
-
-// the argument rules of the _var_dev and _ev_dev entries, past dense_check
-static int irls_var_check(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, bool grid, const double* xs1, int m,
-                          const double* p_star, const double* log_q)
-{
-    if (!irls) return gpc_fail(ctx, GPC_EINVAL, "irls is NULL");
-    if (params->noise_model != 1 && params->noise_model != 2)
-        return gpc_fail(ctx, GPC_EINVAL, "the IRLS loop needs a probit noise_model (1 or 2), got %d", params->noise_model);
-    if (p_star && params->noise_model != 2)
-        return gpc_fail(ctx, GPC_EINVAL, "p_star needs noise_model 2: the \"Phi\" of model 1 is not a probability");
-    if (log_q && params->noise_model != 2)
-        return gpc_fail(ctx, GPC_EINVAL, "log_q needs noise_model 2: the \"Phi\" of model 1 is not a probability");
-    if (irls->max_iter < 1 || !(irls->tol >= 0.0) || !(irls->f_init == irls->f_init))
-        return gpc_fail(ctx, GPC_EINVAL, "irls parameters out of range");
-    if (!(params->noise > 0.0)) return gpc_fail(ctx, GPC_EINVAL, "s20 (params->noise) must be positive");
-    if (!grid && m > 0 && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
-    return GPC_OK;
-}
-
-// The workspace of a fit with the export on: a factor slot per patch | a (when the caller does not take it) | s of the last solve | the
-// variance kernel's per-wave V scratch | the grid as points | the status (when the caller does not take it) | with the evidence wanted:
-// fhat (when the caller does not take it)
-struct IrlsVarWs {
-    size_t slot, o_al, o_s, o_scr, o_xs, o_st, o_fh, bytes;
-};
-static IrlsVarWs irls_var_ws(const gpc_ctx* ctx, int P, int n_max, int n_total, int m, bool evidence)
-{
-    const int ntw = (n_max + 15) / 16;
-    IrlsVarWs w;
-    w.slot = big_slot_doubles(ntw);
-    w.o_al = al256(sizeof(double) * w.slot * (size_t)P);
-    w.o_s = w.o_al + al256(sizeof(double) * (size_t)n_total);
-    w.o_scr = w.o_s + al256(sizeof(double) * (size_t)n_total);
-    w.o_xs = w.o_scr + al256(sizeof(double) * dense_variance_big_scratch_doubles(ctx, ntw));
-    w.o_st = w.o_xs + al256(sizeof(double) * 2 * (size_t)m);
-    w.o_fh = w.o_st + al256(sizeof(int32_t) * (size_t)P);
-    w.bytes = w.o_fh + (evidence ? al256(sizeof(double) * (size_t)n_total) : 0);
-    return w;
-}
-
-// One fit with the export on at `site`, the variance kernel and (log_q != nullptr) the evidence read-out behind it.  Arguments checked,
-// P > 0, n_max >= 1, grid: m = sz sz; caller holds ctx->mu.
-static int irls_var_run(gpc_ctx* ctx, const DenseSite& site, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                        int n_max, int n_total, const double* x0, const double* x1, const double* y, int m, const double* xs0,
-                        const double* xs1, double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
-                        double* fhat_out, int32_t* iters, int32_t* status, double* log_q)
-{
-    const bool grid = (xs0 == nullptr);
-    // nothing for the variance kernel to write (the evidence alone, or with the mean): the fit predicts f* itself, as in the plain entry
-    const bool var = (v_star || p_star) && m > 0;
-    int rc;
-    if (int rcp = gpc_debug_poison_lds(ctx, site)) return rcp;
-    const DenseFacts facts{P, n_max, n_total, 1, m, true, true, alpha_out != nullptr, ctx->num_cus, true};
-    const DenseRoute route = dense_route(facts, dense_switches_read());
-    const int ntw = (n_max + 15) / 16;
-    const IrlsVarWs w = irls_var_ws(ctx, P, n_max, n_total, m, log_q != nullptr);
-    if ((rc = gpc_ws_reserve(ctx, site, w.bytes))) return rc;
-    char* ws = dense_ws(ctx, site);
-    double* d_al = alpha_out ? alpha_out : reinterpret_cast<double*>(ws + w.o_al);
-    double* d_s = reinterpret_cast<double*>(ws + w.o_s);
-    double* d_xs = reinterpret_cast<double*>(ws + w.o_xs);
-    int32_t* d_st = status ? status : reinterpret_cast<int32_t*>(ws + w.o_st);
-    double* d_fh = (fhat_out || !log_q) ? fhat_out : reinterpret_cast<double*>(ws + w.o_fh);
-    if (var && grid && (rc = dense_grid_points_launch(ctx, site, res, sz, d_xs, d_xs + m))) return rc;
-    // with the variance the fit predicts nothing: the variance kernel forms the mean from the K* tiles it evaluates anyway
-    DenseArgs a = dense_args(params, P, off, n_max, n_total, x0, x1, y, 1, var ? 0 : m, f_star, d_al, d_st);
-    a.prm.want_variance = 0;
-    if (var) {
-        a.xs0 = grid ? d_xs : xs0; a.xs1 = grid ? d_xs + m : xs1;
-    } else {
-        a.xs0 = xs0; a.xs1 = xs1;
-        a.grid_res = grid ? res : 0.0; a.grid_sz = grid ? sz : 0;
-    }
-    const IrlsArgs ir{irls->max_iter, irls->tol, irls->f_init, iters, d_fh, d_s};
-    const int cap = ctx->num_cus * route.per_cu, grid_b = P < cap ? P : cap;
-    if ((rc = dense_irls_launch(ctx, site, a, route, ir, grid_b))) return rc;
-    if (var) {
-        a.m = m;
-        if ((rc = dense_variance_big_scaled_launch(ctx, site, a, ntw, reinterpret_cast<const double*>(ws), w.slot, d_al, d_s,
-                                                   reinterpret_cast<double*>(ws + w.o_scr), v_star, p_star)))
-            return rc;
-    }
-    if (log_q && (rc = dense_evidence_launch(ctx, site, a, ntw, reinterpret_cast<const double*>(ws), w.slot, d_al, d_fh, log_q))) return rc;
-    ctx->last_dense_kernel = route.name;
-    return GPC_OK;
-}
-
-int gpc_dense_irls_fit_predict_var_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                                       int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
-                                       const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
-                                       double* p_star, double* alpha_out, double* fhat_out, int32_t* iters, int32_t* status)
-{
-    const bool grid = (xs0 == nullptr);
-    // neither asked for, or nothing to predict: the plain entry, same launches, same bits
-    if ((!v_star && !p_star) || (grid ? sz == 0 : m == 0))
-        return gpc_dense_irls_fit_predict_dev(ctx, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star, alpha_out,
-                                              fhat_out, iters, status);
-    if (ctx && grid && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-    if (grid) m = sz * sz;
-    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
-    if (rc != GPC_OK) return rc;
-    if ((rc = irls_var_check(ctx, params, irls, grid, xs1, m, p_star, nullptr))) return rc;
-    if (P == 0) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    return irls_var_run(ctx, dense_site_of(ctx), params, irls, P, off, n_max < 1 ? 1 : n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz,
-                        f_star, v_star, p_star, alpha_out, fhat_out, iters, status, nullptr);
-}
-
-int gpc_dense_irls_fit_predict_ev_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                                      int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
-                                      const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
-                                      double* p_star, double* alpha_out, double* fhat_out, int32_t* iters, int32_t* status, double* log_q)
-{
-    if (!log_q)
-        return gpc_dense_irls_fit_predict_var_dev(ctx, params, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, f_star, v_star,
-                                                  p_star, alpha_out, fhat_out, iters, status);
-    const bool grid = (xs0 == nullptr);
-    if (ctx && grid && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-    if (grid) m = sz * sz;
-    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
-    if (rc != GPC_OK) return rc;
-    if ((rc = irls_var_check(ctx, params, irls, grid, xs1, m, p_star, log_q))) return rc;
-    if (P == 0) return GPC_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    return irls_var_run(ctx, dense_site_of(ctx), params, irls, P, off, n_max < 1 ? 1 : n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz,
-                        f_star, v_star, p_star, alpha_out, fhat_out, iters, status, log_q);
-}
-
-// ---- selection among candidate hyper-parameters by that evidence ----
-
-int gpc_dense_irls_select_dev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int H, const gpc_hyper* cand, int P,
-                              const int32_t* off, int n_max, int n_total, const double* x0, const double* x1, const double* y, int m,
-                              const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star,
-                              double* p_star, double* alpha_out, double* fhat_out, double* log_q, int32_t* best, double* log_q_all,
-                              int32_t* iters, int32_t* status)
-{
-    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
-    if (!params) return gpc_fail(ctx, GPC_EINVAL, "params is NULL");
-    if (H < 1 || !cand) return gpc_fail(ctx, GPC_EINVAL, "select needs H >= 1 candidates");
-    if (params->noise_model != 2) return gpc_fail(ctx, GPC_EINVAL, "select needs noise_model 2, got %d", params->noise_model);
-    for (int h = 0; h < H; ++h) {
-        const double v[3] = {cand[h].sigmaf_sq, cand[h].l_sq, cand[h].noise};
-        for (double x : v)
-            if (!(x > 0.0) || !(x - x == 0.0)) return gpc_fail(ctx, GPC_EINVAL, "candidate %d has a non-positive or non-finite field", h);
-    }
-    const bool grid = (xs0 == nullptr);
-    if (grid && (sz < 0 || sz > 1024)) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-    if (grid) m = sz * sz;
-    // (f_star may be NULL here: the candidates write into temporaries)
-    int rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, 0, nullptr);
-    if (rc != GPC_OK) return rc;
-    if (m < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if ((rc = irls_var_check(ctx, params, irls, grid, xs1, m, nullptr, nullptr))) return rc;
-    if (P == 0) return GPC_OK;
-    if (n_max < 1) n_max = 1;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    // the workspace: the temporaries of one candidate and the state of the keep-best step in front, the fit's region behind them
-    const size_t Pm = al256(sizeof(double) * (size_t)P * (size_t)m), N8 = al256(sizeof(double) * (size_t)n_total),
-                 P8 = al256(sizeof(double) * (size_t)P), P4 = al256(sizeof(int32_t) * (size_t)P);
-    const size_t tmp = 3 * Pm + 2 * N8 + 2 * P8 + 3 * P4;
-    const DenseSite whole = dense_site_of(ctx);
-    const DenseSite site{whole.stream, whole.ws_off + tmp, 0};
-    if ((rc = gpc_ws_reserve(ctx, whole, tmp + irls_var_ws(ctx, P, n_max, n_total, m, true).bytes))) return rc;
-    char* t = dense_ws(ctx, whole);
-    SelectRows c;
-    c.f = reinterpret_cast<double*>(t);
-    c.v = v_star ? reinterpret_cast<double*>(t + Pm) : nullptr;
-    c.p = p_star ? reinterpret_cast<double*>(t + 2 * Pm) : nullptr;
-    c.alpha = reinterpret_cast<double*>(t + 3 * Pm);
-    c.fhat = reinterpret_cast<double*>(t + 3 * Pm + N8);
-    c.log_q = reinterpret_cast<double*>(t + 3 * Pm + 2 * N8);
-    double* cur_lq = reinterpret_cast<double*>(t + 3 * Pm + 2 * N8 + P8);
-    c.iters = reinterpret_cast<int32_t*>(t + 3 * Pm + 2 * N8 + 2 * P8);
-    c.status = c.iters + P4 / sizeof(int32_t);
-    int32_t* cur_best = c.status + P4 / sizeof(int32_t);
-    const SelectRows out{f_star, v_star, p_star, alpha_out, fhat_out, log_q, iters, status};
-    for (int h = 0; h < H; ++h) {
-        gpc_params prm = *params;
-        prm.sigmaf_sq = cand[h].sigmaf_sq; prm.l_sq = cand[h].l_sq; prm.noise = cand[h].noise;
-        if ((rc = irls_var_run(ctx, site, &prm, irls, P, off, n_max, n_total, x0, x1, y, m, xs0, xs1, res, sz, c.f, c.v, c.p, c.alpha,
-                               c.fhat, c.iters, c.status, c.log_q)))
-            return rc;
-        if ((rc = dense_select_keep_launch(ctx, whole, h, P, m, off, c, out, best, log_q_all ? log_q_all + (size_t)h * P : nullptr,
-                                           cur_best, cur_lq)))
-            return rc;
-    }
-    return GPC_OK;
-}
-
-int gpc_dense_irls_fit_predict_var(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                                   const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
-                                   double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
-                                   double* fhat_out, int32_t* iters, int32_t* status)
-{
-    if (!v_star && !p_star)
-        return gpc_dense_irls_fit_predict(ctx, params, irls, P, off, x0, x1, y, m, xs0, xs1, res, sz, f_star, alpha_out, fhat_out, iters, status);
-    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
-    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    const bool grid = (xs0 == nullptr);
-    if (grid) {
-        if (sz < 0 || sz > 1024) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-        m = sz * sz;
-    }
-    int n_max = 0, n_total = 0;
-    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
-    if (rc != GPC_OK) return rc;
-    rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, m, f_star);
-    if (rc != GPC_OK) return rc;
-    if (!irls) return gpc_fail(ctx, GPC_EINVAL, "irls is NULL");
-    if (p_star && params->noise_model == 1)
-        return gpc_fail(ctx, GPC_EINVAL, "p_star needs noise_model 2: the \"Phi\" of model 1 is not a probability");
-    if (P == 0) return GPC_OK;
-    if (!grid && m && !xs1) return gpc_fail(ctx, GPC_EINVAL, "xs1 is NULL");
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t N = (size_t)n_total, Pz = (size_t)P, Pm = Pz * (size_t)m;
-    GpcStaging st(ctx, "gpc_dense_irls_fit_predict_var");
-    const int32_t* d_off = st.up(off, Pz + 1);
-    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
-    const double *d_xs0 = grid ? nullptr : st.up(xs0, (size_t)m), *d_xs1 = grid ? nullptr : st.up(xs1, (size_t)m);
-    double *d_f = st.out<double>(Pm), *d_al = st.out<double>(N), *d_fh = st.out<double>(N);
-    double *d_v = v_star ? st.out<double>(Pm) : nullptr, *d_p = p_star ? st.out<double>(Pm) : nullptr;
-    int32_t *d_it = st.out<int32_t>(Pz), *d_st = st.out<int32_t>(Pz);
-    if (st.ok())
-        st.rc = gpc_dense_irls_fit_predict_var_dev(ctx, params, irls, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res, sz, d_f,
-                                                   d_v, d_p, d_al, d_fh, d_it, d_st);
-    st.down(f_star, d_f, Pm);
-    if (v_star) st.down(v_star, d_v, Pm);
-    if (p_star) st.down(p_star, d_p, Pm);
-    st.down(alpha_out, d_al, N);
-    st.down(fhat_out, d_fh, N);
-    st.down(iters, d_it, Pz);
-    st.down(status, d_st, Pz);
-    return st.finish();
-}
-
-// The host-pointer forms of the _ev and select entries: one staging list (H == 0: the _ev entry, no best / log_q_all).
-static int irls_select_host(gpc_ctx* ctx, const char* entry, const gpc_params* params, const gpc_irls_params* irls, int H,
-                            const gpc_hyper* cand, int P, const int32_t* off, const double* x0, const double* x1, const double* y, int m,
-                            const double* xs0, const double* xs1, double res, int sz, double* f_star, double* v_star, double* p_star,
-                            double* alpha_out, double* fhat_out, double* log_q, int32_t* best, double* log_q_all, int32_t* iters,
-                            int32_t* status)
-{
-    if (!ctx || ctx->dead.load()) return GPC_EINVAL;
-    if (P < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
-    const bool select = H != 0, grid = (xs0 == nullptr);
-    if (select && (H < 1 || !cand)) return gpc_fail(ctx, GPC_EINVAL, "select needs H >= 1 candidates");
-    if (grid) {
-        if (sz < 0 || sz > 1024) return gpc_fail(ctx, GPC_EINVAL, "sz out of range");
-        m = sz * sz;
-    }
-    int n_max = 0, n_total = 0;
-    int rc = gpc_check_host_off(ctx, P, off, &n_max, &n_total);
-    if (rc != GPC_OK) return rc;
-    rc = dense_check(ctx, params, P, off, n_max, n_total, x0, x1, y, 1, select ? 0 : m, f_star);
-    if (rc != GPC_OK) return rc;
-    if (m < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
-    if ((rc = irls_var_check(ctx, params, irls, grid, xs1, m, p_star, select ? nullptr : log_q))) return rc;
-    if (select && params->noise_model != 2) return gpc_fail(ctx, GPC_EINVAL, "select needs noise_model 2, got %d", params->noise_model);
-    if (P == 0 && !select) return GPC_OK;
-    GPC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t N = (size_t)n_total, Pz = (size_t)P, Pm = Pz * (size_t)m;
-    GpcStaging st(ctx, entry);
-    const int32_t* d_off = st.up(off, Pz + 1);
-    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N);
-    const double *d_xs0 = grid ? nullptr : st.up(xs0, (size_t)m), *d_xs1 = grid ? nullptr : st.up(xs1, (size_t)m);
-    double *d_f = st.out<double>(Pm), *d_al = st.out<double>(N), *d_fh = st.out<double>(N), *d_lq = st.out<double>(Pz);
-    double *d_v = v_star ? st.out<double>(Pm) : nullptr, *d_p = p_star ? st.out<double>(Pm) : nullptr;
-    int32_t *d_it = st.out<int32_t>(Pz), *d_st = st.out<int32_t>(Pz);
-    int32_t* d_best = select ? st.out<int32_t>(Pz) : nullptr;
-    double* d_all = select && log_q_all ? st.out<double>((size_t)H * Pz) : nullptr;
-    if (st.ok())
-        st.rc = select ? gpc_dense_irls_select_dev(ctx, params, irls, H, cand, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res,
-                                                   sz, d_f, d_v, d_p, d_al, d_fh, d_lq, d_best, d_all, d_it, d_st)
-                       : gpc_dense_irls_fit_predict_ev_dev(ctx, params, irls, P, d_off, n_max, n_total, d_x0, d_x1, d_y, m, d_xs0, d_xs1, res,
-                                                           sz, d_f, d_v, d_p, d_al, d_fh, d_it, d_st, d_lq);
-    st.down(f_star, d_f, Pm);
-    if (v_star) st.down(v_star, d_v, Pm);
-    if (p_star) st.down(p_star, d_p, Pm);
-    st.down(alpha_out, d_al, N);
-    st.down(fhat_out, d_fh, N);
-    st.down(log_q, d_lq, Pz);
-    if (select) st.down(best, d_best, Pz);
-    if (d_all) st.down(log_q_all, d_all, (size_t)H * Pz);
-    st.down(iters, d_it, Pz);
-    st.down(status, d_st, Pz);
-    return st.finish();
-}
-
-int gpc_dense_irls_fit_predict_ev(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int P, const int32_t* off,
-                                  const double* x0, const double* x1, const double* y, int m, const double* xs0, const double* xs1,
-                                  double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
-                                  double* fhat_out, int32_t* iters, int32_t* status, double* log_q)
-{
-    if (!log_q)
-        return gpc_dense_irls_fit_predict_var(ctx, params, irls, P, off, x0, x1, y, m, xs0, xs1, res, sz, f_star, v_star, p_star, alpha_out,
-                                              fhat_out, iters, status);
-    return irls_select_host(ctx, "gpc_dense_irls_fit_predict_ev", params, irls, 0, nullptr, P, off, x0, x1, y, m, xs0, xs1, res, sz, f_star,
-                            v_star, p_star, alpha_out, fhat_out, log_q, nullptr, nullptr, iters, status);
-}
-
-int gpc_dense_irls_select(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int H, const gpc_hyper* cand, int P,
-                          const int32_t* off, const double* x0, const double* x1, const double* y, int m, const double* xs0,
-                          const double* xs1, double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
-                          double* fhat_out, double* log_q, int32_t* best, double* log_q_all, int32_t* iters, int32_t* status)
-{
-    if (ctx && !ctx->dead.load() && H == 0) return gpc_fail(ctx, GPC_EINVAL, "select needs H >= 1 candidates");
-    return irls_select_host(ctx, "gpc_dense_irls_select", params, irls, H, cand, P, off, x0, x1, y, m, xs0, xs1, res, sz, f_star, v_star,
-                            p_star, alpha_out, fhat_out, log_q, best, log_q_all, iters, status);
 }
 
 // host-only test hook: dense_route for the given facts under the switches of the environment (no HIP call: works without a GPU)

@@ -48,7 +48,8 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, const DenseSite& site, size_t byt
 // GPC_POISON_LDS for a dense call: launched on the site's stream, and only the site's region of the workspace is filled
 int gpc_debug_poison_lds(gpc_ctx* ctx, const DenseSite& site);
 
-// ---- dispatcher (dense_api.hip), also used by the host-pointer pipeline (dense_host.hip) ----------------------
+// ---- dispatcher (dense_api.hip), also used by the host-pointer pipeline (dense_host.hip); the argument check and dense_args also by
+// ---- the probit / IRLS entries (dense_irls_api.hip) ------------------------------------------------------------
 
 int dense_check(gpc_ctx* ctx, const gpc_params* prm, int P, const void* off, int n_max, int n_total,
                 const void* x0, const void* x1, const void* y, int ny, int m, const void* f_star);

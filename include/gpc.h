@@ -158,7 +158,24 @@ int gpc_dense_fit_predict_grid_dev(gpc_ctx* ctx, const gpc_params* params, int P
  * training points), iters [P] (solves performed) and status [P] may be NULL.  Status GPC_STATUS_NOT_CONVERGED: the step cap ended
  * the loop (outputs are the last iterate).  Status GPC_STATUS_NAN: a weight W_i was not
  * finite and positive (with noise_model 1 this is the normal outcome when a step crosses f = 0); outputs of the patch are NaN.
- * Definition and CPU restatement: oracle/gpc_oracle.c (orc_dense_irls_fit). */
+ * Definition and CPU restatement: oracle/gpc_oracle.c (orc_dense_irls_fit).
+ *
+ * Shared arguments and rules of the eight probit entries (gpc_dense_irls_fit_predict, its _var and _ev forms and gpc_dense_irls_select,
+ * each with its _dev twin).  All take ctx, params, irls, P, off, x0, x1, y, m, xs0, xs1, res, sz as described above; the _dev forms
+ * also n_max (the largest patch) and n_total = off[P], which the host forms read from off.  Every entry checks the same rules in this
+ * order, whichever outputs it was asked for, and the first one broken decides the code and the text of gpc_last_error:
+ *   1. ctx NULL or dead                                                                              GPC_EINVAL (no text)
+ *   2. params NULL
+ *   3. select only: H < 1 or cand NULL; noise_model != 2; a candidate with a non-positive or non-finite field
+ *   4. grid form (xs0 == NULL): sz outside 0 .. 1024
+ *   5. host forms only: P < 0; off NULL with P > 0; off[0] != 0 or off decreasing
+ *   6. the dense rules: a negative size; off, x0, x1 or y NULL where there is something to read; f_star NULL with P > 0 and m > 0
+ *      (not under select, whose every output may be NULL); n_max > GPC_MAX_POINTS: GPC_ERANGE; l_sq <= 0, sigmaf_sq < 0 or noise < 0
+ *   7. irls NULL; noise_model not 1 or 2; p_star or log_q with noise_model != 2 (the "Phi" of model 1 is not a probability);
+ *      max_iter < 1, tol < 0 or NaN, f_init NaN; noise <= 0; point-wise form: xs1 NULL with m > 0
+ *   8. P == 0: GPC_OK, nothing is launched and nothing written
+ * Everything but the one GPC_ERANGE is GPC_EINVAL, and no output is written on an error.  The rules run in full before rule 8 in both
+ * forms: an empty batch with invalid probit parameters is GPC_EINVAL from a host entry as from its _dev twin. */
 typedef struct gpc_irls_params {
     int32_t max_iter;   /* >= 1 */
     int32_t reserved;
@@ -187,8 +204,7 @@ int gpc_dense_irls_fit_predict_dev(gpc_ctx* ctx, const gpc_params* params, const
  * Per patch: an empty patch gives f* = 0, v* = sigmaf_sq, p* = 0.5; status GPC_STATUS_NAN (and NOT_SPD) gives NaN in f*, v*, p*;
  * GPC_STATUS_NOT_CONVERGED gives the outputs of the last iterate, not NaN.
  * v_star and p_star are [P][m]; each may be NULL, and with both NULL (or nothing to predict) the call IS gpc_dense_irls_fit_predict[_dev]:
- * it forwards to it and gives the same bits.  p_star != NULL with noise_model == 1: GPC_EINVAL (the "Phi" of model 1 as written is
- * not a probability); v_star works with both models.  Other errors as in gpc_dense_irls_fit_predict[_dev].
+ * the same launches, the same bits.  p_star needs noise_model 2 (rule 7 above); v_star works with both models.
  * With xs0 == NULL the sz x sz grid of load_compressed is used (res, sz; m = sz*sz, cell p = y*sz + x).  The variance kernel has no
  * separable form, so the library then materialises the grid as m points in its workspace and evaluates point-wise throughout: f_star may
  * differ from the grid form of gpc_dense_irls_fit_predict[_dev] by O(1 ulp) per kernel value.
@@ -216,10 +232,9 @@ int gpc_dense_irls_fit_predict_var_dev(gpc_ctx* ctx, const gpc_params* params, c
  * the three sums has a fixed order (point j goes to lane j mod 64 of one wave, then a fixed shuffle tree): two calls give the same bits.
  * Per patch: an empty patch gives log_q = 0; status GPC_STATUS_NAN (and NOT_SPD) gives NaN; GPC_STATUS_NOT_CONVERGED gives the value at
  * the last iterate; an ef that underflows gives -inf, a valid output.
- * log_q is [P].  log_q == NULL: the call forwards to gpc_dense_irls_fit_predict_var[_dev] and gives the same bits.  log_q != NULL: every
- * other output is bit for bit what that entry gives; noise_model == 1 is GPC_EINVAL (its "Phi" is not a probability).  v_star and p_star
- * may both be NULL and m may be 0: the fit still runs with the factor export on (f_star is then the plain entry's), and the variance
- * kernel is skipped.  Other errors as in gpc_dense_irls_fit_predict_var[_dev].
+ * log_q is [P].  log_q == NULL: the call IS gpc_dense_irls_fit_predict_var[_dev], the same launches and the same bits.  log_q != NULL:
+ * every other output is bit for bit what that entry gives; noise_model 2 only (rule 7 above).  v_star and p_star may both be NULL and m
+ * may be 0: the fit still runs with the factor export on (f_star is then the plain entry's), and the variance kernel is skipped.
  * Workspace: that of gpc_dense_irls_fit_predict_var[_dev] plus fhat (n_total doubles) when fhat_out == NULL --
  *     bytes = 8 (slot(ntw) P + 3 n_total + 2048 CUs ntw + 2 m) + 4 P
  * (each term rounded up to 256 bytes).  A refusal returns GPC_ENOMEM; the batch is not chunked.  The read-out re-runs nothing: it reads
@@ -249,8 +264,7 @@ int gpc_dense_irls_fit_predict_ev_dev(gpc_ctx* ctx, const gpc_params* params, co
  * temporaries --
  *     bytes = ev_bytes + 8 (3 P m + 2 n_total + 2 P) + 4 (3 P)
  * (each term rounded up to 256 bytes); not chunked over patches, a refusal returns GPC_ENOMEM.  The _dev form never synchronises.
- * Errors: GPC_EINVAL for H < 1, cand == NULL, a candidate with a non-positive or non-finite field, noise_model != 2; otherwise those of
- * gpc_dense_irls_fit_predict_ev[_dev]. */
+ * Errors: rule 3 above, then the shared rules. */
 typedef struct gpc_hyper {
     double sigmaf_sq, l_sq, noise;
 } gpc_hyper;
