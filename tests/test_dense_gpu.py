@@ -4,6 +4,7 @@ Oracle: oracle/gpc_oracle.c (and the NumPy/LAPACK golden fixtures).  Stated tole
 oracle are two fp64 evaluations of the same well-conditioned system (kappa(K + 2 sn^2 I) <= 1 + n sf^2 / (2 sn^2),
 ~200 at n = 256, ~800 at n = 1024) that differ in summation order, FMA contraction and exp() (<= 2 ulp):
     |f*_gpu - f*_cpu| <= 1e-9 * max|f*|      |alpha_gpu - alpha_cpu| <= 1e-8 * max|alpha|     |V*_gpu - V*_cpu| <= 1e-11
+What these round figures do and do not catch, and the measured gate that f* and alpha of every route are held to, is in test_dense_accuracy_gpu.py.
 """
 import os
 
