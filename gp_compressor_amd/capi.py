@@ -129,6 +129,10 @@ PROTOTYPES = {
     "gpc_sparse_prune_dev": (C.c_int, [_vp, _i, _vp, _d, _vp, _vp, _vp, _vp]),
     "gpc_sparse_prune_rd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _d, _vp] + [_vp] * 7),
     "gpc_sparse_prune_rd_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _d, _vp] + [_vp] * 7),
+    "gpc_sparse_quantize_rd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp] + [_vp] * 8),
+    "gpc_sparse_quantize_rd_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _d, _vp] + [_vp] * 8),
+    "gpc_sparse_dequantize": (C.c_int, [_vp] * 6),
+    "gpc_sparse_dequantize_dev": (C.c_int, [_vp] * 6),
     "gpc_reproject": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_reproject_dev": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_project_cloud": (C.c_int, [_vp, _vp, _i, _d, _i, C.POINTER(_vp)]),
@@ -174,6 +178,7 @@ PROTOTYPES = {
     "gpc_unpermute_fstar_dev": (C.c_int, [_vp, _i, _vp, _vp]),
     "gpc_test_exp_host": (None, [_vp, _vp, _i]),
     "gpc_test_exp_small_host": (None, [_vp, _vp, _i]),
+    "gpc_test_quantize_host": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp]),
     "gpc_test_par_memcpy": (None, [_vp, _vp, C.c_size_t]),
     "gpc_test_dense_route": (C.c_int, [_i] * 11 + [_vp, _i, _vp]),
 }
@@ -905,6 +910,57 @@ class Sparse:
                                                          _ptr(removed), _ptr(order), _ptr(scores), _ptr(mse), _ptr(mse0), _ptr(mse_next),
                                                          _ptr(status)))
 
+    def quantize_rd(self, off, x0, x1, y, bits_min=1, bits_max=16, max_mse=float("inf"), max_mse_p=None, want_curve=False):
+        """gpc_sparse_quantize_rd (host arrays): per patch the smallest width w in bits_min .. bits_max at which the state, with BV and
+        alpha rounded to w-bit codes over their float range, keeps its mean square error on the patch's own points within max_mse (or
+        its entry of max_mse_p, (P,)).  The object is not modified.  Returns bits (P,) int32 (0: no width accepted, or an escaped patch
+        -- no vectors, no points or a non-finite value), q_alpha (P, ny, ld) and q_bv (P, ld, 2) uint16 (zero where nothing was
+        written), range (P, ny + 2, 2) float32 (NaN where not written), mse0 (P,), mse_q (P,); with want_curve also curve (P, 16), entry
+        w - 1 the error at width w, NaN where not evaluated."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N = int(off[-1]) if len(off) else 0
+        assert off.shape[0] == self.P + 1 and x0.shape[0] == N and x1.shape[0] == N and y.size == self.ny * N
+        bp = None if max_mse_p is None else np.ascontiguousarray(max_mse_p, dtype=np.float64)
+        assert bp is None or bp.shape == (self.P,)
+        ld = self.ld()
+        bits = np.zeros(self.P, dtype=np.int32)
+        qa = np.zeros((self.P, self.ny, ld), dtype=np.uint16)
+        qb = np.zeros((self.P, ld, 2), dtype=np.uint16)
+        rng = np.full((self.P, self.ny + 2, 2), np.nan, dtype=np.float32)
+        mse0, mseq = np.full(self.P, np.nan), np.full(self.P, np.nan)
+        curve = np.full((self.P, 16), np.nan) if want_curve else None
+        self.ctx._check(self.lib.gpc_sparse_quantize_rd(self.h, _ptr(off), _ptr(x0), _ptr(x1), _ptr(y), int(bits_min), int(bits_max),
+                                                        float(max_mse), _ptr(bp), _ptr(bits), _ptr(qa), _ptr(qb), _ptr(rng), _ptr(mse0),
+                                                        _ptr(mseq), _ptr(curve), None))
+        return (bits, qa, qb, rng, mse0, mseq, curve) if want_curve else (bits, qa, qb, rng, mse0, mseq)
+
+    def quantize_rd_dev(self, off, n_total, x0, x1, y, bits_min=1, bits_max=16, max_mse=float("inf"), max_mse_p=None, bits=None,
+                        q_alpha=None, q_bv=None, range=None, mse0=None, mse_q=None, curve=None, status=None):
+        """gpc_sparse_quantize_rd_dev: device buffers (each output may be None), enqueued on the context's stream"""
+        self.ctx._check(self.lib.gpc_sparse_quantize_rd_dev(self.h, _ptr(off), int(n_total), _ptr(x0), _ptr(x1), _ptr(y), int(bits_min),
+                                                            int(bits_max), float(max_mse), _ptr(max_mse_p), _ptr(bits), _ptr(q_alpha),
+                                                            _ptr(q_bv), _ptr(range), _ptr(mse0), _ptr(mse_q), _ptr(curve), _ptr(status)))
+
+    def dequantize(self, bv_count, bits, q_alpha, q_bv, range):
+        """gpc_sparse_dequantize (host arrays, the layouts quantize_rd returns): every patch with bits in 1..16 gets the dequantised
+        alpha and BV, the count bv_count and zero C and Q; a patch with bits 0 is not touched"""
+        ld = self.ld()
+        b = np.ascontiguousarray(bv_count, dtype=np.int32)
+        w = np.ascontiguousarray(bits, dtype=np.int32)
+        qa = np.ascontiguousarray(q_alpha, dtype=np.uint16)
+        qb = np.ascontiguousarray(q_bv, dtype=np.uint16)
+        rng = np.ascontiguousarray(range, dtype=np.float32)
+        assert b.shape == w.shape == (self.P,) and qa.shape == (self.P, self.ny, ld) and qb.shape == (self.P, ld, 2)
+        assert rng.shape == (self.P, self.ny + 2, 2)
+        self.ctx._check(self.lib.gpc_sparse_dequantize(self.h, _ptr(b), _ptr(w), _ptr(qa), _ptr(qb), _ptr(rng)))
+
+    def dequantize_dev(self, bv_count, bits, q_alpha, q_bv, range):
+        """gpc_sparse_dequantize_dev: device buffers, enqueued on the context's stream"""
+        self.ctx._check(self.lib.gpc_sparse_dequantize_dev(self.h, _ptr(bv_count), _ptr(bits), _ptr(q_alpha), _ptr(q_bv), _ptr(range)))
+
     def sizes(self):
         b = np.zeros(self.P, dtype=np.int32)
         self.ctx._check(self.lib.gpc_sparse_sizes(self.h, _ptr(b)))
@@ -1213,6 +1269,22 @@ def exp_host(x, small=False):
     out = np.zeros_like(x)
     (load().gpc_test_exp_small_host if small else load().gpc_test_exp_host)(_ptr(x), _ptr(out), x.size)
     return out
+
+
+def test_quantize_host(v, w):
+    """gpc_test_quantize_host: the kernels' scalar quantiser on one array at width w -- codes (b,) uint16, range (lo, hi) float32 (2,),
+    the dequantised values (b,)"""
+    v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+    q = np.zeros(v.size, dtype=np.uint16)
+    rng = np.zeros(2, dtype=np.float32)
+    deq = np.zeros(v.size)
+    rc = load().gpc_test_quantize_host(_ptr(v), v.size, int(w), _ptr(q), _ptr(rng), _ptr(deq))
+    if rc != GPC_OK:
+        raise GpcError(rc, "gpc_test_quantize_host")
+    return q, rng, deq
+
+
+test_quantize_host.__test__ = False      # (a library call, not a pytest case)
 
 
 ROUTE_KINDS = {-1: "no route", 0: "nothing", 1: "one-wave", 2: "register", 3: "tiled", 4: "generic", 5: "split"}

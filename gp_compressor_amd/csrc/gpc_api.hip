@@ -331,5 +331,24 @@ void gpc_test_exp_small_host(const double* x, double* out, int n)
 {
     for (int i = 0; i < n; ++i) out[i] = gpc_exp_small(x[i]);
 }
+// Host-side evaluation of the scalar quantiser (same source, gpc_device.h): codes q [b], range = (lo, hi), the dequantised values [b].
+int gpc_test_quantize_host(const double* v, int b, int w, uint16_t* q, float* range, double* deq)
+{
+    if (!v || b < 1 || w < 1 || w > 16) return GPC_EINVAL;
+    double mn = v[0], mx = v[0];
+    for (int i = 1; i < b; ++i) {
+        mn = v[i] < mn ? v[i] : mn;
+        mx = v[i] > mx ? v[i] : mx;
+    }
+    const float lo = gpc_q_lo(mn), hi = gpc_q_hi(mx);
+    const double step = gpc_q_step(lo, hi, w);
+    if (range) { range[0] = lo; range[1] = hi; }
+    for (int i = 0; i < b; ++i) {
+        const uint16_t c = gpc_q_code(v[i], lo, step, w);
+        if (q) q[i] = c;
+        if (deq) deq[i] = gpc_q_value(c, lo, step);
+    }
+    return GPC_OK;
+}
 
 }  // extern "C"

@@ -152,6 +152,55 @@ __device__ static inline uint8_t rp_flatten(double x)
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The scalar quantiser of the bit-packed model (include/gpc.h, gpc_sparse_quantize_rd): one definition for the search kernel, the decoder
+// kernel and the host (gpc_test_quantize_host).  An array v[0..b) of finite doubles at width w in 1..16:
+//     lo = the largest float <= min v, hi = the smallest float >= max v      (they do not depend on w)
+//     step = (hi - lo) / (2^w - 1);   q_i = step > 0 ? clamp(rint((v_i - lo) / step), 0, 2^w - 1) : 0;   v'_i = lo + q_i * step
+// Every operation is rounded once (contraction off inside these bodies), so that tests/quantize_ref.py reproduces the bits.
+// ---------------------------------------------------------------------------------------------------------
+__host__ __device__ static inline float gpc_q_lo(double vmin)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __double2float_rd(vmin);
+#else
+    const float f = (float)vmin;
+    return (double)f > vmin ? __builtin_nextafterf(f, -__builtin_inff()) : f;
+#endif
+}
+
+__host__ __device__ static inline float gpc_q_hi(double vmax)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __double2float_ru(vmax);
+#else
+    const float f = (float)vmax;
+    return (double)f < vmax ? __builtin_nextafterf(f, __builtin_inff()) : f;
+#endif
+}
+
+__host__ __device__ static inline double gpc_q_step(float lo, float hi, int w)
+{
+#pragma clang fp contract(off)
+    return ((double)hi - (double)lo) / (double)((1 << w) - 1);
+}
+
+__host__ __device__ static inline uint16_t gpc_q_code(double v, float lo, double step, int w)
+{
+#pragma clang fp contract(off)
+    if (!(step > 0.0)) return 0;
+    const double qmax = (double)((1 << w) - 1);
+    const double r = __builtin_rint((v - (double)lo) / step);      // round-half-even
+    return (uint16_t)(!(r > 0.0) ? 0.0 : (r > qmax ? qmax : r));
+}
+
+__host__ __device__ static inline double gpc_q_value(uint16_t q, float lo, double step)
+{
+#pragma clang fp contract(off)
+    const double t = (double)q * step;
+    return (double)lo + t;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // wave / block reductions
 // ---------------------------------------------------------------------------------------------------------
 __device__ static inline double gpc_wave_sum(double v)

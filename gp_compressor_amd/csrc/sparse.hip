@@ -1800,6 +1800,195 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_prune_rd_kernel(SpPruneRdPa
     }
 }
 
+// ---- quantise to the fewest bits in a distortion bound (include/gpc.h, gpc_sparse_quantize_rd_dev) ----------------------------------
+// The search of sparse_prune_rd_kernel over another axis: not which vector goes, but how many bits each coefficient keeps.  Per patch the
+// ny + 2 arrays (BV column 0, BV column 1, the alpha planes) get their float range once; then, width by width, the dequantised alpha' and
+// BV' go where the look-ahead keeps its al / bv and sp_rd_mse gives their error in its fixed order.  The state is only read: the raw
+// values are re-read from memory at every width (b (ny + 2) doubles, in L2 after the first), and the accepted width's codes are formed
+// from them once more at the end.  Ranges: a block min / max (exact, so the tree does not matter).
+#define SP_Q_MAXBITS 16
+struct SpQuantParams {
+    int P, ny, ld, n_total, bits_min, bits_max;
+    const int32_t* off;
+    const double *x0, *x1, *y;
+    double max_mse;
+    const double* max_mse_p;   // [P] or nullptr (every patch: max_mse)
+    double sf, c_exp;
+    const double *alpha, *BV;
+    const int32_t *b, *stat;
+    int32_t *bits, *status_out;          // each output may be nullptr
+    uint16_t *q_alpha, *q_bv;
+    float* range;
+    double *mse0, *mse_q, *curve;
+};
+
+// array a of the patch (0, 1: the BV columns, 2 + c: alpha plane c), element i
+__device__ static __forceinline__ double sp_q_raw(const double* alpha, const double* BV, int ld, int a, int i)
+{
+    return a < 2 ? BV[2 * i + a] : alpha[(a - 2) * ld + i];
+}
+
+template <int NY>
+__global__ __launch_bounds__(SP_THREADS) void sparse_quantize_rd_kernel(SpQuantParams A)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NA = NY + 2;
+    const int tid = threadIdx.x, ld = A.ld, nw = SP_NTH >> 6;
+    double* sres = reinterpret_cast<double*>(smem);     // 2
+    double* red = sres + 2;                             // [NA][2][4]: per-wave min / max of each array
+    float* rng = reinterpret_cast<float*>(red + NA * 8);   // [NA][2] floats (NA doubles)
+    double* T = red + NA * 8 + NA + (NA & 1);           // 64 (16-byte aligned)
+    double* al = T + GPC_EXP_TABLE_SIZE;                // [NY][ld]: alpha of the state whose error is taken
+    double* bv = al + NY * ld;                          // [ld][2]
+    double* ebuf = bv + 2 * ld;                         // [SP_NTH]: per-point errors of a chunk
+    gpc_exp_table_init(T);
+    for (int patch = blockIdx.x; patch < A.P; patch += gridDim.x) {
+        const double* alpha = A.alpha + (size_t)patch * NY * ld;
+        const double* BV = A.BV + (size_t)patch * ld * 2;
+        int b = A.b[patch];
+        if (b > ld) b = ld;                             // (gpc_sparse_set_state admits no more)
+        if (b < 0) b = 0;
+        const int o = A.off[patch], n = A.off[patch + 1] - o;
+        const double bound = A.max_mse_p ? A.max_mse_p[patch] : A.max_mse;
+        const double *x0 = A.x0 + o, *x1 = A.x1 + o, *y = A.y + o;
+        const double nan = __builtin_nan("");
+        double e0 = nan, eq = nan;
+        int bits = 0;
+        __syncthreads();                                // the scratch of the previous patch is free
+        // the raw state into LDS: mse0, and whether every value is finite
+        int bad = 0;
+        double mn[NA], mx[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) { mn[a] = __builtin_inf(); mx[a] = -__builtin_inf(); }
+        for (int i = tid; i < b; i += SP_NTH) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const double v = sp_q_raw(alpha, BV, ld, a, i);
+                if (a < 2) bv[2 * i + a] = v;
+                else al[(a - 2) * ld + i] = v;
+                bad |= !__builtin_isfinite(v);
+                mn[a] = v < mn[a] ? v : mn[a];
+                mx[a] = v > mx[a] ? v : mx[a];
+            }
+        }
+        if (n > 0) e0 = sp_rd_mse<NY>(al, bv, b, ld, x0, x1, y, n, A.n_total, A.sf, A.c_exp, T, ebuf, sres);
+        const bool escape = __syncthreads_or(bad) != 0 || b == 0 || n == 0;
+        if (!escape) {
+            // the ranges: wave min / max by the xor tree, then across the waves through LDS
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) {
+                    const double m0 = __shfl_xor(mn[a], d, 64), m1 = __shfl_xor(mx[a], d, 64);
+                    mn[a] = m0 < mn[a] ? m0 : mn[a];
+                    mx[a] = m1 > mx[a] ? m1 : mx[a];
+                }
+                if ((tid & 63) == 0) {
+                    red[(a * 2 + 0) * 4 + (tid >> 6)] = mn[a];
+                    red[(a * 2 + 1) * 4 + (tid >> 6)] = mx[a];
+                }
+            }
+            __syncthreads();
+            if (tid < NA) {
+                double m0 = red[(tid * 2) * 4], m1 = red[(tid * 2 + 1) * 4];
+                for (int k = 1; k < nw; ++k) {
+                    const double u0 = red[(tid * 2) * 4 + k], u1 = red[(tid * 2 + 1) * 4 + k];
+                    m0 = u0 < m0 ? u0 : m0;
+                    m1 = u1 > m1 ? u1 : m1;
+                }
+                const float lo = gpc_q_lo(m0), hi = gpc_q_hi(m1);
+                rng[2 * tid] = lo;
+                rng[2 * tid + 1] = hi;
+                if (A.range) {
+                    A.range[((size_t)patch * NA + tid) * 2] = lo;
+                    A.range[((size_t)patch * NA + tid) * 2 + 1] = hi;
+                }
+            }
+            __syncthreads();
+            for (int w = A.bits_min; w <= A.bits_max; ++w) {
+                // (sp_rd_mse has left every thread behind a barrier: the readers of al / bv of the previous width are through)
+                for (int i = tid; i < b; i += SP_NTH) {
+#pragma unroll
+                    for (int a = 0; a < NA; ++a) {
+                        const float lo = rng[2 * a];
+                        const double step = gpc_q_step(lo, rng[2 * a + 1], w);
+                        const double v = gpc_q_value(gpc_q_code(sp_q_raw(alpha, BV, ld, a, i), lo, step, w), lo, step);
+                        if (a < 2) bv[2 * i + a] = v;
+                        else al[(a - 2) * ld + i] = v;
+                    }
+                }
+                const double e = sp_rd_mse<NY>(al, bv, b, ld, x0, x1, y, n, A.n_total, A.sf, A.c_exp, T, ebuf, sres);
+                if (tid == 0 && A.curve) A.curve[(size_t)patch * SP_Q_MAXBITS + (w - 1)] = e;
+                if (e <= bound) { bits = w; eq = e; break; }       // (a NaN error or a NaN bound compares false: on to the next width)
+            }
+            // the accepted width's codes, from the raw state
+            if (bits > 0 && (A.q_alpha || A.q_bv)) {
+                for (int i = tid; i < b; i += SP_NTH) {
+#pragma unroll
+                    for (int a = 0; a < NA; ++a) {
+                        const float lo = rng[2 * a];
+                        const uint16_t q = gpc_q_code(sp_q_raw(alpha, BV, ld, a, i), lo, gpc_q_step(lo, rng[2 * a + 1], bits), bits);
+                        if (a < 2) { if (A.q_bv) A.q_bv[((size_t)patch * ld + i) * 2 + a] = q; }
+                        else if (A.q_alpha) A.q_alpha[((size_t)patch * NY + (a - 2)) * ld + i] = q;
+                    }
+                }
+            }
+        }
+        if (tid == 0) {
+            if (A.bits) A.bits[patch] = bits;
+            if (A.mse0) A.mse0[patch] = e0;
+            if (A.mse_q) A.mse_q[patch] = eq;
+            if (A.status_out) A.status_out[patch] = A.stat[patch];
+        }
+    }
+}
+
+// ---- the decoder of the bit-packed model (include/gpc.h, gpc_sparse_dequantize_dev): one workgroup per patch -------------------------
+struct SpDequantParams {
+    int P, ny, ld;
+    const int32_t *bv_count, *bits;
+    const uint16_t *q_alpha, *q_bv;
+    const float* range;
+    double *alpha, *C, *Q, *BV;
+    int32_t *b, *count, *stat;
+};
+
+__global__ __launch_bounds__(SP_THREADS) void sparse_dequantize_kernel(SpDequantParams A)
+{
+    const int patch = blockIdx.x, tid = threadIdx.x, ld = A.ld, ny = A.ny, na = ny + 2;
+    int w = A.bits[patch];
+    if (w <= 0) return;                                 // a raw leaf: not touched
+    if (w > SP_Q_MAXBITS) w = SP_Q_MAXBITS;
+    int b = A.bv_count[patch];
+    b = b < 0 ? 0 : (b > ld ? ld : b);
+    const float* rng = A.range + (size_t)patch * na * 2;
+    double* alpha = A.alpha + (size_t)patch * ny * ld;
+    double* BV = A.BV + (size_t)patch * ld * 2;
+    for (int e = tid; e < na * ld; e += SP_THREADS) {
+        const int a = e / ld, i = e - a * ld;
+        double v = 0.0;
+        if (i < b) {
+            const float lo = rng[2 * a];
+            const double step = gpc_q_step(lo, rng[2 * a + 1], w);
+            const uint16_t q = a < 2 ? A.q_bv[((size_t)patch * ld + i) * 2 + a] : A.q_alpha[((size_t)patch * ny + (a - 2)) * ld + i];
+            v = gpc_q_value(q, lo, step);
+        }
+        if (a < 2) BV[2 * i + a] = v;
+        else alpha[(a - 2) * ld + i] = v;
+    }
+    double* Cp = A.C + (size_t)patch * ld * ld;
+    double* Qp = A.Q + (size_t)patch * ld * ld;
+    for (int e = tid; e < ld * ld; e += SP_THREADS) {
+        Cp[e] = 0.0;
+        Qp[e] = 0.0;
+    }
+    if (tid == 0) {
+        A.b[patch] = b;
+        A.count[patch] = b;
+        A.stat[patch] = GPC_STATUS_OK;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 static size_t sp_add_lds_small(int bm = SP_BMAX) { return sizeof(double) * (size_t)(64 + 16 + 6 + 4 * (bm + 2) + 22 * (bm + 1) + 2 * bm * bm); }
@@ -2002,6 +2191,49 @@ int sp_prune_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const dou
     per_cu = std::min(per_cu, 1024 / nth);
     const int grid = std::min(g->P, ctx->num_cus * per_cu);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(nth), lds, ctx->stream, A);
+    GPC_HIP(ctx, hipGetLastError());
+    return GPC_OK;
+}
+
+int sp_quantize_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int bits_min,
+                          int bits_max, double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha, uint16_t* q_bv, float* range,
+                          double* mse0, double* mse_q, double* curve, int32_t* status)
+{
+    gpc_ctx* ctx = g->ctx;
+    SpQuantParams A;
+    A.P = g->P; A.ny = g->ny; A.ld = g->ld; A.n_total = n_total; A.bits_min = bits_min; A.bits_max = bits_max;
+    A.off = off; A.x0 = x0; A.x1 = x1; A.y = y;
+    A.max_mse = max_mse; A.max_mse_p = max_mse_p;
+    A.sf = g->prm.sigmaf_sq;
+    A.c_exp = (double)(-0.5f) / g->prm.l_sq;
+    A.alpha = g->alpha; A.BV = g->BV; A.b = g->b; A.stat = g->stat;
+    A.bits = bits; A.status_out = status; A.q_alpha = q_alpha; A.q_bv = q_bv; A.range = range;
+    A.mse0 = mse0; A.mse_q = mse_q; A.curve = curve;
+    // the workgroup shapes and the sizing of sp_prune_rd_launch; the error sum gives the same bits in each
+    const int cap_ = g->prm.capacity;
+    const int nth = (cap_ <= 0 || getenv("GPC_SPARSE_WIDE")) ? SP_THREADS : cap_ <= 64 ? 64 : cap_ <= 100 ? 128 : SP_THREADS;
+    const int na = g->ny + 2;
+    const size_t lds = sizeof(double) * (size_t)(2 + 9 * na + (na & 1) + GPC_EXP_TABLE_SIZE + na * g->ld + nth);
+    void (*const kernel)(SpQuantParams) = g->ny == 1 ? sparse_quantize_rd_kernel<1> : sparse_quantize_rd_kernel<3>;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nth, lds) != hipSuccess || per_cu < 1) per_cu = 768 / nth;
+    per_cu = std::min(per_cu, 1024 / nth);
+    const int grid = std::min(g->P, ctx->num_cus * per_cu);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(nth), lds, ctx->stream, A);
+    GPC_HIP(ctx, hipGetLastError());
+    return GPC_OK;
+}
+
+int sp_dequantize_launch(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
+                         const float* range)
+{
+    gpc_ctx* ctx = g->ctx;
+    SpDequantParams A;
+    A.P = g->P; A.ny = g->ny; A.ld = g->ld;
+    A.bv_count = bv_count; A.bits = bits; A.q_alpha = q_alpha; A.q_bv = q_bv; A.range = range;
+    A.alpha = g->alpha; A.C = g->C; A.Q = g->Q; A.BV = g->BV;
+    A.b = g->b; A.count = g->count; A.stat = g->stat;
+    hipLaunchKernelGGL(sparse_dequantize_kernel, dim3(g->P), dim3(SP_THREADS), 0, ctx->stream, A);
     GPC_HIP(ctx, hipGetLastError());
     return GPC_OK;
 }

@@ -244,6 +244,50 @@ int gpc_sparse_prune_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, cons
                               status);
 }
 
+// what both quantise entries check before they look at the batch (include/gpc.h)
+static int sp_quantize_rd_check(gpc_sparse* g, int bits_min, int bits_max, double max_mse, const double* max_mse_p)
+{
+    gpc_ctx* ctx = g->ctx;
+    if (g->prm.noise_model != GPC_NOISE_GAUSSIAN)
+        return gpc_fail(ctx, GPC_EINVAL, "quantize_rd: the error is taken against the Gaussian read-out (noise_model 0), got %d", g->prm.noise_model);
+    if (bits_min < 1 || bits_max > 16 || bits_min > bits_max)
+        return gpc_fail(ctx, GPC_EINVAL, "quantize_rd: widths must satisfy 1 <= bits_min <= bits_max <= 16, got %d .. %d", bits_min, bits_max);
+    if (!max_mse_p && !(max_mse >= 0.0)) return gpc_fail(ctx, GPC_EINVAL, "max_mse must be >= 0 (+inf allowed), got %g", max_mse);
+    return GPC_OK;
+}
+
+int gpc_sparse_quantize_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
+                               int bits_min, int bits_max, double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha,
+                               uint16_t* q_bv, float* range, double* mse0, double* mse_q, double* curve, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_quantize_rd_check(g, bits_min, bits_max, max_mse, max_mse_p)) return rc;
+    if (n_total < 0) return gpc_fail(ctx, GPC_EINVAL, "negative size");
+    if (g->P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (n_total > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    if (g->P == 0) return GPC_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
+    return sp_quantize_rd_launch(g, off, n_total, x0, x1, y, bits_min, bits_max, max_mse, max_mse_p, bits, q_alpha, q_bv, range, mse0, mse_q,
+                                 curve, status);
+}
+
+int gpc_sparse_dequantize_dev(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
+                              const float* range)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (g->P == 0) return GPC_OK;
+    if (!bv_count || !bits || !q_alpha || !q_bv || !range) return gpc_fail(ctx, GPC_EINVAL, "bv_count/bits/q_alpha/q_bv/range is NULL");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    return sp_dequantize_launch(g, bv_count, bits, q_alpha, q_bv, range);
+}
+
 int gpc_sparse_predict_dev(gpc_sparse* g, int m, const double* xs0, const double* xs1, double* f_star, double* sigma,
                            int conf, int32_t* status)
 {
@@ -495,6 +539,72 @@ int gpc_sparse_prune_rd(gpc_sparse* g, const int32_t* off, const double* x0, con
     st.down(mse0, d_mse0, P);
     st.down(mse_next, d_next, P);
     st.down(status, d_st, P);
+    return st.finish();
+}
+
+int gpc_sparse_quantize_rd(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y, int bits_min, int bits_max,
+                           double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha, uint16_t* q_bv, float* range,
+                           double* mse0, double* mse_q, double* curve, int32_t* status)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    if (int rc = sp_quantize_rd_check(g, bits_min, bits_max, max_mse, max_mse_p)) return rc;
+    const size_t P = (size_t)g->P, ld = (size_t)g->ld, ny = (size_t)g->ny;
+    if (P > 0 && !off) return gpc_fail(ctx, GPC_EINVAL, "off is NULL");
+    if (P == 0) return GPC_OK;
+    if (int rc = gpc_check_host_off(ctx, (int)P, off, nullptr, nullptr)) return rc;
+    const size_t N = (size_t)off[P];
+    if (N > 0 && (!x0 || !x1 || !y)) return gpc_fail(ctx, GPC_EINVAL, "x0/x1/y is NULL");
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_quantize_rd");
+    const int32_t* d_off = st.up(off, P + 1);
+    const double *d_x0 = st.up(x0, N), *d_x1 = st.up(x1, N), *d_y = st.up(y, N * ny);
+    const double* d_bound = max_mse_p ? st.up(max_mse_p, P) : nullptr;
+    int32_t* d_bits = bits ? st.out<int32_t>(P) : nullptr;
+    // what the call may leave unwritten goes up first: the codes at and beyond the basis count, everything of an escaped patch, the
+    // curve entries of the widths not evaluated come back as the caller left them
+    uint16_t* d_qa = q_alpha ? st.up(q_alpha, P * ny * ld) : nullptr;
+    uint16_t* d_qb = q_bv ? st.up(q_bv, P * ld * 2) : nullptr;
+    float* d_rng = range ? st.up(range, P * (ny + 2) * 2) : nullptr;
+    double* d_curve = curve ? st.up(curve, P * 16) : nullptr;
+    double* d_mse0 = mse0 ? st.out<double>(P) : nullptr;
+    double* d_mseq = mse_q ? st.out<double>(P) : nullptr;
+    int32_t* d_st = status ? st.out<int32_t>(P) : nullptr;
+    if (st.ok())
+        st.rc = gpc_sparse_quantize_rd_dev(g, d_off, (int)N, d_x0, d_x1, d_y, bits_min, bits_max, max_mse, d_bound, d_bits, d_qa, d_qb, d_rng,
+                                           d_mse0, d_mseq, d_curve, d_st);
+    st.down(bits, d_bits, P);
+    st.down(q_alpha, d_qa, P * ny * ld);
+    st.down(q_bv, d_qb, P * ld * 2);
+    st.down(range, d_rng, P * (ny + 2) * 2);
+    st.down(curve, d_curve, P * 16);
+    st.down(mse0, d_mse0, P);
+    st.down(mse_q, d_mseq, P);
+    st.down(status, d_st, P);
+    return st.finish();
+}
+
+int gpc_sparse_dequantize(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
+                          const float* range)
+{
+    if (!g) return GPC_EINVAL;
+    gpc_ctx* ctx = g->ctx;
+    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    const size_t P = (size_t)g->P, ld = (size_t)g->ld, ny = (size_t)g->ny;
+    if (P == 0) return GPC_OK;
+    if (!bv_count || !bits || !q_alpha || !q_bv || !range) return gpc_fail(ctx, GPC_EINVAL, "bv_count/bits/q_alpha/q_bv/range is NULL");
+    for (size_t i = 0; i < P; ++i) {
+        if (bits[i] < 0 || bits[i] > 16) return gpc_fail(ctx, GPC_EINVAL, "bits[%d] = %d outside [0, 16]", (int)i, bits[i]);
+        if (bv_count[i] < 0 || bv_count[i] > g->ld)
+            return gpc_fail(ctx, GPC_EINVAL, "bv_count[%d] = %d outside [0, %d]", (int)i, bv_count[i], g->ld);
+    }
+    GPC_HIP(ctx, hipSetDevice(ctx->device));
+    GpcStaging st(ctx, "gpc_sparse_dequantize");
+    const int32_t *d_b = st.up(bv_count, P), *d_w = st.up(bits, P);
+    const uint16_t *d_qa = st.up(q_alpha, P * ny * ld), *d_qb = st.up(q_bv, P * ld * 2);
+    const float* d_rng = st.up(range, P * (ny + 2) * 2);
+    if (st.ok()) st.rc = gpc_sparse_dequantize_dev(g, d_b, d_w, d_qa, d_qb, d_rng);
     return st.finish();
 }
 

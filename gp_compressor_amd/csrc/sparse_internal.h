@@ -36,6 +36,13 @@ int sp_prune_launch(gpc_sparse* g, int keep, const int32_t* target, double score
 int sp_prune_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
                        const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order, double* scores,
                        double* mse, double* mse0, double* mse_next, int32_t* status);
+// sparse.hip: gpc_sparse_quantize_rd_dev behind its argument checks (every output may be nullptr; max_mse_p == nullptr: max_mse)
+int sp_quantize_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int bits_min,
+                          int bits_max, double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha, uint16_t* q_bv, float* range,
+                          double* mse0, double* mse_q, double* curve, int32_t* status);
+// sparse.hip: gpc_sparse_dequantize_dev behind its argument checks (counts and widths are clamped by the kernel)
+int sp_dequantize_launch(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
+                         const float* range);
 // sparse_predict.hip.  off == nullptr: every patch at the shared grid xs0 / xs1 [m]; else patch i at its own points off[i] .. off[i+1]-1 of
 // xs0 / xs1 (m == 0, plane stride n_total).  max_blocks: cap on the resident workgroups per CU of the regular kernel.
 int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, const double* xs0, const double* xs1, double* f_star,

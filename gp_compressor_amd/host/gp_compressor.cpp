@@ -820,10 +820,110 @@ pointcloud gp_compressor::load_compressed()
 // little-endian; header: "GPCM", u32 version = 1, f64 res, i32 sz, i32 P, gpc_params depth, gpc_params rgb (raw structs, with their
 // size in front); per patch: f64 R[9], mean[3], rgb_mean[3]; i32 b_depth, b_rgb; f64 BV_depth[b][2], alpha_depth[b],
 // BV_rgb[b'][2], alpha_rgb[3][b'].
+// version = 2 (save_model_quantized): the same header; per patch after b_depth, b_rgb: u8 w_depth, w_rgb; then per GP (depth, ny = 1; colour,
+// ny = 3): w == 0: the raw doubles of version 1; w > 0: f32 (lo, hi) x (ny + 2) in the order BV column 0, BV column 1, the alpha planes, then
+// the w-bit codes of BV0[0..b), BV1[0..b), alpha plane 0[0..b), .. packed LSB-first (code k holds bits k w .. (k + 1) w - 1 of the stream, bit
+// j of the stream is bit j % 8 of byte j / 8), zero-padded to a whole byte per GP.  The values are v = lo + code * (hi - lo) / (2^w - 1)
+// (include/gpc.h, gpc_sparse_quantize_rd).
 namespace {
 struct file_closer { void operator()(FILE* f) const { if (f) std::fclose(f); } };
 template <class T> void wr(FILE* f, const T* p, size_t n) { if (n && std::fwrite(p, sizeof(T), n, f) != n) throw std::runtime_error("model file: write failed"); }
 template <class T> void rd(FILE* f, T* p, size_t n) { if (n && std::fread(p, sizeof(T), n, f) != n) throw std::runtime_error("model file: truncated"); }
+
+// one GP's codes as a bit stream, LSB-first
+struct bit_packer {
+    std::vector<uint8_t> bytes;
+    uint64_t acc = 0;
+    int held = 0;
+    void put(uint32_t code, int w)
+    {
+        acc |= (uint64_t)(code & ((1u << w) - 1u)) << held;
+        held += w;
+        for (; held >= 8; held -= 8, acc >>= 8) bytes.push_back((uint8_t)(acc & 0xff));
+    }
+    void pad()
+    {
+        if (held > 0) bytes.push_back((uint8_t)(acc & 0xff));
+        acc = 0;
+        held = 0;
+    }
+};
+struct bit_reader {
+    const uint8_t* bytes;
+    size_t pos = 0;
+    uint64_t acc = 0;
+    int held = 0;
+    uint16_t get(int w)
+    {
+        for (; held < w; held += 8) acc |= (uint64_t)bytes[pos++] << held;
+        const uint16_t code = (uint16_t)(acc & ((1u << w) - 1u));
+        acc >>= w;
+        held -= w;
+        return code;
+    }
+};
+size_t packed_bytes(int b, int ny, int w) { return ((size_t)b * (size_t)(ny + 2) * (size_t)w + 7) / 8; }
+
+// what gpc_sparse_quantize_rd leaves of one GP, with the raw state beside it for the leaves that escape
+struct quantized_gp {
+    int ny = 1, ld = 0;
+    std::vector<int32_t> b, bits;
+    std::vector<uint16_t> qa, qb;       // [P][ny][ld], [P][ld][2]
+    std::vector<float> range;           // [P][ny + 2][2]
+    std::vector<double> alpha, bv;      // [P][ny][ld], [P][ld][2]
+};
+
+// the GP of patch i as version 2 stores it
+void write_gp_v2(FILE* f, const quantized_gp& q, int i)
+{
+    const int ny = q.ny, ld = q.ld, b = q.b[i], w = q.bits[i];
+    const double* bv = &q.bv[(size_t)i * ld * 2];
+    if (w == 0) {
+        wr(f, bv, (size_t)2 * b);
+        for (int c = 0; c < ny; ++c) wr(f, &q.alpha[((size_t)i * ny + c) * ld], (size_t)b);
+        return;
+    }
+    wr(f, &q.range[(size_t)i * (ny + 2) * 2], (size_t)(ny + 2) * 2);
+    bit_packer pk;
+    pk.bytes.reserve(packed_bytes(b, ny, w));
+    for (int col = 0; col < 2; ++col)
+        for (int k = 0; k < b; ++k) pk.put(q.qb[((size_t)i * ld + k) * 2 + col], w);
+    for (int c = 0; c < ny; ++c)
+        for (int k = 0; k < b; ++k) pk.put(q.qa[((size_t)i * ny + c) * ld + k], w);
+    pk.pad();
+    wr(f, pk.bytes.data(), pk.bytes.size());
+}
+
+// ... and read back: a raw leaf into alpha / bv, a quantised one into range / qa / qb
+void read_gp_v2(FILE* f, quantized_gp& q, int i)
+{
+    const int ny = q.ny, ld = q.ld, b = q.b[i], w = q.bits[i];
+    if (w == 0) {
+        rd(f, &q.bv[(size_t)i * ld * 2], (size_t)2 * b);
+        for (int c = 0; c < ny; ++c) rd(f, &q.alpha[((size_t)i * ny + c) * ld], (size_t)b);
+        return;
+    }
+    rd(f, &q.range[(size_t)i * (ny + 2) * 2], (size_t)(ny + 2) * 2);
+    std::vector<uint8_t> bytes(packed_bytes(b, ny, w));
+    rd(f, bytes.data(), bytes.size());
+    bit_reader br{bytes.data()};
+    for (int col = 0; col < 2; ++col)
+        for (int k = 0; k < b; ++k) q.qb[((size_t)i * ld + k) * 2 + col] = br.get(w);
+    for (int c = 0; c < ny; ++c)
+        for (int k = 0; k < b; ++k) q.qa[((size_t)i * ny + c) * ld + k] = br.get(w);
+}
+
+void size_gp(quantized_gp& q, int P, int ny, int ld)
+{
+    q.ny = ny; q.ld = ld;
+    q.b.assign(P, 0);
+    q.bits.assign(P, 0);
+    q.qa.assign((size_t)P * ny * ld, 0);
+    q.qb.assign((size_t)P * ld * 2, 0);
+    q.range.assign((size_t)P * (ny + 2) * 2, 0.0f);
+    q.alpha.assign((size_t)P * ny * ld, 0.0);
+    q.bv.assign((size_t)P * ld * 2, 0.0);
+}
 }  // namespace
 
 size_t gp_compressor::save_model(const std::string& path)
@@ -867,6 +967,63 @@ size_t gp_compressor::save_model(const std::string& path)
     return pos < 0 ? 0 : (size_t)pos;
 }
 
+size_t gp_compressor::save_model_quantized(const std::string& path, double max_mse_depth, double max_mse_rgb, int bits_min, int bits_max)
+{
+    if (model_ != gp_model::sparse) throw std::runtime_error("save_model_quantized: the sparse model only");
+    if (!devices_.empty())
+        throw std::runtime_error("save_model_quantized: the single-device flow only (the sharded states live on their devices)");
+    if (loaded_)
+        throw std::runtime_error("save_model_quantized: a loaded model has no training points; quantise the trained object");
+    if (!trained_) { project_cloud(); train_processes(); }
+    const int P = batch_.patches();
+    quantized_gp qd, qc;
+    if (P > 0) {
+        size_gp(qd, P, 1, gpc_sparse_ld(gps_));
+        size_gp(qc, P, 3, gpc_sparse_ld(rgb_gps_));
+        const double* ys[2] = {batch_.y.data(), batch_.rgb.data()};
+        const double bound[2] = {max_mse_depth, max_mse_rgb};
+        gpc_sparse* gp[2] = {gps_, rgb_gps_};
+        quantized_gp* q[2] = {&qd, &qc};
+        for (int k = 0; k < 2; ++k) {
+            check(gpc_sparse_sizes(gp[k], q[k]->b.data()), ctx_, "gpc_sparse_sizes");
+            check(gpc_sparse_get_state(gp[k], q[k]->alpha.data(), nullptr, nullptr, q[k]->bv.data()), ctx_, "gpc_sparse_get_state");
+            check(gpc_sparse_quantize_rd(gp[k], batch_.off.data(), batch_.x0.data(), batch_.x1.data(), ys[k], bits_min, bits_max, bound[k], nullptr,
+                                         q[k]->bits.data(), q[k]->qa.data(), q[k]->qb.data(), q[k]->range.data(), nullptr, nullptr, nullptr,
+                                         nullptr),
+                  ctx_, k == 0 ? "gpc_sparse_quantize_rd(depth)" : "gpc_sparse_quantize_rd(rgb)");
+            // a leaf whose quantised form (ranges + codes) would not be smaller than its raw doubles -- one vector -- stays raw
+            for (int i = 0; i < P; ++i) {
+                const size_t na = (size_t)q[k]->ny + 2, b = (size_t)q[k]->b[i];
+                if (q[k]->bits[i] > 0 && 8 * na + packed_bytes((int)b, q[k]->ny, q[k]->bits[i]) >= 8 * b * na) q[k]->bits[i] = 0;
+            }
+        }
+    }
+    std::unique_ptr<FILE, file_closer> f(std::fopen(path.c_str(), "wb"));
+    if (!f) throw std::runtime_error("save_model_quantized: cannot open " + path);
+    const uint32_t version = 2, psz = (uint32_t)sizeof(gpc_params);
+    wr(f.get(), "GPCM", 4);
+    wr(f.get(), &version, 1);
+    wr(f.get(), &res_, 1);
+    const int32_t hdr[2] = {sz_, P};
+    wr(f.get(), hdr, 2);
+    wr(f.get(), &psz, 1);
+    wr(f.get(), &depth_params, 1);
+    wr(f.get(), &rgb_params, 1);
+    for (int i = 0; i < P; ++i) {
+        wr(f.get(), batch_.rotations[i].data(), 9);
+        wr(f.get(), batch_.means[i].data(), 3);
+        wr(f.get(), batch_.rgb_means[i].data(), 3);
+        const int32_t b2[2] = {qd.b[i], qc.b[i]};
+        wr(f.get(), b2, 2);
+        const uint8_t w2[2] = {(uint8_t)qd.bits[i], (uint8_t)qc.bits[i]};
+        wr(f.get(), w2, 2);
+        write_gp_v2(f.get(), qd, i);
+        write_gp_v2(f.get(), qc, i);
+    }
+    const long pos = std::ftell(f.get());
+    return pos < 0 ? 0 : (size_t)pos;
+}
+
 gp_compressor* gp_compressor::load_model(const std::string& path, int device)
 {
     std::unique_ptr<FILE, file_closer> f(std::fopen(path.c_str(), "rb"));
@@ -877,7 +1034,7 @@ gp_compressor* gp_compressor::load_model(const std::string& path, int device)
     int32_t hdr[2] = {0, 0};
     rd(f.get(), magic, 4);
     rd(f.get(), &version, 1);
-    if (std::memcmp(magic, "GPCM", 4) != 0 || version != 1) throw std::runtime_error("load_model: not a GPCM v1 file");
+    if (std::memcmp(magic, "GPCM", 4) != 0 || (version != 1 && version != 2)) throw std::runtime_error("load_model: not a GPCM v1 or v2 file");
     rd(f.get(), &res, 1);
     rd(f.get(), hdr, 2);
     rd(f.get(), &psz, 1);
@@ -896,8 +1053,10 @@ gp_compressor* gp_compressor::load_model(const std::string& path, int device)
         check(gpc_sparse_create(g->ctx_, &g->depth_params, P, 1, &g->gps_), g->ctx_, "gpc_sparse_create(depth)");
         check(gpc_sparse_create(g->ctx_, &g->rgb_params, P, 3, &g->rgb_gps_), g->ctx_, "gpc_sparse_create(rgb)");
         const int ldd = gpc_sparse_ld(g->gps_), ldc = gpc_sparse_ld(g->rgb_gps_);
-        std::vector<int32_t> bd(P), bc(P);
-        std::vector<double> ad((size_t)P * ldd, 0.0), bvd((size_t)P * ldd * 2, 0.0), ac((size_t)P * 3 * ldc, 0.0), bvc((size_t)P * ldc * 2, 0.0);
+        quantized_gp qd, qc;                 // (version 1: every width 0, every leaf raw)
+        size_gp(qd, P, 1, ldd);
+        size_gp(qc, P, 3, ldc);
+        bool any_quantized = false;
         for (int i = 0; i < P; ++i) {
             rd(f.get(), g->batch_.rotations[i].data(), 9);
             rd(f.get(), g->batch_.means[i].data(), 3);
@@ -905,15 +1064,26 @@ gp_compressor* gp_compressor::load_model(const std::string& path, int device)
             int32_t b2[2];
             rd(f.get(), b2, 2);
             if (b2[0] < 0 || b2[0] > ldd || b2[1] < 0 || b2[1] > ldc) throw std::runtime_error("load_model: basis-vector count out of range");
-            bd[i] = b2[0];
-            bc[i] = b2[1];
-            rd(f.get(), &bvd[(size_t)i * ldd * 2], (size_t)2 * bd[i]);
-            rd(f.get(), &ad[(size_t)i * ldd], (size_t)bd[i]);
-            rd(f.get(), &bvc[(size_t)i * ldc * 2], (size_t)2 * bc[i]);
-            for (int c = 0; c < 3; ++c) rd(f.get(), &ac[((size_t)i * 3 + c) * ldc], (size_t)bc[i]);
+            uint8_t w2[2] = {0, 0};
+            if (version == 2) rd(f.get(), w2, 2);
+            if (w2[0] > 16 || w2[1] > 16) throw std::runtime_error("load_model: code width out of range");
+            qd.b[i] = b2[0];
+            qc.b[i] = b2[1];
+            qd.bits[i] = w2[0];
+            qc.bits[i] = w2[1];
+            any_quantized = any_quantized || w2[0] || w2[1];
+            read_gp_v2(f.get(), qd, i);
+            read_gp_v2(f.get(), qc, i);
         }
-        check(gpc_sparse_set_state(g->gps_, bd.data(), ad.data(), nullptr, nullptr, bvd.data()), g->ctx_, "gpc_sparse_set_state(depth)");
-        check(gpc_sparse_set_state(g->rgb_gps_, bc.data(), ac.data(), nullptr, nullptr, bvc.data()), g->ctx_, "gpc_sparse_set_state(rgb)");
+        // the raw leaves (a quantised one: zeros for now), then the decoder over the quantised ones
+        check(gpc_sparse_set_state(g->gps_, qd.b.data(), qd.alpha.data(), nullptr, nullptr, qd.bv.data()), g->ctx_, "gpc_sparse_set_state(depth)");
+        check(gpc_sparse_set_state(g->rgb_gps_, qc.b.data(), qc.alpha.data(), nullptr, nullptr, qc.bv.data()), g->ctx_, "gpc_sparse_set_state(rgb)");
+        if (any_quantized) {
+            check(gpc_sparse_dequantize(g->gps_, qd.b.data(), qd.bits.data(), qd.qa.data(), qd.qb.data(), qd.range.data()), g->ctx_,
+                  "gpc_sparse_dequantize(depth)");
+            check(gpc_sparse_dequantize(g->rgb_gps_, qc.b.data(), qc.bits.data(), qc.qa.data(), qc.qb.data(), qc.range.data()), g->ctx_,
+                  "gpc_sparse_dequantize(rgb)");
+        }
     }
     g->trained_ = true;
     g->loaded_ = true;
@@ -1078,6 +1248,16 @@ long long gpc_host_save_model(void* h, const char* path, char* err, int errlen)
 {
     try {
         return (long long)static_cast<gpc::gp_compressor*>(h)->save_model(path);
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// the bit-packed model file: gp_compressor::save_model_quantized (trains first if needed).  Returns bytes, < 0 on error.
+long long gpc_host_save_model_quantized(void* h, const char* path, double max_mse_depth, double max_mse_rgb, int bits_min, int bits_max,
+                                        char* err, int errlen)
+{
+    try {
+        return (long long)static_cast<gpc::gp_compressor*>(h)->save_model_quantized(path, max_mse_depth, max_mse_rgb, bits_min, bits_max);
     } catch (const std::exception& e) {
         return fail(e, err, errlen);
     }

@@ -90,6 +90,13 @@ public:
     // (gpc_sparse_prune_rd on the projected batch; it stops at the first removal that would exceed the bound).  Same preconditions and
     // exceptions as prune(); save_model() then writes the smaller model.  Returns the vectors removed {depth, colour}.
     std::array<long long, 2> prune_to_error(double max_mse_depth, double max_mse_rgb, int keep_depth = 1, int keep_rgb = 1);
+    // Rate control by precision: the model file with every leaf's (BV, alpha) stored at the fewest bits per coefficient, one width per
+    // GP and leaf in bits_min .. bits_max, whose mean square error on the leaf's own training points stays within max_mse_depth /
+    // max_mse_rgb (gpc_sparse_quantize_rd on the projected batch; the first accepted width wins).  Writes GPCM version 2: per GP the
+    // width, ny + 2 float ranges and the bit-packed codes; a leaf no width fits (or that would not be smaller) is stored raw as in version 1.  The
+    // object itself is not modified; load_model() reads both versions.  Trains first if needed.  Same preconditions and exceptions as
+    // prune_to_error(); an argument gpc_sparse_quantize_rd refuses throws.  Returns the number of bytes written.
+    size_t save_model_quantized(const std::string& path, double max_mse_depth, double max_mse_rgb, int bits_min = 1, int bits_max = 16);
 
     // host-only part, usable without a GPU
     void project_cloud();                            // src/gp_compressor.cpp:177-249

@@ -45,6 +45,8 @@ def load():
         L.gpc_host_roundtrip.argtypes = [vp, vp, vp, i, vp, vp, vp, i]
         L.gpc_host_save_model.restype = C.c_longlong
         L.gpc_host_save_model.argtypes = [vp, C.c_char_p, vp, i]
+        L.gpc_host_save_model_quantized.restype = C.c_longlong
+        L.gpc_host_save_model_quantized.argtypes = [vp, C.c_char_p, d, d, i, i, vp, i]
         L.gpc_host_decompress_file.argtypes = [C.c_char_p, i, vp, vp, i, vp, i]
         L.gpc_host_prune.argtypes = [vp, i, i, d, d, vp, vp, i]
         L.gpc_host_prune_to_error.argtypes = [vp, d, d, i, i, vp, vp, i]
@@ -154,6 +156,17 @@ class GpCompressor:
         n = self.L.gpc_host_save_model(self.h, os.fsencode(path), C.addressof(err), 512)
         if n < 0:
             raise RuntimeError(f"save_model failed: {err.value.decode()}")
+        return int(n)
+
+    def save_model_quantized(self, path, max_mse_depth, max_mse_rgb, bits_min=1, bits_max=16):
+        """gp_compressor::save_model_quantized: the model file (GPCM version 2) with every leaf's (BV, alpha) at the fewest bits per
+        coefficient in bits_min .. bits_max whose mean square error on the leaf's own training points stays within max_mse_depth /
+        max_mse_rgb; a leaf no width fits is stored raw.  The object is not modified (trains first if needed).  Returns the file size."""
+        err = C.create_string_buffer(512)
+        n = self.L.gpc_host_save_model_quantized(self.h, os.fsencode(path), float(max_mse_depth), float(max_mse_rgb), int(bits_min),
+                                                 int(bits_max), C.addressof(err), 512)
+        if n < 0:
+            raise RuntimeError(f"save_model_quantized failed: {err.value.decode()}")
         return int(n)
 
     def prune(self, keep_depth, keep_rgb, tol_depth=0.0, tol_rgb=0.0):

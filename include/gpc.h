@@ -435,6 +435,51 @@ int gpc_sparse_prune_rd(gpc_sparse* g, const int32_t* off, const double* x0, con
 int gpc_sparse_prune_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
                             const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order,
                             double* scores, double* mse, double* mse0, double* mse_next, int32_t* status);
+/* Rate control by precision: the fewest bits per coefficient whose error stays within the patch's bound.  Pruning decides how many
+ * coefficients a leaf keeps, this call how precisely each is stored.  NOT in place: g is only read.  The batch (off, x0, x1, y in ny
+ * planes, n_total) and the error mse(alpha, BV, b) -- definition and summation order -- are those of gpc_sparse_prune_rd.
+ * The scalar quantiser, for an array v[0..b) of finite doubles and a width w in 1..16 (one definition for the kernels and the host,
+ * csrc/gpc_device.h):
+ *     lo = (double)(float) of min v rounded toward -inf;  hi = (double)(float) of max v rounded toward +inf     (independent of w)
+ *     step = (hi - lo) / (double)(2^w - 1)
+ *     q_i = step > 0 ? clamp(rint((v_i - lo) / step), 0, 2^w - 1) : 0          (rint: round-half-even)
+ *     v'_i = lo + (double)q_i * step                                            (every operation rounded once, no FMA)
+ * A patch's ny + 2 arrays are quantised separately at ONE width: BV column 0, BV column 1, then the alpha planes.
+ * Per patch, with b its basis count (clamped to ld), n = off[p+1] - off[p] and B = max_mse_p ? max_mse_p[p] : max_mse:
+ *     mse0[p] = mse(current state)                  (n == 0: NaN);  status[p] = the object's sticky status
+ *     the patch ESCAPES if b == 0, n == 0 or any of its b (ny + 2) values is not finite: bits[p] = 0, mse_q[p] = NaN, and nothing else
+ *     of the patch is written -- the caller stores such a leaf raw
+ *     otherwise range[p] is written, and for w = bits_min .. bits_max ascending:
+ *       e = mse(alpha', BV', b) with every array quantised at w, the state's index order unchanged;  curve[p][w-1] = e
+ *       if e <= B: bits[p] = w, mse_q[p] = e, the codes of this width go to q_alpha[p] / q_bv[p] (entries at and beyond b are left as
+ *       they were); stop                             (a NaN e or a NaN B compares false)
+ *     no width accepted: bits[p] = 0, mse_q[p] = NaN (range and the evaluated curve entries are written)
+ * Outputs, each may be NULL: bits [P], q_alpha [P][ny][ld] and q_bv [P][ld][2] uint16, range [P][ny+2][2] float (rows in the array
+ * order above, each (lo, hi)), mse0, mse_q [P], curve [P][16] (entries of widths not evaluated are left as they were), status [P].
+ *   - The FIRST accepted width wins.  The error is not monotone in w (a coarser grid can happen to fit better), and the call does not
+ *     search further.
+ *   - max_mse = 0 evaluates every width of bits_min .. bits_max and so yields the whole rate-distortion curve (on noisy data).
+ *   - max_mse = +inf accepts bits_min.
+ *   - The same inputs give the same bits in every workgroup shape; there are no atomics.
+ * GPC_EINVAL: a NULL or dead object; bits_min < 1, bits_max > 16 or bits_min > bits_max; max_mse NaN or negative with max_mse_p == NULL;
+ * n_total < 0; NULL off with P > 0; NULL x0, x1 or y with n_total > 0; an object whose noise_model is not 0.  P == 0: GPC_OK.
+ * gpc_sparse_quantize_rd_dev takes DEVICE pointers, enqueues on the context's stream and never synchronises; gpc_sparse_quantize_rd
+ * takes HOST pointers (n_total = off[P]) and is synchronous. */
+int gpc_sparse_quantize_rd(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y, int bits_min, int bits_max,
+                           double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha, uint16_t* q_bv, float* range,
+                           double* mse0, double* mse_q, double* curve, int32_t* status);
+int gpc_sparse_quantize_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
+                               int bits_min, int bits_max, double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha,
+                               uint16_t* q_bv, float* range, double* mse0, double* mse_q, double* curve, int32_t* status);
+/* The decoder.  For every patch with bits[p] in 1..16: alpha and BV become the dequantised values v' of the codes (layouts and range as
+ * above; entries at and beyond bv_count[p] are zero), the basis count becomes bv_count[p], and C and Q are zeroed -- the patch is as
+ * gpc_sparse_set_state with NULL C and Q leaves it.  A patch with bits[p] == 0 is not touched: load the raw leaves with
+ * gpc_sparse_set_state first.  GPC_EINVAL: a NULL or dead object; a NULL array with P > 0; in the host form a count outside 0..ld or
+ * a width outside 0..16 (the _dev form clamps both).  P == 0: GPC_OK.  _dev: DEVICE pointers, the context's stream, no synchronisation. */
+int gpc_sparse_dequantize(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
+                          const float* range);
+int gpc_sparse_dequantize_dev(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
+                              const float* range);
 
 /* ---- hyper-parameter training: the live part of sparse_gp::train_parameters ---------------- */
 /* src/sparse_gp.hpp:586-640 up to the exit(0) at :640 (the call site is commented out upstream, src/gp_compressor.cpp:161):
@@ -767,6 +812,9 @@ void gpc_test_exp_host(const double* x, double* out, int n);
 /* Same for the small-argument polynomial (-2^-5 <= x <= 0) the register-tile kernel switches to when the patch extent
  * proves the range. */
 void gpc_test_exp_small_host(const double* x, double* out, int n);
+/* Host-side evaluation of the scalar quantiser of gpc_sparse_quantize_rd (same source) on one array v[0..b) at width w: the codes
+ * q [b], range = (lo, hi) and the dequantised values deq [b]; each output may be NULL.  GPC_EINVAL: NULL v, b < 1, w outside 1..16. */
+int gpc_test_quantize_host(const double* v, int b, int w, uint16_t* q, float* range, double* deq);
 /* the multi-threaded staging copy of the host-pointer entries (pageable caller buffers), callable without a GPU: concurrency test */
 void gpc_test_par_memcpy(void* dst, const void* src, size_t bytes);
 /* The rule that chooses the kernels of a dense batch, callable without a GPU.  The facts of the batch: its sizes, whether the
