@@ -133,6 +133,8 @@ PROTOTYPES = {
     "gpc_sparse_quantize_rd_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _d, _vp] + [_vp] * 8),
     "gpc_sparse_dequantize": (C.c_int, [_vp] * 6),
     "gpc_sparse_dequantize_dev": (C.c_int, [_vp] * 6),
+    "gpc_rate_allocate": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, C.c_int64, _i, _vp, _vp, _vp, _vp]),
+    "gpc_rate_allocate_dev": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, C.c_int64, _i, _vp, _vp, _vp, _vp]),
     "gpc_reproject": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_reproject_dev": (C.c_int, [_vp, _i, _i] + [_vp] * 10),
     "gpc_project_cloud": (C.c_int, [_vp, _vp, _i, _d, _i, C.POINTER(_vp)]),
@@ -179,6 +181,7 @@ PROTOTYPES = {
     "gpc_test_exp_host": (None, [_vp, _vp, _i]),
     "gpc_test_exp_small_host": (None, [_vp, _vp, _i]),
     "gpc_test_quantize_host": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp]),
+    "gpc_test_rate_allocate_host": (C.c_int, [_i, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, C.c_int64, _i, _vp, _vp, _vp, _vp]),
     "gpc_test_par_memcpy": (None, [_vp, _vp, C.c_size_t]),
     "gpc_test_dense_route": (C.c_int, [_i] * 11 + [_vp, _i, _vp]),
 }
@@ -315,6 +318,28 @@ class Context:
         p = getattr(self, "_pinned", {}).pop(a.ctypes.data, None)
         if p is not None:
             self._check(self.lib.gpc_host_free(self.h, p))
+
+    def rate_allocate(self, kmax, d0, d, need, w=None, w_all=1.0, unit=None, unit_all=24, refine=True, count=None):
+        """gpc_rate_allocate (host arrays): how many removals each of the R rows takes -- kmax (R,) int32 options, errors d0 (R,) and
+        d (R, ld), weights w (R,) or w_all, bytes per removal unit (R,) int32 or unit_all -- so that at least `need` bytes are saved at
+        the smallest total weighted error.  Returns (k (R,) int32, result) and, with count (R,) int32, (k, target, result): target =
+        max(1, count - k); result: dict of lambda, lambda_bits, saved, max_saving, feasible, switched_rows."""
+        a = _rate_args(kmax, d0, d, w, unit, count)
+        R, ld = a[2].shape
+        k = np.zeros(R, dtype=np.int32)
+        tg = None if count is None else np.zeros(R, dtype=np.int32)
+        res = np.zeros(1, dtype=RATE_RESULT_DTYPE)
+        self._check(self.lib.gpc_rate_allocate(self.h, R, ld, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), float(w_all), _ptr(a[4]),
+                                               int(unit_all), int(need), int(bool(refine)), _ptr(a[5]), _ptr(k), _ptr(tg), _ptr(res)))
+        return (k, rate_result(res)) if count is None else (k, tg, rate_result(res))
+
+    def rate_allocate_dev(self, R, ld, kmax, d0, d, need, w=None, w_all=1.0, unit=None, unit_all=24, refine=True, count=None, k=None,
+                          target=None, result=None):
+        """gpc_rate_allocate_dev: device buffers (w, unit, count and each output may be None; result: 32 bytes, rate_result() reads
+        them), enqueued on the context's stream"""
+        self._check(self.lib.gpc_rate_allocate_dev(self.h, int(R), int(ld), _ptr(kmax), _ptr(d0), _ptr(d), _ptr(w), float(w_all),
+                                                   _ptr(unit), int(unit_all), int(need), int(bool(refine)), _ptr(count), _ptr(k),
+                                                   _ptr(target), _ptr(result)))
 
     def last_dense_kernel(self):
         return self.lib.gpc_last_dense_kernel(self.h).decode()
@@ -961,6 +986,56 @@ class Sparse:
         """gpc_sparse_dequantize_dev: device buffers, enqueued on the context's stream"""
         self.ctx._check(self.lib.gpc_sparse_dequantize_dev(self.h, _ptr(bv_count), _ptr(bits), _ptr(q_alpha), _ptr(q_bv), _ptr(range)))
 
+    def rd_curves_dev(self, off, n_total, x0, x1, y):
+        """Every patch's whole rate-distortion curve, the object untouched: prune_rd_dev(keep=1, max_mse=inf) on an identity remap copy.
+        Device batch as prune_rd_dev takes it.  Returns device tensors removed (P,) int32, mse0 (P,), mse (P, ld) -- NaN beyond
+        removed[p]; enqueued, not synchronised."""
+        import torch
+        P, ld = self.P, self.ld()
+        removed = torch.zeros(max(P, 1), dtype=torch.int32, device="cuda")
+        mse0 = torch.full((max(P, 1),), float("nan"), dtype=torch.float64, device="cuda")
+        mse = torch.full((max(P, 1), ld), float("nan"), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize(mse.device)
+        cp = self.remap(P, np.arange(P, dtype=np.int32))
+        try:
+            cp.prune_rd_dev(off, n_total, x0, x1, y, keep=1, max_mse=float("inf"), removed=removed, mse=mse, mse0=mse0)
+            self.ctx.synchronize()
+        finally:
+            cp.close()
+        return removed, mse0, mse
+
+    def prune_to_bytes(self, off, x0, x1, y, need, weight=None, refine=True):
+        """Rate control to a byte budget: save at least `need` bytes of the model file (24 bytes per vector with ny = 1, 40 with ny = 3)
+        by the removals that raise sum_p weight[p] n_p ny mse_p least.  The batch is prune_rd's (host arrays, or device tensors);
+        weight (P,) defaults to 1.  The curves come from an identity remap copy, the allocation from Context.rate_allocate_dev, and the
+        object itself is then pruned in place to b - k per patch (prune_dev(target=..., score_tol=0) replays the first k removals of
+        the curve's chain).  Returns (k (P,) int32, result); an infeasible `need` prunes to choice(+inf) and reports feasible = 0."""
+        import torch
+
+        def dev(a, dt):
+            return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to("cuda")
+        off_h = off.cpu().numpy() if torch.is_tensor(off) else np.ascontiguousarray(off, dtype=np.int32)
+        P, ld = self.P, self.ld()
+        assert off_h.shape == (P + 1,)
+        k = np.zeros(P, dtype=np.int32)
+        if P == 0:
+            return k, rate_result(np.zeros(1, dtype=RATE_RESULT_DTYPE))
+        n_p = np.diff(off_h).astype(np.float64)
+        wt = np.ones(P) if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        assert wt.shape == (P,)
+        d_off, d_x0, d_x1, d_y = dev(off, np.int32), dev(x0, np.float64), dev(x1, np.float64), dev(y, np.float64)
+        d_w = torch.from_numpy(wt * n_p * float(self.ny)).to("cuda")
+        d_count = torch.from_numpy(self.sizes()).to("cuda")
+        d_k = torch.zeros(P, dtype=torch.int32, device="cuda")
+        d_target = torch.zeros(P, dtype=torch.int32, device="cuda")
+        d_res = torch.zeros(RATE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        removed, mse0, mse = self.rd_curves_dev(d_off, int(off_h[-1]), d_x0, d_x1, d_y)    # (synchronises: the buffers above are ready)
+        self.ctx.rate_allocate_dev(P, ld, removed, mse0, mse, int(need), w=d_w, unit_all=24 if self.ny == 1 else 40, refine=refine,
+                                   count=d_count, k=d_k, target=d_target, result=d_res)
+        self.prune_dev(target=d_target, score_tol=0.0)
+        self.ctx.synchronize()
+        return d_k.cpu().numpy(), rate_result(d_res)
+
     def sizes(self):
         b = np.zeros(self.P, dtype=np.int32)
         self.ctx._check(self.lib.gpc_sparse_sizes(self.h, _ptr(b)))
@@ -1137,6 +1212,51 @@ class Mapping:
         out = rm.cpu().numpy()
         return out[0, :v.P], out[1, :v.P]
 
+    def prune_to_bytes(self, need, w_depth=0.0, w_rgb=0.0):
+        """Bound the map by size: save at least `need` bytes of its model (24 bytes per depth vector, 40 per colour vector) in ONE
+        allocation over the 2 P rows of both GPs, depth then colour, on the curves of the map's current batch (Sparse.rd_curves_dev).
+        A row's weight is w_g n_p ny; w_depth / w_rgb = 0 means normalise: w_g = 1 / sum_p n_p ny mse0_p of that GP, summed in
+        ascending leaf order, so that the objective is the sum of the two relative total errors.  Leaves the last scan did not touch
+        have no error there (d0 = NaN) and stay as they are.  Both objects are pruned in place.  Returns (k_depth, k_rgb, result)."""
+        import torch
+        v = self.patches.view
+        P = v.P
+        if P == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), rate_result(np.zeros(1, dtype=RATE_RESULT_DTYPE))
+        off_h = np.zeros(P + 1, dtype=np.int32)
+        self.ctx._check(self.ctx.lib.gpc_dev_memcpy(self.ctx.h, _ptr(off_h), v.off, off_h.nbytes, 2))
+        n_p = np.diff(off_h).astype(np.float64)
+        gps = ((self.depth, v.y, float(w_depth)), (self.rgb, v.rgb, float(w_rgb)))
+        ld = max(g.ld() for g, _, _ in gps)
+        kmax = torch.zeros(2 * P, dtype=torch.int32, device="cuda")
+        d0 = torch.full((2 * P,), float("nan"), dtype=torch.float64, device="cuda")
+        d = torch.full((2 * P, ld), float("nan"), dtype=torch.float64, device="cuda")
+        w = np.zeros(2 * P)
+        for i, (g, y, wg) in enumerate(gps):
+            removed, mse0, mse = g.rd_curves_dev(v.off, v.n_total, v.x0, v.x1, y)
+            kmax[i * P:(i + 1) * P], d0[i * P:(i + 1) * P], d[i * P:(i + 1) * P, :g.ld()] = removed[:P], mse0[:P], mse[:P]
+            if wg == 0.0:
+                total = 0.0
+                for n, e in zip(n_p, mse0[:P].cpu().numpy()):
+                    if n > 0 and np.isfinite(e):
+                        total += n * float(g.ny) * float(e)
+                wg = 1.0 / total if total > 0.0 and np.isfinite(total) else 1.0
+            w[i * P:(i + 1) * P] = wg * n_p * float(g.ny)
+        d_w = torch.from_numpy(w).to("cuda")
+        d_unit = torch.from_numpy(np.repeat(np.array([24, 40], dtype=np.int32), P)).to("cuda")
+        d_count = torch.from_numpy(np.concatenate([self.depth.sizes(), self.rgb.sizes()])).to("cuda")
+        d_k = torch.zeros(2 * P, dtype=torch.int32, device="cuda")
+        d_target = torch.zeros(2 * P, dtype=torch.int32, device="cuda")
+        d_res = torch.zeros(RATE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize(d_res.device)
+        self.ctx.rate_allocate_dev(2 * P, ld, kmax, d0, d, int(need), w=d_w, unit=d_unit, count=d_count, k=d_k, target=d_target,
+                                   result=d_res)
+        self.depth.prune_dev(target=d_target[:P], score_tol=0.0)
+        self.rgb.prune_dev(target=d_target[P:], score_tol=0.0)
+        self.ctx.synchronize()
+        k = d_k.cpu().numpy()
+        return k[:P], k[P:], rate_result(d_res)
+
     def render(self, origin, dirs, params=None, use_cells=True, want=("leaf", "range", "local")):
         """The map as a sensor at `origin` sees it along `dirs` (Context.camera_rays, or any (n, 3) float64 device tensor): Patches.render
         on the map's current batch, depth and colour GPs; use_cells: cells a scan saw through (CELL_FREE) do not stop a ray."""
@@ -1285,6 +1405,48 @@ def test_quantize_host(v, w):
 
 
 test_quantize_host.__test__ = False      # (a library call, not a pytest case)
+
+# struct gpc_rate_result (include/gpc.h), 32 bytes
+RATE_RESULT_DTYPE = np.dtype([("lambda", "<f8"), ("saved", "<i8"), ("max_saving", "<i8"), ("feasible", "<i4"), ("switched_rows", "<i4")])
+
+
+def rate_result(buf):
+    """a gpc_rate_result -- a RATE_RESULT_DTYPE array, or 32 bytes as a uint8 tensor / array -- as a dict, with the multiplier's bits"""
+    if hasattr(buf, "cpu"):
+        buf = buf.cpu().numpy()
+    r = np.ascontiguousarray(buf).view(RATE_RESULT_DTYPE).ravel()[0]
+    return dict(lambda_bits=int(np.array(r["lambda"]).view(np.uint64)), **{"lambda": float(r["lambda"])}, saved=int(r["saved"]),
+                max_saving=int(r["max_saving"]), feasible=int(r["feasible"]), switched_rows=int(r["switched_rows"]))
+
+
+def _rate_args(kmax, d0, d, w, unit, count):
+    """the host arrays of a rate allocation in the types the C entries read, shapes checked"""
+    kmax = np.ascontiguousarray(kmax, dtype=np.int32)
+    d0 = np.ascontiguousarray(d0, dtype=np.float64)
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    assert d.ndim == 2 and kmax.shape == d0.shape == (d.shape[0],)
+    w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+    unit = None if unit is None else np.ascontiguousarray(unit, dtype=np.int32)
+    count = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+    assert all(a is None or a.shape == kmax.shape for a in (w, unit, count))
+    return kmax, d0, d, w, unit, count
+
+
+def test_rate_allocate_host(kmax, d0, d, need, w=None, w_all=1.0, unit=None, unit_all=24, refine=True, count=None):
+    """gpc_test_rate_allocate_host: Context.rate_allocate's rule from the same source on the CPU, no context and no device"""
+    a = _rate_args(kmax, d0, d, w, unit, count)
+    R, ld = a[2].shape
+    k = np.zeros(R, dtype=np.int32)
+    tg = None if count is None else np.zeros(R, dtype=np.int32)
+    res = np.zeros(1, dtype=RATE_RESULT_DTYPE)
+    rc = load().gpc_test_rate_allocate_host(R, ld, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), float(w_all), _ptr(a[4]), int(unit_all),
+                                            int(need), int(bool(refine)), _ptr(a[5]), _ptr(k), _ptr(tg), _ptr(res))
+    if rc != GPC_OK:
+        raise GpcError(rc, "gpc_test_rate_allocate_host")
+    return (k, rate_result(res)) if count is None else (k, tg, rate_result(res))
+
+
+test_rate_allocate_host.__test__ = False
 
 
 ROUTE_KINDS = {-1: "no route", 0: "nothing", 1: "one-wave", 2: "register", 3: "tiled", 4: "generic", 5: "split"}

@@ -201,6 +201,129 @@ __host__ __device__ static inline double gpc_q_value(uint16_t q, float lo, doubl
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The allocation rule of the byte budget (include/gpc.h, gpc_rate_allocate): one definition for the kernels (rate_alloc.hip) and the host
+// (gpc_test_rate_allocate_host).  Row r offers k = 0 .. kmax removals; the cost of an option at the multiplier lambda is
+//     c(k) = w e(k) + (rate(k) == 0 ? 0.0 : lambda (double)rate(k)),     rate(k) = unit (kmax - k)  (int64)
+// with the product and the sum rounded once each (contraction off).  The choice is the largest k that attains the minimum over the options
+// whose cost is not NaN (0 for a row whose c(0) is NaN): gpc_ra_take is that order, so a sequential scan and any reduction tree agree.
+// ---------------------------------------------------------------------------------------------------------
+#define GPC_RA_UNDECIDED 0
+#define GPC_RA_INFEASIBLE 1    // S(+inf) < need
+#define GPC_RA_FREE 2          // S(0) >= need
+#define GPC_RA_BISECT 3
+
+// which multiplier an evaluation sweep uses, and which total of the state it adds to
+#define GPC_RA_AT_INF 0
+#define GPC_RA_AT_ZERO 1
+#define GPC_RA_AT_MID 2
+#define GPC_RA_AT_HI 3         // the final multiplier: k_hi
+#define GPC_RA_AT_LO 4         // the bracket's lower end (refinement; else the final multiplier again): k_lo
+
+// the bracket and the totals of one call (device memory in the _dev entry: no sweep's launch depends on a value read back)
+struct gpc_ra_state {
+    unsigned long long lo, hi;          // bit patterns of the bracket's ends
+    long long need;
+    long long s[5];                     // S at the multiplier of each GPC_RA_AT_*; s[GPC_RA_AT_MID] is cleared after every sweep
+    long long saved_ref;                // the saving of the refined choice
+    int mode, refine;
+    int switched_ref, switched_all;     // rows with k != k_lo under the refined choice / under k_hi
+    int fallback;                       // the refined choice missed `need`: k = k_hi
+};
+
+__host__ __device__ static inline double gpc_ra_from_bits(unsigned long long b)
+{
+    double v;
+    __builtin_memcpy(&v, &b, sizeof v);
+    return v;
+}
+
+__host__ __device__ static inline int gpc_ra_kmax(int kmax, int ld) { return kmax < 0 ? 0 : (kmax > ld ? ld : kmax); }
+__host__ __device__ static inline int gpc_ra_unit(const int32_t* unit, int unit_all, int r)
+{
+    const int u = unit ? unit[r] : unit_all;
+    return u < 1 ? 1 : u;
+}
+
+__host__ __device__ static inline double gpc_ra_cost(double w, double e, long long rate, double lambda)
+{
+#pragma clang fp contract(off)
+    const double D = w * e;
+    const double t = rate == 0 ? 0.0 : lambda * (double)rate;
+    return D + t;
+}
+
+// does option (c, k) replace the best so far (cb, kb)?  kb < 0: there is none yet.  c is not NaN.
+__host__ __device__ static inline bool gpc_ra_take(double c, int k, double cb, int kb)
+{
+    return kb < 0 || c < cb || (c == cb && k > kb);
+}
+
+// the row's choice by the sequential scan (the host twin; the kernel strides the options over a wave and merges with gpc_ra_take)
+__host__ __device__ static inline int gpc_ra_choice(int kmax, double d0, const double* d, double w, int unit, double lambda)
+{
+    const double c0 = gpc_ra_cost(w, d0, (long long)unit * kmax, lambda);
+    if (c0 != c0) return 0;
+    double cb = c0;
+    int kb = 0;
+    for (int k = 1; k <= kmax; ++k) {
+        const double c = gpc_ra_cost(w, d[k - 1], (long long)unit * (kmax - k), lambda);
+        if (c == c && gpc_ra_take(c, k, cb, kb)) { cb = c; kb = k; }
+    }
+    return kb;
+}
+
+__host__ __device__ static inline void gpc_ra_init(gpc_ra_state* s, long long need, int refine)
+{
+    s->lo = 0ull;                       // bits(0.0)
+    s->hi = 0x7ff0000000000000ull;      // bits(+inf)
+    s->need = need;
+    for (int i = 0; i < 5; ++i) s->s[i] = 0;
+    s->saved_ref = 0;
+    s->mode = GPC_RA_UNDECIDED;
+    s->refine = refine != 0;
+    s->switched_ref = s->switched_all = s->fallback = 0;
+}
+
+// is the sweep `at` still to be done, and at which multiplier?
+__host__ __device__ static inline bool gpc_ra_sweep(const gpc_ra_state* s, int at, double* lambda)
+{
+    const double inf = gpc_ra_from_bits(0x7ff0000000000000ull);
+    switch (at) {
+    case GPC_RA_AT_INF: *lambda = inf; return true;
+    case GPC_RA_AT_ZERO: *lambda = 0.0; return true;
+    case GPC_RA_AT_MID:
+        if (s->mode != GPC_RA_BISECT || s->hi - s->lo <= 1ull) return false;
+        *lambda = gpc_ra_from_bits(s->lo + (s->hi - s->lo) / 2ull);
+        return true;
+    default: {
+        const double fin = s->mode == GPC_RA_INFEASIBLE ? inf : (s->mode == GPC_RA_FREE ? 0.0 : gpc_ra_from_bits(s->hi));
+        *lambda = (at == GPC_RA_AT_LO && s->mode == GPC_RA_BISECT && s->refine) ? gpc_ra_from_bits(s->lo) : fin;
+        return true;
+    }
+    }
+}
+
+// after the two end points: which case is it?
+__host__ __device__ static inline void gpc_ra_decide(gpc_ra_state* s)
+{
+    s->mode = s->s[GPC_RA_AT_INF] < s->need ? GPC_RA_INFEASIBLE : (s->s[GPC_RA_AT_ZERO] >= s->need ? GPC_RA_FREE : GPC_RA_BISECT);
+}
+
+// after a sweep at mid: move one end (a no-op once the bracket has closed, or outside the bisection)
+__host__ __device__ static inline void gpc_ra_update(gpc_ra_state* s)
+{
+    if (s->mode == GPC_RA_BISECT && s->hi - s->lo > 1ull) {
+        const unsigned long long mid = s->lo + (s->hi - s->lo) / 2ull;
+        if (s->s[GPC_RA_AT_MID] >= s->need) s->hi = mid;
+        else s->lo = mid;
+    }
+    s->s[GPC_RA_AT_MID] = 0;
+}
+
+// the row's final count from the exclusive scan E of unit (k_hi - k_lo), started at S(lo)
+__host__ __device__ static inline int gpc_ra_pick(long long E, long long need, int k_hi, int k_lo) { return E < need ? k_hi : k_lo; }
+
+// ---------------------------------------------------------------------------------------------------------
 // wave / block reductions
 // ---------------------------------------------------------------------------------------------------------
 __device__ static inline double gpc_wave_sum(double v)

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -1126,6 +1127,83 @@ std::array<long long, 2> gp_compressor::prune_to_error(double max_mse_depth, dou
     return total;
 }
 
+size_t gp_compressor::model_bytes() const
+{
+    if (model_ != gp_model::sparse) throw std::runtime_error("model_bytes: the sparse model only");
+    if (!devices_.empty()) throw std::runtime_error("model_bytes: the single-device flow only (the sharded states live on their devices)");
+    if (!trained_) throw std::runtime_error("model_bytes: the object is not trained yet");
+    const int P = batch_.patches();
+    size_t bytes = 4 + sizeof(uint32_t) + sizeof(double) + 2 * sizeof(int32_t) + sizeof(uint32_t) + 2 * sizeof(gpc_params);
+    if (P <= 0) return bytes;
+    std::vector<int32_t> bd((size_t)P), bc((size_t)P);
+    check(gpc_sparse_sizes(gps_, bd.data()), ctx_, "gpc_sparse_sizes");
+    check(gpc_sparse_sizes(rgb_gps_, bc.data()), ctx_, "gpc_sparse_sizes");
+    for (int i = 0; i < P; ++i) bytes += 15 * sizeof(double) + 2 * sizeof(int32_t) + (size_t)24 * bd[i] + (size_t)40 * bc[i];
+    return bytes;
+}
+
+std::array<long long, 2> gp_compressor::prune_to_bytes(size_t budget_bytes, double w_depth, double w_rgb)
+{
+    if (model_ != gp_model::sparse) throw std::runtime_error("prune_to_bytes: the sparse model only");
+    if (!devices_.empty()) throw std::runtime_error("prune_to_bytes: the single-device flow only (the sharded states live on their devices)");
+    if (loaded_) throw std::runtime_error("prune_to_bytes: a loaded model holds (BV, alpha) only; prune the trained object before save_model");
+    if (!(w_depth >= 0.0) || !(w_rgb >= 0.0)) throw std::runtime_error("prune_to_bytes: the weights must be >= 0 (0: normalise)");
+    if (!trained_) { project_cloud(); train_processes(); }
+    const int P = batch_.patches();
+    std::array<long long, 2> total = {0, 0};
+    const size_t now = model_bytes();
+    if (P <= 0) {
+        if (budget_bytes < now) throw std::runtime_error("prune_to_bytes: the budget is below the floor of " + std::to_string(now) + " bytes");
+        return total;
+    }
+    const long long need = (long long)now - (long long)budget_bytes;
+    gpc_sparse* const gp[2] = {gps_, rgb_gps_};
+    const double* const ys[2] = {batch_.y.data(), batch_.rgb.data()};
+    const int ny[2] = {1, 3}, unit_of[2] = {24, 40}, ldg[2] = {gpc_sparse_ld(gps_), gpc_sparse_ld(rgb_gps_)};
+    const double wg[2] = {w_depth, w_rgb};
+    const int ld = std::max(ldg[0], ldg[1]);
+    const size_t R = (size_t)2 * P;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<int32_t> kmax(R, 0), unit(R), count(R), k(R), target(R), ident((size_t)P);
+    std::vector<double> d0(R, nan), d(R * (size_t)ld, nan), w(R);
+    for (int i = 0; i < P; ++i) ident[i] = i;
+    for (int g = 0; g < 2; ++g) {
+        // the curves: every removal of the chain with its error, on a copy
+        gpc_sparse* cp = nullptr;
+        check(gpc_sparse_remap(gp[g], P, ident.data(), &cp), ctx_, "gpc_sparse_remap");
+        std::vector<double> mse((size_t)P * ldg[g], nan);
+        const int rc = gpc_sparse_prune_rd(cp, batch_.off.data(), batch_.x0.data(), batch_.x1.data(), ys[g], 1, nullptr,
+                                           std::numeric_limits<double>::infinity(), nullptr, &kmax[(size_t)g * P], nullptr, nullptr, mse.data(),
+                                           &d0[(size_t)g * P], nullptr, nullptr);
+        gpc_sparse_destroy(cp);
+        check(rc, ctx_, "gpc_sparse_prune_rd (curves)");
+        check(gpc_sparse_sizes(gp[g], &count[(size_t)g * P]), ctx_, "gpc_sparse_sizes");
+        double sum = 0.0;                       // sum_p n_p ny mse0_p in ascending leaf order
+        for (int i = 0; i < P; ++i) {
+            const size_t r = (size_t)g * P + i;
+            std::memcpy(&d[r * ld], &mse[(size_t)i * ldg[g]], sizeof(double) * ldg[g]);
+            unit[r] = unit_of[g];
+            const double n = (double)(batch_.off[i + 1] - batch_.off[i]);
+            if (n > 0 && std::isfinite(d0[r])) sum += n * (double)ny[g] * d0[r];
+        }
+        const double scale = wg[g] != 0.0 ? wg[g] : ((sum > 0.0 && std::isfinite(sum)) ? 1.0 / sum : 1.0);
+        for (int i = 0; i < P; ++i) w[(size_t)g * P + i] = scale * (double)(batch_.off[i + 1] - batch_.off[i]) * (double)ny[g];
+    }
+    gpc_rate_result res = {};
+    check(gpc_rate_allocate(ctx_, (int)R, ld, kmax.data(), d0.data(), d.data(), w.data(), 0.0, unit.data(), 0, (int64_t)need, 1, count.data(),
+                            k.data(), target.data(), &res),
+          ctx_, "gpc_rate_allocate");
+    if (!res.feasible)
+        throw std::runtime_error("prune_to_bytes: a budget of " + std::to_string(budget_bytes) + " bytes is below the floor of " +
+                                 std::to_string((long long)now - (long long)res.max_saving) + " bytes (the model holds " + std::to_string(now) + ")");
+    std::vector<int32_t> removed(R);
+    for (int g = 0; g < 2; ++g)
+        check(gpc_sparse_prune(gp[g], 0, &target[(size_t)g * P], 0.0, &removed[(size_t)g * P], nullptr, nullptr, nullptr), ctx_, "gpc_sparse_prune");
+    for (int g = 0; g < 2; ++g)
+        for (int i = 0; i < P; ++i) total[g] += removed[(size_t)g * P + i];
+    return total;
+}
+
 }  // namespace gpc
 
 // ---- C doors for the Python test-suite -----------------------------------------------------------------------------
@@ -1279,6 +1357,27 @@ int gpc_host_prune_to_error(void* h, double max_mse_depth, double max_mse_rgb, i
 {
     try {
         const auto r = static_cast<gpc::gp_compressor*>(h)->prune_to_error(max_mse_depth, max_mse_rgb, keep_depth, keep_rgb);
+        if (removed) { removed[0] = r[0]; removed[1] = r[1]; }
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// the exact size of the file save_model would write now: gp_compressor::model_bytes.  Bytes, or < 0 on error.
+long long gpc_host_model_bytes(void* h, char* err, int errlen)
+{
+    try {
+        return (long long)static_cast<gpc::gp_compressor*>(h)->model_bytes();
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// rate control to a byte budget: gp_compressor::prune_to_bytes (trains first if needed); removed[2] as above.  0, or < 0 on error.
+int gpc_host_prune_to_bytes(void* h, long long budget_bytes, double w_depth, double w_rgb, long long removed[2], char* err, int errlen)
+{
+    try {
+        if (budget_bytes < 0) throw std::runtime_error("prune_to_bytes: a negative budget");
+        const auto r = static_cast<gpc::gp_compressor*>(h)->prune_to_bytes((size_t)budget_bytes, w_depth, w_rgb);
         if (removed) { removed[0] = r[0]; removed[1] = r[1]; }
         return 0;
     } catch (const std::exception& e) {

@@ -97,6 +97,17 @@ public:
     // object itself is not modified; load_model() reads both versions.  Trains first if needed.  Same preconditions and exceptions as
     // prune_to_error(); an argument gpc_sparse_quantize_rd refuses throws.  Returns the number of bytes written.
     size_t save_model_quantized(const std::string& path, double max_mse_depth, double max_mse_rgb, int bits_min = 1, int bits_max = 16);
+    // The exact size of the file save_model() would write for the object as it stands: the header, per leaf 15 doubles and 2 int32, and
+    // 24 bytes per depth vector, 40 per colour vector.  A trained (or loaded) sparse model of the single-device flow; anything else throws.
+    size_t model_bytes() const;
+    // Rate control to a byte budget: make the model fit in budget_bytes and spend the bytes where they buy the most.  need =
+    // model_bytes() - budget_bytes; every leaf's two rate-distortion curves on its own training points (gpc_sparse_prune_rd without a
+    // bound, on copies); ONE allocation over the 2 P rows, depth then colour (gpc_rate_allocate: it minimises the sum of weight x n_p x ny x
+    // mse_p); then both GPs are pruned in place to the allocated counts.  w_depth / w_rgb = 0 normalises that GP's rows by 1 / sum_p n_p ny
+    // mse0_p, so that the objective is the sum of the two relative total errors.  Same preconditions and exceptions as prune_to_error(); a
+    // budget below what the removals can reach throws, its message naming the floor, and leaves the object untouched.  save_model() then
+    // writes at most budget_bytes.  Returns the vectors removed {depth, colour}.
+    std::array<long long, 2> prune_to_bytes(size_t budget_bytes, double w_depth = 0, double w_rgb = 0);
 
     // host-only part, usable without a GPU
     void project_cloud();                            // src/gp_compressor.cpp:177-249

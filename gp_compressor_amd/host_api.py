@@ -50,6 +50,9 @@ def load():
         L.gpc_host_decompress_file.argtypes = [C.c_char_p, i, vp, vp, i, vp, i]
         L.gpc_host_prune.argtypes = [vp, i, i, d, d, vp, vp, i]
         L.gpc_host_prune_to_error.argtypes = [vp, d, d, i, i, vp, vp, i]
+        L.gpc_host_model_bytes.restype = C.c_longlong
+        L.gpc_host_model_bytes.argtypes = [vp, vp, i]
+        L.gpc_host_prune_to_bytes.argtypes = [vp, C.c_longlong, d, d, vp, vp, i]
         L.gpc_host_load_compressed.argtypes = [vp, vp, vp, i, vp, i]
         L.gpc_host_shard.argtypes = [vp, i, i, i] + [vp] * 12 + [i]
         L.gpc_host_shard_scatter.argtypes = [vp, i, i, i, vp, vp, vp, i]
@@ -188,6 +191,25 @@ class GpCompressor:
         if self.L.gpc_host_prune_to_error(self.h, float(max_mse_depth), float(max_mse_rgb), int(keep_depth), int(keep_rgb), rm.ctypes.data,
                                           C.addressof(err), 512) != 0:
             raise RuntimeError(f"prune_to_error failed: {err.value.decode()}")
+        return int(rm[0]), int(rm[1])
+
+    def model_bytes(self):
+        """gp_compressor::model_bytes: the exact size of the file save_model would write for the trained object as it stands"""
+        err = C.create_string_buffer(512)
+        n = self.L.gpc_host_model_bytes(self.h, C.addressof(err), 512)
+        if n < 0:
+            raise RuntimeError(f"model_bytes failed: {err.value.decode()}")
+        return int(n)
+
+    def prune_to_bytes(self, budget_bytes, w_depth=0.0, w_rgb=0.0):
+        """gp_compressor::prune_to_bytes: make the model fit in budget_bytes by one joint allocation of removals over every leaf's
+        depth and colour GP (a weight of 0 normalises that GP's errors by their total); in place (trains first if needed).  An
+        infeasible budget raises, naming the floor, and leaves the object as it was.  Returns (removed_depth, removed_rgb)."""
+        err = C.create_string_buffer(512)
+        rm = np.zeros(2, dtype=np.int64)
+        if self.L.gpc_host_prune_to_bytes(self.h, int(budget_bytes), float(w_depth), float(w_rgb), rm.ctypes.data, C.addressof(err),
+                                          512) != 0:
+            raise RuntimeError(f"prune_to_bytes failed: {err.value.decode()}")
         return int(rm[0]), int(rm[1])
 
     def load_compressed(self):

@@ -480,6 +480,53 @@ int gpc_sparse_dequantize(gpc_sparse* g, const int32_t* bv_count, const int32_t*
                           const float* range);
 int gpc_sparse_dequantize_dev(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
                               const float* range);
+/* Rate control to a byte budget: the allocator.  The calls above decide leaf by leaf; this one decides ACROSS rows -- a row is one GP of
+ * one leaf -- how many removals each takes, so that at least `need` bytes are saved and the total weighted error is smallest.  It only
+ * allocates: the curves come from gpc_sparse_prune_rd (max_mse = +inf on a gpc_sparse_remap identity copy: kmax = removed, d0 = mse0,
+ * d = mse), and gpc_sparse_prune_dev(target = b - k, score_tol = 0) replays exactly the first k removals of that chain.
+ * Row r of R has
+ *     kmax[r] >= 0 removals on its curve (clamped to 0 .. ld): the options are k = 0 .. kmax[r]
+ *     the error after k removals  e_r(k) = (k == 0 ? d0[r] : d[r * ld + k - 1])
+ *     a weight w[r] (w == NULL: w_all for every row) and unit[r] bytes saved per removal (unit == NULL: unit_all; entries < 1 count as 1)
+ * and, at a multiplier lambda >= 0 (one definition for the kernels and the host, csrc/gpc_device.h):
+ *     D(k) = w_r * e_r(k)                                                       (one rounded product)
+ *     rate(k) = unit_r * (kmax_r - k)                                           (int64)
+ *     c(k) = D(k) + (rate(k) == 0 ? 0.0 : lambda * (double)rate(k))             (product and sum rounded once each, no FMA)
+ *     choice_r(lambda) = 0 if c(0) is NaN (the row is fixed), else the LARGEST k that attains the minimum of c over the options whose
+ *       cost is not NaN -- the scan "k ascending, replace the best iff c(k) <= c(best)": ties go to fewer bytes, a NaN is never chosen
+ *     S(lambda) = sum_r unit_r * choice_r(lambda)                               (int64, exact: the order of the sum is free)
+ * Given `need` bytes to save:
+ *     S(+inf) < need:  INFEASIBLE.  k = choice(+inf), feasible = 0, lambda = +inf
+ *     S(0) >= need:    FREE (always so for need <= 0).  k = choice(0), feasible = 1, lambda = 0; it may remove vectors where a removal
+ *                      does not raise the error
+ *     otherwise bisect on the BIT PATTERN of lambda: lo = bits(0.0), hi = bits(+inf); while hi - lo > 1: mid = lo + (hi - lo) / 2,
+ *       hi = mid if S(double(mid)) >= need, else lo = mid.  At most 63 steps; the outcome is defined by this procedure, not by a
+ *       property of S.  lambda = double(hi), k_hi = choice(lambda), feasible = 1
+ *       refine == 0: k = k_hi
+ *       refine != 0: k_lo = choice(double(lo)), delta_r = unit_r (k_hi(r) - k_lo(r)), E_r = S(double(lo)) + sum_{q < r} delta_q (an int64
+ *         exclusive scan in ascending r), k(r) = E_r < need ? k_hi(r) : k_lo(r); if that saves less than need (only possible with a
+ *         negative delta), k = k_hi.  Rows whose curves tie at lambda are so switched in ascending row order only until the saving is
+ *         met: the overshoot is less than one row's step.
+ * Outputs (each may be NULL): k [R]; target [R] = max(1, count[r] - k[r]), ready for gpc_sparse_prune_dev (needs count [R], the rows'
+ * basis counts); and *result: lambda as above, saved = sum unit_r k(r), max_saving = S(+inf), feasible, switched_rows = the rows
+ * whose k differs from k_lo(r) (0 outside a refined bisection).
+ * GPC_EINVAL: a NULL or dead ctx; R < 0; ld < 1; NULL kmax, d0 or d with R > 0; w_all NaN or negative with w == NULL; unit_all < 1 with
+ * unit == NULL; target without count.  R == 0: GPC_OK, nothing is written.
+ * gpc_rate_allocate_dev takes DEVICE pointers (result too), enqueues a fixed sequence of launches on the context's stream -- the two end
+ * points, 63 sweeps that are no-ops once the bracket has closed, k_hi and k_lo, the scan, the write-out -- and never reads back or
+ * synchronises; scratch is the context's workspace.  The totals are integer atomics: the same inputs give the same bits in every
+ * grid shape.  gpc_rate_allocate takes HOST pointers and is synchronous. */
+typedef struct gpc_rate_result {
+    double lambda;
+    int64_t saved, max_saving;
+    int32_t feasible, switched_rows;
+} gpc_rate_result;
+int gpc_rate_allocate(gpc_ctx* ctx, int R, int ld, const int32_t* kmax, const double* d0, const double* d, const double* w, double w_all,
+                      const int32_t* unit, int unit_all, int64_t need, int refine, const int32_t* count, int32_t* k, int32_t* target,
+                      gpc_rate_result* result);
+int gpc_rate_allocate_dev(gpc_ctx* ctx, int R, int ld, const int32_t* kmax, const double* d0, const double* d, const double* w, double w_all,
+                          const int32_t* unit, int unit_all, int64_t need, int refine, const int32_t* count, int32_t* k, int32_t* target,
+                          gpc_rate_result* result);
 
 /* ---- hyper-parameter training: the live part of sparse_gp::train_parameters ---------------- */
 /* src/sparse_gp.hpp:586-640 up to the exit(0) at :640 (the call site is commented out upstream, src/gp_compressor.cpp:161):
@@ -815,6 +862,10 @@ void gpc_test_exp_small_host(const double* x, double* out, int n);
 /* Host-side evaluation of the scalar quantiser of gpc_sparse_quantize_rd (same source) on one array v[0..b) at width w: the codes
  * q [b], range = (lo, hi) and the dequantised values deq [b]; each output may be NULL.  GPC_EINVAL: NULL v, b < 1, w outside 1..16. */
 int gpc_test_quantize_host(const double* v, int b, int w, uint16_t* q, float* range, double* deq);
+/* gpc_rate_allocate on the CPU: the same rule from the same source, no context and no device (host pointers; GPC_EINVAL as there). */
+int gpc_test_rate_allocate_host(int R, int ld, const int32_t* kmax, const double* d0, const double* d, const double* w, double w_all,
+                                const int32_t* unit, int unit_all, int64_t need, int refine, const int32_t* count, int32_t* k, int32_t* target,
+                                gpc_rate_result* result);
 /* the multi-threaded staging copy of the host-pointer entries (pageable caller buffers), callable without a GPU: concurrency test */
 void gpc_test_par_memcpy(void* dst, const void* src, size_t bytes);
 /* The rule that chooses the kernels of a dense batch, callable without a GPU.  The facts of the batch: its sizes, whether the
