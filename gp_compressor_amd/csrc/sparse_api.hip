@@ -1,5 +1,5 @@
 // sparse_api.hip -- the gpc_sparse_* entry points of the C-ABI (include/gpc.h): the object, the _dev entries (argument checks,
-// locking, then the launcher beside the kernels: sparse.hip, sparse_predict.hip) and their host-pointer twins.
+// locking, then the launcher beside the kernels: sparse.hip, sparse_rate.hip, sparse_predict.hip) and their host-pointer twins.
 #include <new>
 
 #include "sparse_internal.h"

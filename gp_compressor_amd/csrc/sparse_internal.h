@@ -1,5 +1,6 @@
-// sparse_internal.h -- what the translation units of the sparse path share: sparse.hip (the add and prune kernels), sparse_predict.hip (the
-// predict / likelihood / train kernels) and sparse_api.hip (the gpc_sparse_* C-ABI).
+// sparse_internal.h -- what the translation units of the sparse path share: sparse.hip (the add kernels), sparse_rate.hip (the prune and
+// quantise kernels), sparse_predict.hip (the predict / likelihood / train kernels) and sparse_api.hip (the gpc_sparse_* C-ABI).  The
+// device helpers of the kernels that change the state are in sparse_device.h.
 #pragma once
 
 #include "gpc_device.h"
@@ -29,18 +30,20 @@ __device__ static __forceinline__ double sp_kstar(double sf, double x0, double x
 // sparse.hip: the phases of one add call
 int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, const int32_t* perm,
                   int32_t* status);
-// sparse.hip: gpc_sparse_prune_dev behind its argument checks (removed / order / scores / status may be nullptr; target == nullptr: keep)
+// sparse.hip: threads per patch (64, 128 or 256) of the add call's regular kernel and of every rate-control launch
+int sp_workgroup_threads(const gpc_sparse* g);
+// sparse_rate.hip: gpc_sparse_prune_dev behind its argument checks (removed / order / scores / status may be nullptr; target == nullptr: keep)
 int sp_prune_launch(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order, double* scores,
                     int32_t* status);
-// sparse.hip: gpc_sparse_prune_rd_dev behind its argument checks (every output may be nullptr; max_mse_p == nullptr: max_mse)
+// sparse_rate.hip: gpc_sparse_prune_rd_dev behind its argument checks (every output may be nullptr; max_mse_p == nullptr: max_mse)
 int sp_prune_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int keep,
                        const int32_t* target, double max_mse, const double* max_mse_p, int32_t* removed, int32_t* order, double* scores,
                        double* mse, double* mse0, double* mse_next, int32_t* status);
-// sparse.hip: gpc_sparse_quantize_rd_dev behind its argument checks (every output may be nullptr; max_mse_p == nullptr: max_mse)
+// sparse_rate.hip: gpc_sparse_quantize_rd_dev behind its argument checks (every output may be nullptr; max_mse_p == nullptr: max_mse)
 int sp_quantize_rd_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, int bits_min,
                           int bits_max, double max_mse, const double* max_mse_p, int32_t* bits, uint16_t* q_alpha, uint16_t* q_bv, float* range,
                           double* mse0, double* mse_q, double* curve, int32_t* status);
-// sparse.hip: gpc_sparse_dequantize_dev behind its argument checks (counts and widths are clamped by the kernel)
+// sparse_rate.hip: gpc_sparse_dequantize_dev behind its argument checks (counts and widths are clamped by the kernel)
 int sp_dequantize_launch(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
                          const float* range);
 // sparse_predict.hip.  off == nullptr: every patch at the shared grid xs0 / xs1 [m]; else patch i at its own points off[i] .. off[i+1]-1 of

@@ -58,7 +58,7 @@ def batch(cap, n, P, ny):
 # ---- the arg-min ------------------------------------------------------------------------------------------------------------------
 
 def sp_take(ov, oi, val, idx):
-    """SP_TAKE of csrc/sparse.hip: does (ov, oi) come before (val, idx) in the order in which the reference's scan picks its minimum --
+    """SP_TAKE of csrc/sparse_device.h: does (ov, oi) come before (val, idx) in the order in which the reference's scan picks its minimum --
     a NaN at index 0 first, then by value with NaN last, then by index"""
     nan0 = lambda v, i: i == 0 and v != v
     return bool(nan0(ov, oi) or (not nan0(val, idx) and (ov < val or (ov == val and oi < idx) or (val != val and ov == ov))))
