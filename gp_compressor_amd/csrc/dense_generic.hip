@@ -327,7 +327,7 @@ __global__ __launch_bounds__(GEN_THREADS) void dense_generic_kernel(GenParams g)
                         }
                     }
                 }
-                if (active) A.v_star[(size_t)patch * m + p] = sf - vv;   // k** = sigmaf_sq * exp(0)
+                if (active) A.v_star[(size_t)patch * m + p] = gpc_kss(sf, q0, q1) - vv;   // k** = sigmaf_sq * exp(0); NaN for a non-finite x*
             }
         }
         if (tid == 0 && A.status) A.status[patch] = GPC_STATUS_OK;

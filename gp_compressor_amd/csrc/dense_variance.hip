@@ -220,7 +220,9 @@ __global__ __launch_bounds__(64 * WV, 2) void dense_variance_kernel(VarParams g)
             fm[c] += __shfl_xor(fm[c], 32, 64);
         }
         if (qv && lg == 0) {
-            vs[q] = sf - nrm;                           // squared_exp_distance(x*, x*) = sigma_f^2 (no noise term, :40)
+            // squared_exp_distance(x*, x*) = sigma_f^2 (no noise term, :40), NaN for a non-finite x* (re-read: one write per block, and
+            // gx0 / gx1 need not stay live past the solve)
+            vs[q] = gpc_kss(sf, A.xs0[q], A.xs1[q]) - nrm;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
                 if (c < ny) fs[(size_t)c * m + q] = fm[c];
@@ -513,7 +515,7 @@ __global__ __launch_bounds__(DV_THREADS, 2) void dense_variance_big_kernel(typen
                     if (g.v_star) vst[q] = v;
                     if (g.p_star) g.p_star[(size_t)patch * m + q] = dvb_probability(A.prm.noise, fm[0], v);
                 } else
-                vst[q] = sf - nrm;
+                vst[q] = gpc_kss(sf, A.xs0[q], A.xs1[q]) - nrm;     // (the probit entries' X* is outside this rule: their own tests)
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     if (c < ny) fs[(size_t)c * m + q] = fm[c];

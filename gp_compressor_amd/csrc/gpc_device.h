@@ -132,6 +132,11 @@ __device__ static inline double gpc_rbf_neg(double sf, double c, double xi0, dou
     return sf * gpc_exp_neg(c * sq, T);
 }
 
+// k(x*, x*) of the predictive variance (gaussian_process::predict_measurements, src/gaussian_process.cpp:40): sf exp(c |x* - x*|^2) is sf
+// for a finite x* (x - x = +0 and exp(0) is exactly 1: finite data keeps its bits) and NaN when a coordinate is NaN or +-inf (x - x = NaN),
+// as the reference's own evaluation gives it.  No select, three operations per prediction point (sp_kstar is the sparse path's twin).
+__device__ static inline double gpc_kss(double sf, double x0, double x1) { return sf + ((x0 - x0) + (x1 - x1)); }
+
 __device__ static inline double gpc_rbf_small(double sf, double c, double xi0, double xi1, double xj0, double xj1)
 {
     double d0 = xi0 - xj0, d1 = xi1 - xj1;

@@ -142,6 +142,21 @@ int gpc_dense_fit_predict_grid(gpc_ctx* ctx, const gpc_params* params, int P, co
 int gpc_dense_fit_predict_grid_dev(gpc_ctx* ctx, const gpc_params* params, int P, const int32_t* off, int n_max,
                                    int n_total, const double* x0, const double* x1, const double* y, int ny,
                                    double res, int sz, double* f_star, double* alpha_out, int32_t* status);
+/* Non-finite data (all four entries, every kernel they dispatch to; hyper-parameters must be finite, see the argument rules).  The
+ * arithmetic is the reference's, which takes no special case, and what a NaN or an infinity reaches is decided per patch, per target
+ * plane and per X* column -- nothing else in the batch changes, and the variance of everything untouched keeps its bits:
+ *   x0 / x1 of a training point NaN or +-inf: the point's diagonal entry is sf * exp(c (inf - inf)^2) = NaN, a NaN pivot is not
+ *     positive: status[i] = GPC_STATUS_NOT_SPD, and f_star, v_star and alpha_out of patch i are NaN in every entry, every plane.
+ *   y of a training point NaN or +-inf: status[i] stays GPC_STATUS_OK; alpha_out and f_star of THAT plane of patch i are non-finite
+ *     in every entry (NaN or +-inf: where the infinities of a sum cancel depends on its order); the patch's other planes and its
+ *     v_star, which does not depend on y, are as without the poison.
+ *   a coordinate of X* column j NaN (point-wise entries): f_star[.][j] and v_star[j] are NaN for every patch with points.  +-inf: the
+ *     kernel value against every training point is exp(-inf) = 0, so f_star[.][j] = 0, and v_star[j] = k(x*, x*) - 0 is NaN, since
+ *     k(x*, x*) = sf * exp(c (inf - inf)^2) as gaussian_process::predict_measurements evaluates it.
+ *   a patch without points writes the prior whatever X* holds, f_star = 0 and v_star = sigmaf_sq: nothing is evaluated for it.
+ *     This is the one place where the contract is not the reference's arithmetic, which gives v_star = NaN there under a non-finite x*.
+ * The other columns of a call with a non-finite X* agree with the clean call to rounding, not to the bit (the variance kernel bounds
+ * its exponential by the extent of all of X*). */
 
 /* ---- dense GP with the probit functor: Newton / IRLS loop on the GPU (BASELINE config 5) ---------------------------- */
 /* The reference never instantiates probit_noise and holds no IRLS loop (its occupancy map is a ray-cast boolean mask,
