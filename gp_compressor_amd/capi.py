@@ -153,6 +153,8 @@ PROTOTYPES = {
     "gpc_patches_render_attrs": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "gpc_patches_render_attrs_dev": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "gpc_camera_rays_dev": (C.c_int, [_vp, _vp, _d, _d, _d, _d, _i, _i, _vp]),
+    "gpc_sparse_decode": (C.c_int, [_vp, _vp, _d, _i] + [_vp] * 5 + [_i] + [_vp] * 5),
+    "gpc_sparse_decode_dev": (C.c_int, [_vp, _vp, _d, _i] + [_vp] * 5 + [_i] + [_vp] * 5),
     "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
     "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "gpc_registration_destroy": (None, [_vp]),
@@ -712,6 +714,45 @@ class Patches:
             self.ctx.synchronize()
         return sg, nm
 
+    def decode(self, depth, rgb=None, cells=None, use_w=True, want=("leaf", "point"), device=False):
+        """gpc_sparse_decode_dev on this batch: the cloud of the map's trained leaves at the grid points whose cell holds data -- W of
+        the batch (use_w) and / or cells (P, m) uint8, a device tensor of occupancy labels (CELL_FREE cells are dropped).  depth / rgb:
+        the Sparse objects trained on the batch (rgb None: colours 0).  Rotations, means, W, sz and res are the batch's own.  A sizing
+        call, an exact allocation, the decode; complete on return.  Returns a dict: cloud (n,) POINT_DTYPE records in ascending (leaf,
+        point), and what `want` names of leaf (n,) int32, point (n,) int32 (the grid index p) and count (P,) int32 (kept points per
+        leaf).  device=True: device tensors instead of numpy arrays (cloud as (n, 32) uint8)."""
+        import torch
+        if self.res is None:
+            raise ValueError("the Patches object does not know its res (create it through Context.project_cloud)")
+        assert set(want) <= {"leaf", "point", "count"}
+        v = self.view
+        P, sz = v.P, int(round(v.m ** 0.5))
+        assert sz * sz == v.m
+        if cells is not None:
+            assert cells.numel() == P * v.m and cells.element_size() == 1
+        dev = cells.device if cells is not None else torch.device("cuda")
+        npts = torch.zeros(1, dtype=torch.int32, device=dev)
+        count = torch.zeros(max(P, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)                        # the buffers above were filled on torch's stream
+        head = (rgb, self.res, sz, v.W if (use_w and P) else None, cells if P else None, v.rotations, v.means,
+                v.rgb_means if rgb is not None else None)
+        depth.decode_dev(*head, 0, None, count=count, n_points=npts)
+        self.ctx.synchronize()
+        n = int(npts.cpu()[0])
+        cloud = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+        out = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in ("leaf", "point") if k in want}
+        torch.cuda.synchronize(dev)
+        if n:
+            depth.decode_dev(*head, n, cloud, leaf=out.get("leaf"), point=out.get("point"), n_points=npts)
+            self.ctx.synchronize()
+        if "count" in want:
+            out["count"] = count[:P]
+        out["cloud"] = cloud
+        if not device:
+            out = {k: t.cpu().numpy() for k, t in out.items()}
+            out["cloud"] = out["cloud"].reshape(-1).view(Context.POINT_DTYPE)
+        return out
+
     def occupancy_batch(self, cells):
         """gpc_occupancy_batch_dev: the labelled cells (device tensor (P, m) uint8) as the ragged batch the probit GP reads -- per leaf the
         observed cells in ascending cell index at their centres, y = +1 occupied / -1 free.  Returns device tensors off (P + 1,) int32,
@@ -802,6 +843,34 @@ class Sparse:
     def predict_dev(self, m, xs0, xs1, f_star, sigma=None, conf=False, status=None):
         self.ctx._check(self.lib.gpc_sparse_predict_dev(self.h, m, _ptr(xs0), _ptr(xs1), _ptr(f_star), _ptr(sigma),
                                                         int(conf), _ptr(status)))
+
+    def decode_dev(self, rgb, res, sz, W, cells, rotations, means, rgb_means, capacity, cloud, leaf=None, point=None, count=None,
+                   n_points=None):
+        """gpc_sparse_decode_dev with this object as the depth GP (rgb: the colour Sparse or None): device tensors or raw addresses,
+        enqueued on the context's stream.  cloud None is the sizing call."""
+        self.ctx._check(self.lib.gpc_sparse_decode_dev(self.h, rgb.h if rgb is not None else None, float(res), int(sz), _ptr(W), _ptr(cells),
+                                                       _ptr(rotations), _ptr(means), _ptr(rgb_means), int(capacity), _ptr(cloud),
+                                                       _ptr(leaf), _ptr(point), _ptr(count), _ptr(n_points)))
+
+    def decode(self, rgb, res, sz, rotations, means, rgb_means=None, W=None, cells=None, capacity=None):
+        """gpc_sparse_decode (host arrays, synchronous) with this object as the depth GP.  capacity None: a sizing call first, then
+        exactly n_points records.  Returns cloud (min(n_points, capacity),) POINT_DTYPE, leaf, point (same length) int32, count (P,)
+        int32 and n_points."""
+        P, m = self.P, int(sz) * int(sz)
+        f8 = lambda a, k: None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(P, k)
+        u1 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(P, m)
+        head = (self.h, rgb.h if rgb is not None else None, float(res), int(sz), _ptr(u1(W)), _ptr(u1(cells)), _ptr(f8(rotations, 9)),
+                _ptr(f8(means, 3)), _ptr(f8(rgb_means, 3)))
+        count = np.zeros(max(P, 1), dtype=np.int32)
+        npts = np.zeros(1, dtype=np.int32)
+        if capacity is None:
+            self.ctx._check(self.lib.gpc_sparse_decode(*head, 0, None, None, None, _ptr(count), _ptr(npts)))
+            capacity = int(npts[0])
+        cloud = np.zeros(max(capacity, 1), dtype=Context.POINT_DTYPE)
+        leaf, point = np.zeros(max(capacity, 1), dtype=np.int32), np.zeros(max(capacity, 1), dtype=np.int32)
+        self.ctx._check(self.lib.gpc_sparse_decode(*head, int(capacity), _ptr(cloud), _ptr(leaf), _ptr(point), _ptr(count), _ptr(npts)))
+        w = min(int(npts[0]), int(capacity))
+        return cloud[:w], leaf[:w], point[:w], count[:P], int(npts[0])
 
     def predict_points(self, off, x0, x1, want_sigma=False, conf=False):
         """predict_measurements with every patch on its own (ragged) point set: f (ny, N), sigma (N,)|None, status (P,)"""
@@ -1261,6 +1330,11 @@ class Mapping:
         """The map as a sensor at `origin` sees it along `dirs` (Context.camera_rays, or any (n, 3) float64 device tensor): Patches.render
         on the map's current batch, depth and colour GPs; use_cells: cells a scan saw through (CELL_FREE) do not stop a ray."""
         return self.patches.render(origin, dirs, self.depth, self.rgb, self.cells if use_cells else None, params, want)
+
+    def decode(self, use_cells=True, use_w=True, want=("leaf", "point"), device=False):
+        """The map as a cloud: Patches.decode on the map's current batch, depth and colour GPs -- every trained leaf's grid points whose
+        cell holds data (use_w: the batch's W) and that no scan saw through (use_cells: cells labelled CELL_FREE are dropped)."""
+        return self.patches.decode(self.depth, self.rgb, self.cells if use_cells else None, use_w, want, device)
 
     def _occupancy_args(self):
         """What the occupancy calls share: P, m, sz of the leaf grids and the labelled batch (off, x0, x1, y, n_total, n_max)."""

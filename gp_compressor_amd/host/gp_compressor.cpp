@@ -817,6 +817,49 @@ pointcloud gp_compressor::load_compressed()
     return to_cloud(recs);
 }
 
+// load_compressed() in one pass and only where the leaf holds data: gpc_sparse_decode under the occupancy mask W that project_points built
+// for this purpose (:90-92, :117; its use at :323-325 is commented out upstream).  The records are those load_compressed() gives for the
+// grid points whose cell of W is set, in the same order.  A model read from a file carries no W and decodes every point.
+pointcloud gp_compressor::load_compressed_masked()
+{
+    if (model_ == gp_model::dense) throw std::runtime_error("load_compressed_masked: the sparse model only (the dense model keeps grids, not GP states)");
+    if (!devices_.empty()) throw std::runtime_error("load_compressed_masked: the single-device flow only (the sharded states live on their devices)");
+    const int P = batch_.patches();
+    if (!trained_ || P == 0) return {};
+    int32_t npts = 0;
+    std::vector<gpc_point_xyzrgb> recs;
+    if (dev_patches_) {
+        // the batch is in HBM: a sizing call, then exactly that many records, which are the only download
+        gpc_patches_view dv{};
+        gpc_patches_view_dev(dev_patches_, &dv);
+        dev_buf d_n(ctx_, 4);
+        check(gpc_sparse_decode_dev(gps_, rgb_gps_, res_, sz_, dv.W, nullptr, dv.rotations, dv.means, dv.rgb_means, 0, nullptr, nullptr, nullptr,
+                                    nullptr, d_n.as<int32_t>()), ctx_, "gpc_sparse_decode_dev (sizing)");
+        d_n.download(&npts, 4);
+        recs.resize((size_t)std::max(npts, 0));
+        if (recs.empty()) return {};
+        dev_buf d_rec(ctx_, sizeof(gpc_point_xyzrgb) * recs.size());
+        check(gpc_sparse_decode_dev(gps_, rgb_gps_, res_, sz_, dv.W, nullptr, dv.rotations, dv.means, dv.rgb_means, npts,
+                                    d_rec.as<gpc_point_xyzrgb>(), nullptr, nullptr, nullptr, d_n.as<int32_t>()), ctx_, "gpc_sparse_decode_dev");
+        d_rec.download(recs.data(), sizeof(gpc_point_xyzrgb) * recs.size());
+        return to_cloud(recs);
+    }
+    std::vector<double> R((size_t)P * 9), mu((size_t)P * 3), cm((size_t)P * 3);
+    for (int i = 0; i < P; ++i) {
+        std::memcpy(&R[(size_t)i * 9], batch_.rotations[i].data(), 9 * sizeof(double));
+        std::memcpy(&mu[(size_t)i * 3], batch_.means[i].data(), 3 * sizeof(double));
+        std::memcpy(&cm[(size_t)i * 3], batch_.rgb_means[i].data(), 3 * sizeof(double));
+    }
+    const uint8_t* W = batch_.W.size() == (size_t)P * sz_ * sz_ ? batch_.W.data() : nullptr;
+    check(gpc_sparse_decode(gps_, rgb_gps_, res_, sz_, W, nullptr, R.data(), mu.data(), cm.data(), 0, nullptr, nullptr, nullptr, nullptr, &npts),
+          ctx_, "gpc_sparse_decode (sizing)");
+    recs.resize((size_t)std::max(npts, 0));
+    if (recs.empty()) return {};
+    check(gpc_sparse_decode(gps_, rgb_gps_, res_, sz_, W, nullptr, R.data(), mu.data(), cm.data(), npts, recs.data(), nullptr, nullptr, nullptr,
+                            &npts), ctx_, "gpc_sparse_decode");
+    return to_cloud(recs);
+}
+
 // ---- model file (row f3) ---------------------------------------------------------------------------------------------
 // little-endian; header: "GPCM", u32 version = 1, f64 res, i32 sz, i32 P, gpc_params depth, gpc_params rgb (raw structs, with their
 // size in front); per patch: f64 R[9], mean[3], rgb_mean[3]; i32 b_depth, b_rgb; f64 BV_depth[b][2], alpha_depth[b],
@@ -1389,6 +1432,15 @@ int gpc_host_load_compressed(void* h, float* out_xyz, uint8_t* out_rgb, int capa
 {
     try {
         return put_cloud(static_cast<gpc::gp_compressor*>(h)->load_compressed(), out_xyz, out_rgb, capacity_pts);
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// load_compressed_masked() of the object as it stands: the point count or < 0
+int gpc_host_load_compressed_masked(void* h, float* out_xyz, uint8_t* out_rgb, int capacity_pts, char* err, int errlen)
+{
+    try {
+        return put_cloud(static_cast<gpc::gp_compressor*>(h)->load_compressed_masked(), out_xyz, out_rgb, capacity_pts);
     } catch (const std::exception& e) {
         return fail(e, err, errlen);
     }

@@ -72,6 +72,11 @@ public:
 
     void save_compressed(const std::string& name);   // src/gp_compressor.cpp:21-27 (name unused upstream as well)
     pointcloud load_compressed();                    // src/gp_compressor.cpp:267-386
+    // load_compressed() restricted to the grid points whose cell of the occupancy mask W holds data (the use of W the reference
+    // comments out, :323-325), in one pass on the GPU (gpc_sparse_decode): the same records in the same order, without the GP's
+    // extrapolation into the empty part of a leaf's window.  Sparse model, single-device flow; anything else throws.  A model read
+    // from a file stores no W and decodes every point.
+    pointcloud load_compressed_masked();
 
     // The wire format the reference never wrote (save_compressed ignores `name`): per patch the
     // frame (R_i, mean_i, RGB mean) and the two sparse GPs as (BV, alpha) -- all the decompressor's mean prediction needs.

@@ -54,6 +54,7 @@ def load():
         L.gpc_host_model_bytes.argtypes = [vp, vp, i]
         L.gpc_host_prune_to_bytes.argtypes = [vp, C.c_longlong, d, d, vp, vp, i]
         L.gpc_host_load_compressed.argtypes = [vp, vp, vp, i, vp, i]
+        L.gpc_host_load_compressed_masked.argtypes = [vp, vp, vp, i, vp, i]
         L.gpc_host_shard.argtypes = [vp, i, i, i] + [vp] * 12 + [i]
         L.gpc_host_shard_scatter.argtypes = [vp, i, i, i, vp, vp, vp, i]
         _lib = L
@@ -212,13 +213,15 @@ class GpCompressor:
             raise RuntimeError(f"prune_to_bytes failed: {err.value.decode()}")
         return int(rm[0]), int(rm[1])
 
-    def load_compressed(self):
-        """load_compressed() of the object as it stands (trained, possibly pruned): (xyz float32 (M,3), rgb uint8 (M,3))"""
+    def load_compressed(self, masked=False):
+        """load_compressed() of the object as it stands (trained, possibly pruned): (xyz float32 (M,3), rgb uint8 (M,3)).  masked:
+        load_compressed_masked(), only the grid points whose cell of the occupancy mask W holds data (sparse model, one device)."""
         cap = self.L.gpc_host_patch_count(self.h) * self.sz * self.sz
         oxyz = np.zeros((max(cap, 1), 3), dtype=np.float32)
         orgb = np.zeros((max(cap, 1), 3), dtype=np.uint8)
         err = C.create_string_buffer(512)
-        n = self.L.gpc_host_load_compressed(self.h, oxyz.ctypes.data, orgb.ctypes.data, cap, C.addressof(err), 512)
+        entry = self.L.gpc_host_load_compressed_masked if masked else self.L.gpc_host_load_compressed
+        n = entry(self.h, oxyz.ctypes.data, orgb.ctypes.data, cap, C.addressof(err), 512)
         if n < 0:
             raise RuntimeError(f"load_compressed failed ({n}): {err.value.decode()}")
         return oxyz[:n], orgb[:n]

@@ -775,6 +775,43 @@ int gpc_patches_render_attrs_dev(gpc_ctx* ctx, const gpc_patches* map, gpc_spars
 int gpc_camera_rays_dev(gpc_ctx* ctx, const double R[9], double fx, double fy, double cx, double cy, int width, int height,
                         double* dirs_dev);
 
+/* ---- masked decode: the map to a cloud in one pass, only the cells that hold data ------------------------------------------------ */
+/* The patch loop of gp_compressor::load_compressed (src/gp_compressor.cpp:298-380) -- predict the depth GP and the colour GP of every
+ * trained leaf on its sz x sz grid, reproject, clamp -- fused, and restricted to the grid points whose cell holds data: the producer's
+ * occupancy mask W (its use upstream is commented out, :323-325) and / or the ray cast's cell labels.  depth (ny == 1) is required; rgb
+ * (ny == 3, the same P) may be NULL: the colours are then 0 and rgb_means may be NULL.  Both are live objects of one context.
+ *   grid     m = sz * sz.  Grid point p has gx = p % sz, gy = p / sz and the coordinates q0 = res (((double)gx + 0.5) / (double)sz - 0.5),
+ *            q1 likewise from gy: the grid of gpc_dense_fit_predict_grid.  Its cell in the layout of W and of `cells` is
+ *            c(p) = sz gx + gy: the producer's cell function (gpc_patches_raycast), transposed against p.
+ *   kept     Leaf L is decoded iff depth's basis count of L is > 0 (the reference's `gps[i].size() == 0` skip, :299-301).  Point (L, p)
+ *            is kept iff L is decoded, and W == NULL or W[L m + c(p)] != 0, and cells == NULL or cells[L m + c(p)] != GPC_CELL_FREE.
+ *   order    The kept points are written in ascending (L, p).  No atomics: the same inputs give the same bytes.
+ *   record   Record j of kept (L, p) is, bit for bit, the record gpc_reproject_dev writes for that point from the outputs of
+ *            gpc_sparse_predict_dev on the two objects: f = sum_j alpha_j k_j, j ascending over the min(basis count, ld) vectors, k_j =
+ *            sigma_f^2 exp((double)(-0.5f) / l^2 |q - BV_j|^2) with the library's exp, accumulated as the predict kernels accumulate it; the
+ *            colour mean likewise per plane under rgb's own parameters and basis (an empty colour basis gives the mean colour);
+ *            xyz[i] = (float)(((R[i] f + R[i + 3] q0) + R[i + 6] q1) + mean[i]) with no contraction, rgb = flatten_colors(c + rgb_mean),
+ *            w = 1, a = 255, pad zero.  leaf[j] = L, point[j] = p.
+ *   counts   count[L] is the number of kept points of L (0 for a leaf that is not decoded); *n_points = sum_L count[L], the FULL count
+ *            even where it exceeds capacity.  Records and leaf / point entries with index >= capacity are not written; entries at and
+ *            beyond n_points are left as they were.  cloud == NULL is the sizing call: only count and n_points are written and no GP is
+ *            evaluated; the caller allocates exactly n_points records for a second call (P m records are always enough).
+ *   outputs  W, cells [P][m]; rotations [P][9] column-major, means, rgb_means [P][3] as gpc_reproject takes them; cloud [capacity];
+ *            leaf, point [capacity] and count [P] may each be NULL; n_points must not be.
+ *   errors   On an error nothing is written.  GPC_EINVAL: a NULL depth or one whose context is gone, rgb of another context, with
+ *            another P or with ny != 3, depth with ny != 1, sz < 1, a res that is not finite, capacity < 0, NULL rotations or means
+ *            with P > 0 and cloud != NULL, rgb without rgb_means, NULL n_points.  GPC_ERANGE: P m > 2^31 - 1.  P == 0: *n_points = 0,
+ *            GPC_OK.
+ * gpc_sparse_decode_dev takes DEVICE pointers (n_points included), enqueues on the context's stream and never synchronises or reads
+ * back; its scratch (the per-leaf counts and first records) is the context's workspace.  gpc_sparse_decode takes HOST pointers and is
+ * synchronous; like gpc_reproject it downloads the count first and then only min(n_points, capacity) records. */
+int gpc_sparse_decode(gpc_sparse* depth, gpc_sparse* rgb, double res, int sz, const uint8_t* W, const uint8_t* cells,
+                      const double* rotations, const double* means, const double* rgb_means, int capacity, gpc_point_xyzrgb* cloud,
+                      int32_t* leaf, int32_t* point, int32_t* count, int32_t* n_points);
+int gpc_sparse_decode_dev(gpc_sparse* depth, gpc_sparse* rgb, double res, int sz, const uint8_t* W, const uint8_t* cells,
+                          const double* rotations, const double* means, const double* rgb_means, int capacity, gpc_point_xyzrgb* cloud,
+                          int32_t* leaf, int32_t* point, int32_t* count, int32_t* n_points);
+
 /* ---- scan-to-model registration (SURVEY section 8, row f): gp_registration on the GPU ------------------------------------ */
 /* gp_registration (src/gp_registration.h, src/gp_registration.cpp) aligns a scan to a trained model by gradient ascent on the
  * mean likelihood of the scan's points under the per-leaf depth and colour GPs.  One step (registration_step, :73-92) is
