@@ -50,6 +50,16 @@ class RenderParams(C.Structure):
     _fields_ = [("newton_iters", C.c_int32), ("use_w", C.c_int32), ("eps_rel", C.c_double), ("t_max", C.c_double)]
 
 
+class DistortionParams(C.Structure):
+    """struct gpc_distortion_params (include/gpc.h)."""
+    _fields_ = [("cell", C.c_double), ("max_dist", C.c_double)]
+
+
+# struct gpc_distortion_result (include/gpc.h), as a numpy record
+DISTORTION_RESULT_DTYPE = np.dtype([("n_valid", "<i8"), ("n_matched", "<i8"), ("n_plane", "<i8"), ("sse_d1", "<f8"), ("max_d1", "<f8"),
+                                    ("sse_d2", "<f8"), ("max_d2", "<f8"), ("sse_rgb", "<f8", (3,)), ("sse_luma", "<f8")])
+
+
 class PatchesView(C.Structure):
     """struct gpc_patches_view (include/gpc.h): sizes + device addresses of a patch batch."""
     _fields_ = [("P", C.c_int32), ("n_total", C.c_int32), ("n_max", C.c_int32), ("m", C.c_int32)] + \
@@ -155,6 +165,11 @@ PROTOTYPES = {
     "gpc_camera_rays_dev": (C.c_int, [_vp, _vp, _d, _d, _d, _d, _i, _i, _vp]),
     "gpc_sparse_decode": (C.c_int, [_vp, _vp, _d, _i] + [_vp] * 5 + [_i] + [_vp] * 5),
     "gpc_sparse_decode_dev": (C.c_int, [_vp, _vp, _d, _i] + [_vp] * 5 + [_i] + [_vp] * 5),
+    "gpc_default_params_distortion": (None, [C.POINTER(DistortionParams)]),
+    "gpc_cloud_distortion": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(DistortionParams), _vp, _vp, _vp, _vp]),
+    "gpc_cloud_distortion_dev": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(DistortionParams), _vp, _vp, _vp, _vp]),
+    "gpc_patches_normals": (C.c_int, [_vp, _i, _vp]),
+    "gpc_patches_normals_dev": (C.c_int, [_vp, _i, _vp]),
     "gpc_default_params_registration": (None, [C.POINTER(RegistrationParams)]),
     "gpc_registration_create": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "gpc_registration_destroy": (None, [_vp]),
@@ -267,6 +282,39 @@ def default_params_render(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def psnr(sse, count, peak):
+    """10 log10(peak^2 count / sse): the PSNR of `count` errors whose squares add up to sse.  +inf at sse == 0; NaN over no error."""
+    import math
+    if not count > 0 or sse != sse:
+        return float("nan")
+    if sse == 0:
+        return float("inf")
+    return 10.0 * math.log10(float(peak) * float(peak) * float(count) / float(sse))
+
+
+def symmetric_psnr(ab, ba, peak):
+    """The two directions' results of cloud_distortion -> per metric both mean square errors and the PSNR of the larger (Context.cloud_psnr)"""
+    def pick(r, name):
+        if name == "d1":
+            return r["sse_d1"], r["n_matched"], peak
+        if name == "d2":
+            return r["sse_d2"], r["n_plane"], peak
+        if name == "luma":
+            return r["sse_luma"], r["n_matched"], 255.0
+        return r["sse_rgb"]["rgb".index(name)], r["n_matched"], 255.0
+
+    out = {"ab": ab, "ba": ba}
+    for name in ("d1", "d2", "r", "g", "b", "luma"):
+        pairs = [pick(r, name) for r in (ab, ba)]
+        mse = tuple(float(s) / float(c) if c > 0 else float("nan") for s, c, _ in pairs)
+        worst = None                                          # the direction with the larger mean square error; ties: a -> b
+        for p, m in zip(pairs, mse):
+            if m == m and (worst is None or m > worst[1]):
+                worst = (p, m)
+        out[name] = {"mse": mse, "psnr": psnr(*worst[0]) if worst else float("nan")}
+    return out
 
 
 class Context:
@@ -528,6 +576,55 @@ class Context:
             self._check(self.lib.gpc_project_cloud_dev(self.h, _ptr(cloud), int(n), float(res), int(sz), C.byref(h)))
         return Patches(self, h, float(res))
 
+    def cloud_distortion(self, a, b, normals_b=None, cell=0.0, max_dist=float("inf"), want=("nn", "d2")):
+        """gpc_cloud_distortion, one direction a -> b on host record arrays (make_cloud): for every point of a its EXACT nearest valid
+        neighbour in b (ties: the lowest index), D1, D2 along normals_b (nb, 3) float32 if given, colour.  cell: voxel side of the
+        search table, 0 = the library's choice (a performance knob: no output depends on it).  Returns a dict of the fields of
+        gpc_distortion_result (n_valid, n_matched, n_plane, sse_d1, max_d1, sse_d2, max_d2, sse_rgb (3,), sse_luma) plus the per-point
+        arrays named in want: nn (na,) int32, d2, e2 (na,) float64."""
+        assert a.dtype == self.POINT_DTYPE and b.dtype == self.POINT_DTYPE
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        nb_ = None if normals_b is None else np.ascontiguousarray(normals_b, dtype=np.float32).reshape(len(b), 3)
+        prm = DistortionParams(float(cell), float(max_dist))
+        out = {k: np.zeros(max(len(a), 1), dtype=np.int32 if k == "nn" else np.float64) for k in ("nn", "d2", "e2") if k in want}
+        res = np.zeros(1, dtype=DISTORTION_RESULT_DTYPE)
+        self._check(self.lib.gpc_cloud_distortion(self.h, _ptr(a) if len(a) else None, len(a), _ptr(b) if len(b) else None, len(b),
+                                                  _ptr(nb_) if nb_ is not None and len(b) else None, C.byref(prm), _ptr(out.get("nn")),
+                                                  _ptr(out.get("d2")), _ptr(out.get("e2")), _ptr(res)))
+        return dict({k: res[k][0] for k in DISTORTION_RESULT_DTYPE.names}, **{k: v[:len(a)] for k, v in out.items()})
+
+    def cloud_distortion_dev(self, a, na, b, nb, normals_b=None, cell=0.0, max_dist=float("inf"), nn=None, d2=None, e2=None, result=None):
+        """gpc_cloud_distortion_dev: device buffers (tensors or addresses) of na / nb records, normals_b (nb, 3) float32, outputs nn
+        int32 / d2 / e2 float64 of na entries (each may be None).  With result (88 bytes on the device, DISTORTION_RESULT_DTYPE) the
+        call is left enqueued on the context's stream; without, the result is fetched and returned as a dict."""
+        import torch
+        prm = DistortionParams(float(cell), float(max_dist))
+        mine = None
+        if result is None:
+            mine = result = torch.zeros(DISTORTION_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+        self._check(self.lib.gpc_cloud_distortion_dev(self.h, _ptr(a), int(na), _ptr(b), int(nb), _ptr(normals_b), C.byref(prm), _ptr(nn),
+                                                      _ptr(d2), _ptr(e2), _ptr(result)))
+        if mine is None:
+            return None
+        self.synchronize()
+        res = mine.cpu().numpy().view(DISTORTION_RESULT_DTYPE)
+        return {k: res[k][0] for k in DISTORTION_RESULT_DTYPE.names}
+
+    def cloud_psnr(self, a, b, peak, normals_a=None, normals_b=None, na=None, nb=None, cell=0.0):
+        """Both directions of gpc_cloud_distortion and the symmetric figures a codec reports.  a, b: host record arrays, or device
+        buffers with their record counts na, nb (normals then on the device too).  The direction a -> b uses normals_b, b -> a
+        normals_a; a direction without normals has no D2.  Returns {"ab": result a -> b, "ba": result b -> a, and per metric in d1, d2,
+        r, g, b, luma: {"mse": (a -> b, b -> a), "psnr": psnr()} of the direction with the LARGER mean square error (NaN ignored)}; the peak
+        is `peak` for d1 and d2 and 255 for the colours.  A mean over no point is NaN."""
+        if isinstance(a, np.ndarray):
+            ab = self.cloud_distortion(a, b, normals_b, cell=cell, want=())
+            ba = self.cloud_distortion(b, a, normals_a, cell=cell, want=())
+        else:
+            ab = self.cloud_distortion_dev(a, na, b, nb, normals_b, cell=cell)
+            ba = self.cloud_distortion_dev(b, nb, a, na, normals_a, cell=cell)
+        return symmetric_psnr(ab, ba, peak)
+
     def reproject_dev(self, P, m, bv_count, xs0, xs1, f_star, c_star, rotations, means, rgb_means, cloud, n_points):
         self._check(self.lib.gpc_reproject_dev(self.h, P, m, _ptr(bv_count), _ptr(xs0), _ptr(xs1), _ptr(f_star), _ptr(c_star),
                                                _ptr(rotations), _ptr(means), _ptr(rgb_means), _ptr(cloud), _ptr(n_points)))
@@ -586,6 +683,16 @@ class Patches:
                                                                                   "rgb_mean", "W", "src")]))
         o["R"] = o["R"].reshape(P, 3, 3).transpose(0, 2, 1).copy()
         return o
+
+    def normals(self, n, out=None):
+        """gpc_patches_normals[_dev]: (n, 3) float32 for the cloud of n points this batch was cut from: the plane normal (column 0 of R)
+        of the leaf that owns a point, NaN for a point no leaf owns.  out: a device buffer of 3 n floats to fill instead (returned)."""
+        if out is not None:
+            self.ctx._check(self.lib.gpc_patches_normals_dev(self.h, int(n), _ptr(out)))
+            return out
+        nrm = np.zeros((max(int(n), 1), 3), dtype=np.float32)
+        self.ctx._check(self.lib.gpc_patches_normals(self.h, int(n), _ptr(nrm)))
+        return nrm[:int(n)]
 
     def insert_cloud(self, cloud, min_nbr=100, depth=None, n=None):
         """gpc_patches_insert_cloud[_dev]: a registered scan -- host record array (Context.make_cloud) or device buffer of n records -- cut

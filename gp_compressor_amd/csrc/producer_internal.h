@@ -1,5 +1,6 @@
 // producer_internal.h -- the cloud cutter: what producer.hip (gpc_project_cloud), registration.hip (gpc_registration_*), mapping.hip
-// (gpc_patches_insert_cloud), raycast.hip (gpc_patches_raycast) and render.hip (gpc_patches_render) share.  Inline device pieces: the
+// (gpc_patches_insert_cloud), raycast.hip (gpc_patches_raycast), render.hip (gpc_patches_render) and distortion.hip
+// (gpc_cloud_distortion) share.  Inline device pieces: the
 // voxel grid of a patch batch and the key arithmetic of its leaf table, the search in that table, the per-point walk to the first leaf
 // that accepts a point, a leaf's frame, mask cell and moment matrix, the ray / box test.  Declarations of what producer.hip defines
 // once for every unit: the host stages that turn a cloud into a voxel table and a batch object, and the launchers of the bucket

@@ -860,6 +860,71 @@ pointcloud gp_compressor::load_compressed_masked()
     return to_cloud(recs);
 }
 
+// The decoded cloud against the input cloud, both directions, through gpc_cloud_distortion; D2 along the producer's plane normals, which
+// only the original side has.
+distortion_stats gp_compressor::distortion(const pointcloud& decoded, double peak)
+{
+    if (!devices_.empty()) throw std::runtime_error("distortion: the single-device flow only");
+    if (cloud_.empty()) throw std::runtime_error("distortion: the object holds no input cloud (a model read from a file does not)");
+    if (!ctx_) check(gpc_ctx_create(&ctx_, device_), nullptr, "gpc_ctx_create");
+    auto records = [](const pointcloud& c) {
+        std::vector<gpc_point_xyzrgb> rec(c.size());
+        for (size_t i = 0; i < c.size(); ++i) rec[i] = gpc_point_xyzrgb{c[i].x, c[i].y, c[i].z, 1.0f, c[i].b, c[i].g, c[i].r, 255, {0.0f, 0.0f, 0.0f}};
+        return rec;
+    };
+    const std::vector<gpc_point_xyzrgb> orig = records(cloud_), dec = records(decoded);
+    const int n = (int)orig.size(), nd = (int)dec.size();
+    std::vector<float> normals(3 * orig.size());
+    if (dev_patches_) {
+        check(gpc_patches_normals(dev_patches_, n, normals.data()), ctx_, "gpc_patches_normals");
+    } else {
+        gpc_patches* cut = nullptr;
+        check(gpc_project_cloud(ctx_, orig.data(), n, res_, sz_, &cut), ctx_, "gpc_project_cloud");
+        const int rc = gpc_patches_normals(cut, n, normals.data());
+        gpc_patches_destroy(cut);
+        check(rc, ctx_, "gpc_patches_normals");
+    }
+    gpc_distortion_result r[2];
+    check(gpc_cloud_distortion(ctx_, dec.data(), nd, orig.data(), n, normals.data(), nullptr, nullptr, nullptr, nullptr, &r[0]), ctx_,
+          "gpc_cloud_distortion (decoded -> original)");
+    check(gpc_cloud_distortion(ctx_, orig.data(), n, dec.data(), nd, nullptr, nullptr, nullptr, nullptr, nullptr, &r[1]), ctx_,
+          "gpc_cloud_distortion (original -> decoded)");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    auto psnr = [&](double sse, long long count, double pk) {
+        if (!(count > 0) || sse != sse) return nan;
+        if (sse == 0) return std::numeric_limits<double>::infinity();
+        return 10.0 * std::log10(pk * pk * (double)count / sse);
+    };
+    // both means, and the PSNR of the direction with the larger one
+    auto metric = [&](const double sse[2], const long long count[2], double pk, double mse[2]) {
+        int worst = -1;
+        for (int d = 0; d < 2; ++d) {
+            mse[d] = count[d] > 0 ? sse[d] / (double)count[d] : nan;
+            if (mse[d] == mse[d] && (worst < 0 || mse[d] > mse[worst])) worst = d;
+        }
+        return worst < 0 ? nan : psnr(sse[worst], count[worst], pk);
+    };
+    distortion_stats s{};
+    long long matched[2], plane[2];
+    for (int d = 0; d < 2; ++d) {
+        s.n_valid[d] = r[d].n_valid;
+        matched[d] = s.n_matched[d] = r[d].n_matched;
+        plane[d] = s.n_plane[d] = r[d].n_plane;
+    }
+    const double d1[2] = {r[0].sse_d1, r[1].sse_d1}, d2[2] = {r[0].sse_d2, r[1].sse_d2}, lu[2] = {r[0].sse_luma, r[1].sse_luma};
+    s.psnr_d1 = metric(d1, matched, peak, s.mse_d1);
+    s.psnr_d2 = metric(d2, plane, peak, s.mse_d2);
+    s.psnr_luma = metric(lu, matched, 255.0, s.mse_luma);
+    for (int c = 0; c < 3; ++c) {
+        const double sc[2] = {r[0].sse_rgb[c], r[1].sse_rgb[c]};
+        double mse[2];
+        s.psnr_rgb[c] = metric(sc, matched, 255.0, mse);
+        s.mse_rgb[0][c] = mse[0];
+        s.mse_rgb[1][c] = mse[1];
+    }
+    return s;
+}
+
 // ---- model file (row f3) ---------------------------------------------------------------------------------------------
 // little-endian; header: "GPCM", u32 version = 1, f64 res, i32 sz, i32 P, gpc_params depth, gpc_params rgb (raw structs, with their
 // size in front); per patch: f64 R[9], mean[3], rgb_mean[3]; i32 b_depth, b_rgb; f64 BV_depth[b][2], alpha_depth[b],
@@ -1441,6 +1506,32 @@ int gpc_host_load_compressed_masked(void* h, float* out_xyz, uint8_t* out_rgb, i
 {
     try {
         return put_cloud(static_cast<gpc::gp_compressor*>(h)->load_compressed_masked(), out_xyz, out_rgb, capacity_pts);
+    } catch (const std::exception& e) {
+        return fail(e, err, errlen);
+    }
+}
+// gp_compressor::distortion of the cloud (xyz, rgb; n points) against the object's input cloud.  out[24]: n_valid[2], n_matched[2],
+// n_plane[2] (as doubles), mse_d1[2], mse_d2[2], mse_rgb[2][3], mse_luma[2], psnr_d1, psnr_d2, psnr_rgb[3], psnr_luma.  0, or < 0 on error.
+int gpc_host_distortion(void* h, const float* xyz, const uint8_t* rgb, int n, double peak, double* out, char* err, int errlen)
+{
+    try {
+        gpc::pointcloud c((size_t)(n > 0 ? n : 0));
+        for (size_t i = 0; i < c.size(); ++i) c[i] = gpc::point{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]};
+        const gpc::distortion_stats s = static_cast<gpc::gp_compressor*>(h)->distortion(c, peak);
+        int k = 0;
+        for (int d = 0; d < 2; ++d) out[k++] = (double)s.n_valid[d];
+        for (int d = 0; d < 2; ++d) out[k++] = (double)s.n_matched[d];
+        for (int d = 0; d < 2; ++d) out[k++] = (double)s.n_plane[d];
+        for (int d = 0; d < 2; ++d) out[k++] = s.mse_d1[d];
+        for (int d = 0; d < 2; ++d) out[k++] = s.mse_d2[d];
+        for (int d = 0; d < 2; ++d)
+            for (int ch = 0; ch < 3; ++ch) out[k++] = s.mse_rgb[d][ch];
+        for (int d = 0; d < 2; ++d) out[k++] = s.mse_luma[d];
+        out[k++] = s.psnr_d1;
+        out[k++] = s.psnr_d2;
+        for (int ch = 0; ch < 3; ++ch) out[k++] = s.psnr_rgb[ch];
+        out[k++] = s.psnr_luma;
+        return 0;
     } catch (const std::exception& e) {
         return fail(e, err, errlen);
     }

@@ -61,6 +61,15 @@ struct patch_batch {
     int patches() const { return (int)off.size() - 1; }
 };
 
+// What gp_compressor::distortion reports.  Index 0: decoded -> original, 1: original -> decoded.  A mean over no point is NaN.
+struct distortion_stats {
+    long long n_valid[2], n_matched[2], n_plane[2];       // gpc_distortion_result's counts per direction
+    double mse_d1[2], mse_d2[2], mse_rgb[2][3], mse_luma[2];
+    // 10 log10(peak^2 count / sse) of the direction with the LARGER mean square error (NaN ignored); +inf at sse == 0.  The peak is the
+    // caller's for d1 and d2 and 255 for the colours.
+    double psnr_d1, psnr_d2, psnr_rgb[3], psnr_luma;
+};
+
 class gp_compressor {
 public:
     // gp_compressor(pointcloud::ConstPtr ncloud, double res = 0.1f, int sz = 10)   src/gp_compressor.h:65
@@ -77,6 +86,12 @@ public:
     // extrapolation into the empty part of a leaf's window.  Sparse model, single-device flow; anything else throws.  A model read
     // from a file stores no W and decodes every point.
     pointcloud load_compressed_masked();
+    // The distortion of a decoded cloud against the object's own input cloud, in both directions (gpc_cloud_distortion: the exact nearest
+    // neighbour, D1, D2, colour).  D2 uses the plane normals of the projected batch (gpc_patches_normals), which exist on the ORIGINAL
+    // side only: mse_d2[1] is NaN.  Either model; the single-device flow, and an object that has its input cloud (a loaded model has
+    // none); anything else throws.  The object is not modified: where the batch was cut on the host, the same batch is cut on the device for
+    // the normals alone and dropped.
+    distortion_stats distortion(const pointcloud& decoded, double peak);
 
     // The wire format the reference never wrote (save_compressed ignores `name`): per patch the
     // frame (R_i, mean_i, RGB mean) and the two sparse GPs as (BV, alpha) -- all the decompressor's mean prediction needs.

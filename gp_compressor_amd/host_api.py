@@ -55,6 +55,7 @@ def load():
         L.gpc_host_prune_to_bytes.argtypes = [vp, C.c_longlong, d, d, vp, vp, i]
         L.gpc_host_load_compressed.argtypes = [vp, vp, vp, i, vp, i]
         L.gpc_host_load_compressed_masked.argtypes = [vp, vp, vp, i, vp, i]
+        L.gpc_host_distortion.argtypes = [vp, vp, vp, i, d, vp, vp, i]
         L.gpc_host_shard.argtypes = [vp, i, i, i] + [vp] * 12 + [i]
         L.gpc_host_shard_scatter.argtypes = [vp, i, i, i, vp, vp, vp, i]
         _lib = L
@@ -225,6 +226,26 @@ class GpCompressor:
         if n < 0:
             raise RuntimeError(f"load_compressed failed ({n}): {err.value.decode()}")
         return oxyz[:n], orgb[:n]
+
+
+    def distortion(self, xyz, rgb, peak):
+        """gp_compressor::distortion: the cloud (xyz (M, 3) float32, rgb (M, 3) uint8) against the object's input cloud, both directions,
+        index 0 = decoded -> original.  Returns counts {"n_valid", "n_matched", "n_plane"}: (2,) and per metric in d1, d2, r, g, b, luma
+        {"mse": (2,), "psnr": of the larger mse}, the layout of capi.Context.cloud_psnr.  D2 has the original side's normals only."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        out = np.zeros(24)
+        err = C.create_string_buffer(512)
+        if self.L.gpc_host_distortion(self.h, xyz.ctypes.data, rgb.ctypes.data, len(xyz), float(peak), out.ctypes.data, C.addressof(err),
+                                      512) != 0:
+            raise RuntimeError(f"distortion failed: {err.value.decode()}")
+        res = {k: out[2 * j:2 * j + 2].astype(np.int64) for j, k in enumerate(("n_valid", "n_matched", "n_plane"))}
+        res["d1"] = {"mse": tuple(out[6:8]), "psnr": out[18]}
+        res["d2"] = {"mse": tuple(out[8:10]), "psnr": out[19]}
+        for c, k in enumerate("rgb"):
+            res[k] = {"mse": (out[10 + c], out[13 + c]), "psnr": out[20 + c]}
+        res["luma"] = {"mse": tuple(out[16:18]), "psnr": out[23]}
+        return res
 
 
 def decompress_file(path, capacity_pts, device=0):

@@ -812,6 +812,65 @@ int gpc_sparse_decode_dev(gpc_sparse* depth, gpc_sparse* rgb, double res, int sz
                           const double* rotations, const double* means, const double* rgb_means, int capacity, gpc_point_xyzrgb* cloud,
                           int32_t* leaf, int32_t* point, int32_t* count, int32_t* n_points);
 
+/* ---- cloud-to-cloud distortion: exact nearest neighbour, D1 / D2 / colour ------------------------------------------------------------ */
+/* What a point-cloud codec reports: for every point of cloud A (na records) its nearest neighbour in cloud B (nb records), and from it
+ * the point-to-point error D1, the point-to-plane error D2 and the colour error, summed over A.  ONE direction, A -> B, per call; a
+ * symmetric figure is two calls.  The rule is stated per point, with nothing left to the scheduler, and no number it gives depends on
+ * `cell`, which only sizes the search table.
+ *   valid    A record is valid iff x, y and z are all finite.  Invalid records of B are never a neighbour; invalid records of A get
+ *            nn = -1, d2 = e2 = NaN and count nowhere.  (The organised clouds of gpc_patches_render carry NaN misses: usable as either.)
+ *   d2       For valid a, b:  dx = (double)a.x - (double)b.x, dy, dz likewise;  d2(a, b) = (dx dx + dy dy) + dz dz, no contraction.
+ *   nn       nn[i] = the valid record of B with the smallest d2(a_i, .); of several with that d2, the LOWEST index in B: the EXACT
+ *            nearest neighbour, as a scan of B in ascending index gives it.  Not approximate at any cell, density or position of A
+ *            (inside B's box, on a voxel face, far outside it): the ring search stops only when (r - 2^-20)^2 cell^2 plus A's squared
+ *            distance outside the table's box, less the rounding of its own terms, STRICTLY exceeds the best d2.
+ *   none     If that d2 > max_dist max_dist (formed in double), or B has no valid record: nn = -1, d2 = e2 = NaN; the point counts
+ *            in n_valid, not in n_matched.  max_dist = +inf (the default) searches exhaustively; max_dist = 0 matches coincident points.
+ *   e2       With normals_b != NULL (nb x 3 floats, indexed like B) and the neighbour's normal finite in all three components:
+ *            e2 = ((dx n0 + dy n1) + dz n2)^2, the normal widened to double, used as given and NOT renormalised.  Otherwise e2 = NaN
+ *            and the point is not in n_plane.
+ *   colour   Per matched point, from the integer channel differences dr, dg, db (a minus b):  (double)dc (double)dc per channel, in
+ *            r, g, b order, and ((0.2126 dr + 0.7152 dg) + 0.0722 db)^2.
+ *   sums     A sum over an array of values indexed by i (the record index of A; entries that do not take part contribute +0.0) is
+ *            taken in chunks of 4096 consecutive entries: inside a chunk entry i goes to class i mod 64, each class adds its entries in
+ *            ascending i starting from +0.0, and the 64 class sums s go through the xor-shuffle tree  s[c] <- s[c] + s[c ^ d],
+ *            d = 32, 16, .. 1 (the tree of gpc_sparse_prune_rd's mse), whose s[0] is the chunk's sum.  The array of chunk sums is
+ *            summed by the same rule, and again, until one value is left.  Maxima are 0 where nothing takes part.  No atomics: the
+ *            same inputs give the same bytes, at every cell.
+ *   outputs  nn (int32), d2, e2 (double): na entries each, any may be NULL.  result: see the struct.  na == 0: result all zero, GPC_OK.
+ *   errors   On an error nothing is written.  GPC_EINVAL: a NULL or destroyed ctx, negative na or nb, NULL A with na > 0, NULL B with
+ *            nb > 0, NULL result, cell negative or not finite, max_dist NaN or negative.  GPC_ERANGE: a cell so small that B's box
+ *            spans more than 2^21 voxels along an axis (the cutters' key limit); cell = 0, the library's choice, never does: it is
+ *            c0 = max(sqrt(4 e1 e2 / nv), e1 / 2^20) with e1 >= e2 the two largest extents of B's box and nv its valid records (four
+ *            points per voxel if B were a surface filling its box), and where that table holds more than 8 points per OCCUPIED voxel
+ *            on average (a patchy or folded surface), max(c0 sqrt(4 / that average), e1 / 2^20).  params == NULL: the defaults.
+ * gpc_cloud_distortion_dev takes DEVICE pointers, result included, works on the context's stream and in its workspace, and
+ * SYNCHRONISES the stream while it builds the table (its size depends on the data), as the cutters do; the search and the sums are
+ * enqueued behind that, so the outputs are complete once the stream is.  gpc_cloud_distortion takes HOST pointers and is synchronous. */
+typedef struct gpc_distortion_params {
+    double cell;       /* voxel side of the search table over B; 0 = chosen by the library.  A PERFORMANCE knob only */
+    double max_dist;   /* a neighbour counts only if d2 <= max_dist * max_dist; +inf = exhaustive (the default) */
+} gpc_distortion_params;
+typedef struct gpc_distortion_result {
+    int64_t n_valid, n_matched, n_plane;     /* A points with finite xyz; of those, with a neighbour; of those, with a finite normal */
+    double sse_d1, max_d1;                   /* over matched points: sum and max of d2 */
+    double sse_d2, max_d2;                   /* over plane points: sum and max of e2 */
+    double sse_rgb[3], sse_luma;             /* over matched points */
+} gpc_distortion_result;
+void gpc_default_params_distortion(gpc_distortion_params* p);
+int gpc_cloud_distortion(gpc_ctx* ctx, const gpc_point_xyzrgb* a, int na, const gpc_point_xyzrgb* b, int nb, const float* normals_b,
+                         const gpc_distortion_params* params, int32_t* nn, double* d2, double* e2, gpc_distortion_result* result);
+int gpc_cloud_distortion_dev(gpc_ctx* ctx, const gpc_point_xyzrgb* a, int na, const gpc_point_xyzrgb* b, int nb, const float* normals_b,
+                             const gpc_distortion_params* params, int32_t* nn, double* d2, double* e2, gpc_distortion_result* result);
+/* The normals that make D2 usable on a cloud this library cut: for a batch cut from a cloud of n points, normals[n][3] (float): point
+ * src[j] of leaf L (off[L] <= j < off[L + 1]) gets (float) of column 0 of R_L, the plane normal the producer fitted over the leaf's
+ * sphere; a point no leaf owns gets three NaN.  GPC_EINVAL: a NULL or destroyed batch, NULL normals with n > 0, n < 0, a batch that
+ * holds more points than n or a src entry >= n (gpc_patches_raycast's test: the batch was cut from another cloud); nothing is written
+ * then.  gpc_patches_normals_dev takes a DEVICE buffer, works on the context's stream and synchronises it once (the src test);
+ * gpc_patches_normals takes a HOST buffer and is synchronous. */
+int gpc_patches_normals(const gpc_patches* p, int n, float* normals);
+int gpc_patches_normals_dev(const gpc_patches* p, int n, float* normals);
+
 /* ---- scan-to-model registration (SURVEY section 8, row f): gp_registration on the GPU ------------------------------------ */
 /* gp_registration (src/gp_registration.h, src/gp_registration.cpp) aligns a scan to a trained model by gradient ascent on the
  * mean likelihood of the scan's points under the per-leaf depth and colour GPs.  One step (registration_step, :73-92) is
