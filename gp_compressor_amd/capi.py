@@ -104,6 +104,11 @@ PROTOTYPES = {
     "gpc_dense_fit_predict_grid": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _vp, _vp, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "gpc_dense_fit_predict_grid_dev": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _i, _i, _vp, _vp, _vp, _i, _d, _i,
                                                  _vp, _vp, _vp]),
+    # ctx, params, [H, cand,] P, off, [n_max, n_total,] x0, x1, y, ny, m, xs0, xs1, res, sz, then the outputs
+    "gpc_dense_fit_predict_ev": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i] + [_vp] * 5),
+    "gpc_dense_fit_predict_ev_dev": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i] + [_vp] * 5),
+    "gpc_dense_select": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i] + [_vp] * 7),
+    "gpc_dense_select_dev": (C.c_int, [_vp, C.POINTER(Params), _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i] + [_vp] * 7),
     "gpc_default_params_irls": (None, [C.POINTER(IrlsParams)]),
     "gpc_dense_irls_fit_predict": _irls_proto(_IRLS_HOST, 5),
     "gpc_dense_irls_fit_predict_dev": _irls_proto(_IRLS_DEV, 5),
@@ -424,6 +429,72 @@ class Context:
         self._check(self.lib.gpc_dense_fit_predict_grid(self.h, C.byref(params), P, _ptr(off), _ptr(x0), _ptr(x1), _ptr(y),
                                                         ny, float(res), int(sz), _ptr(f), _ptr(al), _ptr(st)))
         return (f, st, al) if want_alpha else (f, st)
+
+    # ---- dense GP with the log marginal likelihood, and the selection among candidates by it ---------------------------
+    def _ev_host_args(self, params, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_alpha, want_status):
+        """What the two host entries share: the arguments of the C call from P to sz, the contiguous inputs behind their addresses
+        (the caller keeps them alive over the call), and the outputs f (P, ny, m), v (P, m), alpha (ny, N), status (P,), log_ev (P, ny)
+        filled with NaN / -1 (None where not wanted)."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        y = np.ascontiguousarray(np.atleast_2d(y), dtype=np.float64)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        if xs0 is not None:
+            xs0 = np.ascontiguousarray(xs0, dtype=np.float64)
+            xs1 = np.ascontiguousarray(xs1, dtype=np.float64)
+            m = xs0.shape[0]
+        else:
+            m = sz * sz
+        P, ny = off.shape[0] - 1, y.shape[0]
+        f = np.full((P, ny, m), np.nan)
+        v = np.full((P, m), np.nan) if want_v else None
+        al = np.full_like(y, np.nan) if want_alpha else None
+        st = np.full(P, -1, dtype=np.int32) if want_status else None
+        ev = np.full((P, ny), np.nan)
+        keep = (off, x0, x1, y, xs0, xs1)
+        mid = [P, _ptr(off), _ptr(x0), _ptr(x1), _ptr(y), ny, m, _ptr(xs0), _ptr(xs1), float(res), int(sz)]
+        return mid, keep, (f, v, al, st, ev)
+
+    def dense_fit_predict_ev(self, params, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, want_alpha=True,
+                             want_status=True, want_ev=True):
+        """Host-pointer entry (gpc_dense_fit_predict_ev): the dense fit with the log marginal likelihood per patch and plane.  y: (ny, N).
+        X* point-wise (xs0, xs1) or the sz x sz grid.  Returns f_star (P, ny, m), v_star (P, m), alpha (ny, N), status (P,),
+        log_ev (P, ny) -- None where not wanted."""
+        mid, keep, (f, v, al, st, ev) = self._ev_host_args(params, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_alpha, want_status)
+        if not want_ev:
+            ev = None
+        self._check(self.lib.gpc_dense_fit_predict_ev(self.h, C.byref(params), *mid, *map(_ptr, (f, v, al, st, ev))))
+        return f, v, al, st, ev
+
+    def dense_fit_predict_ev_dev(self, params, P, off, n_max, n_total, x0, x1, y, ny, m, xs0, xs1, res, sz, f_star,
+                                 v_star=None, alpha_out=None, status=None, log_ev=None):
+        self._check(self.lib.gpc_dense_fit_predict_ev_dev(self.h, C.byref(params), P, _ptr(off), n_max, n_total, _ptr(x0), _ptr(x1),
+                                                          _ptr(y), ny, m, _ptr(xs0), _ptr(xs1), float(res), int(sz),
+                                                          *map(_ptr, (f_star, v_star, alpha_out, status, log_ev))))
+
+    def dense_select(self, params, candidates, off, x0, x1, y, xs0=None, xs1=None, res=0.0, sz=0, want_v=True, skip=()):
+        """Host-pointer entry (gpc_dense_select): per patch the candidate (sigmaf_sq, l_sq, noise) of largest log marginal likelihood
+        (summed over the planes) and its outputs.  Returns a dict of f_star (P, ny, m), v_star (P, m), alpha (ny, N), log_ev (P, ny),
+        best (P,) int32 (-1: no eligible candidate), log_ev_all (H, P, ny), status (P,); names in `skip` are passed as NULL."""
+        mid, keep, (f, v, al, st, ev) = self._ev_host_args(params, off, x0, x1, y, xs0, xs1, res, sz, want_v, True, True)
+        H, P, ny = len(candidates), mid[0], mid[5]
+        out = dict(f_star=f, v_star=v, alpha=al, log_ev=ev, best=np.full(P, -2, dtype=np.int32), log_ev_all=np.full((H, P, ny), np.nan),
+                   status=st)
+        for k in skip:
+            out[k] = None
+        arr = self.hyper_array(candidates)
+        self._check(self.lib.gpc_dense_select(self.h, C.byref(params), H, C.addressof(arr), *mid,
+                                              *map(_ptr, (out[k] for k in ("f_star", "v_star", "alpha", "log_ev", "best", "log_ev_all",
+                                                                           "status")))))
+        return out
+
+    def dense_select_dev(self, params, candidates, P, off, n_max, n_total, x0, x1, y, ny, m, xs0, xs1, res, sz, f_star=None, v_star=None,
+                         alpha_out=None, log_ev=None, best=None, log_ev_all=None, status=None):
+        """gpc_dense_select_dev: device pointers throughout, except the candidates (host, read at call time)."""
+        arr = self.hyper_array(candidates)
+        self._check(self.lib.gpc_dense_select_dev(self.h, C.byref(params), len(candidates), C.addressof(arr), P, _ptr(off), n_max, n_total,
+                                                  _ptr(x0), _ptr(x1), _ptr(y), ny, m, _ptr(xs0), _ptr(xs1), float(res), int(sz),
+                                                  *map(_ptr, (f_star, v_star, alpha_out, log_ev, best, log_ev_all, status))))
 
     # ---- dense GP + probit functor, Newton / IRLS loop (BASELINE config 5) ---------------------------------------------
     def _irls_host_args(self, params, irls, off, x0, x1, y, xs0, xs1, res, sz, want_v, want_p):

@@ -148,7 +148,7 @@ int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* 
         // One factor slot (304 KB) per patch of a launch.  If the device cannot serve that, the batch goes
         // through in smaller launches that reuse fewer slots, and below two launches' worth of resident patches it takes the
         // route it would have had without this kernel -- the register-resident one needs no workspace at all.
-        for (int cap_w1 = 0;;) {
+        for (int cap_w1 = site.w1_cap;;) {      // (site.w1_cap: where the caller's own dense_reserve, which ran this loop, ended)
             rc = gpc_ws_reserve(ctx, site, al256(dense_w1_ws_bytes(facts, route, &grid, cap_w1)));
             if (rc != GPC_ENOMEM) break;
             cap_w1 = grid / 2;
@@ -185,6 +185,41 @@ int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* 
     }
     if (rc == GPC_OK) ctx->last_dense_kernel = route.name;
     return rc;
+}
+
+// What dense_dispatch will reserve for a batch on the variance route, `front` bytes of the caller's own in front of it, reserved in one
+// step at `site`: the caller may then fill its front region before the dispatch without a later grow moving the workspace from under it.
+// The one-wave route runs the dispatcher's retry with fewer slots here and leaves where it ended in *w1_cap.  A batch off the variance
+// route is GPC_EINVAL; DENSE_NO_ROUTE stays GPC_ENOMEM.
+int dense_reserve(gpc_ctx* ctx, const DenseSite& site, size_t front, const DenseArgs& a, int* w1_cap)
+{
+    *w1_cap = 0;
+    const DenseFacts facts = dense_facts(ctx, a);
+    const DenseRoute route = dense_route(facts, dense_switches_read());
+    int grid = 0, rc = GPC_ENOMEM;
+    switch (route.kind) {
+        case DENSE_NOTHING:
+            return gpc_ws_reserve(ctx, site, front);
+        case DENSE_ONE_WAVE:
+            for (int cap_w1 = 0;;) {
+                rc = gpc_ws_reserve(ctx, site, front + al256(dense_w1_ws_bytes(facts, route, &grid, cap_w1)));
+                *w1_cap = cap_w1;
+                if (rc != GPC_ENOMEM) break;
+                cap_w1 = grid / 2;
+                if (cap_w1 < 4 * ctx->num_cus) break;
+            }
+            return rc;
+        case DENSE_REGISTER:
+            return gpc_ws_reserve(ctx, site, front + dense_mfma_ws_bytes(a, route));
+        case DENSE_TILED:
+            return gpc_ws_reserve(ctx, site, front + al256(dense_big_ws_bytes(ctx, a, route, &grid)));
+        case DENSE_GENERIC:
+            return gpc_ws_reserve(ctx, site, front + dense_generic_ws_bytes(ctx, a, &grid));
+        case DENSE_NO_ROUTE:
+            return gpc_fail(ctx, GPC_ENOMEM, "no kernel computes the variance of this batch without the one-wave workspace");
+        default:
+            return gpc_fail(ctx, GPC_EINVAL, "dense_reserve: not a batch of the variance route");
+    }
 }
 
 extern "C" {

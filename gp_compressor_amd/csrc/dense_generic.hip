@@ -90,6 +90,7 @@ __global__ __launch_bounds__(GEN_THREADS) void dense_generic_kernel(GenParams g)
             if (A.v_star)
                 for (int p = tid; p < m; p += GEN_THREADS) A.v_star[(size_t)patch * m + p] = (n == 0) ? sf : __builtin_nan("");
             if (tid == 0 && A.status) A.status[patch] = (n == 0) ? GPC_STATUS_OK : GPC_STATUS_NAN;
+            if (A.log_ev && tid < ny) A.log_ev[(size_t)patch * ny + tid] = (n == 0) ? 0.0 : __builtin_nan("");
             continue;
         }
         for (int i = tid; i < n; i += GEN_THREADS) {
@@ -194,6 +195,7 @@ __global__ __launch_bounds__(GEN_THREADS) void dense_generic_kernel(GenParams g)
                 for (int i = tid; i < n * ny; i += GEN_THREADS)
                     A.alpha_out[(size_t)(i / n) * A.n_total + o + (i % n)] = __builtin_nan("");
             if (tid == 0 && A.status) A.status[patch] = GPC_STATUS_NOT_SPD;
+            if (A.log_ev && tid < ny) A.log_ev[(size_t)patch * ny + tid] = __builtin_nan("");
             continue;
         }
 
@@ -246,6 +248,22 @@ __global__ __launch_bounds__(GEN_THREADS) void dense_generic_kernel(GenParams g)
         if (A.alpha_out)
             for (int i = tid; i < n; i += GEN_THREADS)
                 for (int c = 0; c < ny; ++c) A.alpha_out[(size_t)c * A.n_total + o + i] = al[c * n_max + i];
+
+        // ---- optional log marginal likelihood (gpc_dense_fit_predict_ev, include/gpc.h) from the pivots in the slot: the sums in the order
+        // of dense_gauss_evidence_kernel (point j in lane j mod 64 of wave 0, then the shuffle tree), so that the MFMA routes are checked
+        // against a value that no factor export went into ----
+        if (A.log_ev && wave == 0) {
+            double quad[3] = {0.0, 0.0, 0.0}, ldet = 0.0;
+            for (int j = lane; j < n; j += 64) {
+                ldet -= log(W[j + (size_t)j * ld]);
+                for (int c = 0; c < ny; ++c) quad[c] = __builtin_fma(A.y[(size_t)c * A.n_total + o + j], al[c * n_max + j], quad[c]);
+            }
+            ldet = ev_wave_sum(ldet);
+            for (int c = 0; c < ny; ++c) {
+                const double q = ev_wave_sum(quad[c]);
+                if (lane == 0) A.log_ev[(size_t)patch * ny + c] = (-0.5 * q + ldet) - EV_HALF_LOG_2PI * (double)n;
+            }
+        }
 
         // ---- predictive mean f* = K*^T alpha on X* (point-wise list or the reference's sz x sz grid) ----
         for (int p = tid; p < m; p += GEN_THREADS) {

@@ -22,12 +22,16 @@ struct DenseArgs {
     const int32_t* sel_count;
     int sel_base;              // generic kernel only: it works on sel[sel_base .. *sel_count) -- the overflow launch behind a class launch that
                                // was sized from a host-side hint (dense_api.hip)
+    // gpc_dense_fit_predict_ev (include/gpc.h): the log marginal likelihood [P][ny], or nullptr.  A call that asks for it takes the
+    // variance route (dense_facts) with the factor export on, and needs status and alpha_out (dense_ev_api.hip supplies temporaries)
+    double* log_ev;
 };
 
 // Where a dense call runs.  A host-side value handed from the dispatcher to the launchers, never part of a kernel-parameter struct.
 struct DenseSite {
     hipStream_t stream;     // every launch, memset and event record of the call in hand
     size_t ws_off, ws_len;  // the region of ctx->ws it may use; ws_len == 0: the whole workspace, not a chunk of the host-pointer pipeline
+    int w1_cap = 0;         // one-wave route: the factor slots the caller's own dense_reserve settled on (0: the route's)
 };
 
 // a call on the context's stream that may use the whole workspace (caller holds ctx->mu)
@@ -48,6 +52,19 @@ static inline int gpc_ws_reserve(gpc_ctx* ctx, const DenseSite& site, size_t byt
 // GPC_POISON_LDS for a dense call: launched on the site's stream, and only the site's region of the workspace is filled
 int gpc_debug_poison_lds(gpc_ctx* ctx, const DenseSite& site);
 
+// Regions of the workspace, one behind the other, each rounded up to 256 bytes; take() answers the region's byte offset (pointers are
+// formed after the reserve, which may move the workspace).
+struct WsCarve {
+    size_t bytes = 0;
+    template <class T> size_t take(size_t count)
+    {
+        const size_t at = bytes;
+        bytes += (sizeof(T) * count + 255) & ~(size_t)255;
+        return at;
+    }
+};
+template <class T> static inline T* ws_at(char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
+
 // ---- dispatcher (dense_api.hip), also used by the host-pointer pipeline (dense_host.hip); the argument check and dense_args also by
 // ---- the probit / IRLS entries (dense_irls_api.hip) ------------------------------------------------------------
 
@@ -59,12 +76,17 @@ DenseArgs dense_args(const gpc_params* prm, int P, const int32_t* off, int n_max
 // what dense_route looks at, of a batch as its entry point received it
 static inline DenseFacts dense_facts(const gpc_ctx* ctx, const DenseArgs& a, bool irls = false)
 {
-    return DenseFacts{a.P, a.n_max, a.n_total, a.ny, a.m, a.prm.want_variance && a.v_star, a.xs0 != nullptr, a.alpha_out != nullptr,
-                      ctx->num_cus, irls};
+    return DenseFacts{a.P, a.n_max, a.n_total, a.ny, a.m, (a.prm.want_variance && a.v_star) || a.log_ev, a.xs0 != nullptr,
+                      a.alpha_out != nullptr, ctx->num_cus, irls};
 }
 // Asks dense_route for the kernels of a batch and launches them at `site`; caller holds ctx->mu.  `seen_gen`: a chunk of the two-stream
 // host-pointer pipeline hands in gpc_ctx::foreign_gen as its compute stream last saw it (gpc_pipe_chunk_order); nullptr everywhere else.
 int dense_dispatch(gpc_ctx* ctx, DenseArgs& a, const DenseSite& site, unsigned* seen_gen = nullptr);
+// `front` bytes of the caller's own plus everything the dispatch of `a` (a batch of the variance route) will reserve behind them, in one
+// step.  *w1_cap: what the dispatch must find in its DenseSite::w1_cap.  The entries that keep temporaries in the workspace across a
+// dispatch (dense_ev_api.hip) call it first.  It asks the same byte functions as the dispatcher and the launchers (dense_w1_ws_bytes,
+// dense_mfma_ws_bytes, dense_big_ws_bytes, dense_generic_ws_bytes): a launcher that reserves anything else must say so here too.
+int dense_reserve(gpc_ctx* ctx, const DenseSite& site, size_t front, const DenseArgs& a, int* w1_cap);
 
 // ---- launchers implemented in the kernel translation units -------------------------------------------------
 
@@ -73,6 +95,8 @@ size_t dense_generic_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, int* grid_
 int dense_generic_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int grid, double* ws_override = nullptr);
 
 // register-tile MFMA kernel: n <= 256, trailing matrix resident in VGPRs (see dense_mfma.hip)
+// (what its launcher reserves with the factor export on -- v_star or log_ev wanted --, else 0)
+size_t dense_mfma_ws_bytes(const DenseArgs& a, const DenseRoute& r);
 int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, const DenseRoute& r);
 
 // predictive variance from the exported factor of the register-tile kernel (dense_variance.hip): V* [P][m]
@@ -97,6 +121,24 @@ int dense_grid_points_launch(gpc_ctx* ctx, const DenseSite& site, double res, in
 // include/gpc.h): a, fhat, the labels a.y, the fit's status a.status and the L_kk^-1 images of the slots; log_q [P]
 int dense_evidence_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int ntw, const double* ws, size_t slot,
                           const double* alpha, const double* fhat, double* log_q);
+// The log marginal likelihood of the regression GP from what a fit with the export on left behind (dense_evidence.hip; definition:
+// include/gpc.h, gpc_dense_fit_predict_ev): y, alpha, the fit's status a.status and the diagonals of the L_kk^-1 images; log_ev [P][ny].
+// The factor is in one of two layouts: tri_nt > 0: [P][tri_nt (tri_nt + 1) / 2] images, the lower triangle the register and the one-wave
+// kernel export (image k (k + 1) / 2 + k is L_kk^-1); tri_nt == 0: the tiled kernel's slots of `slot` doubles (ntw tile columns).
+int dense_gauss_evidence_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a, int tri_nt, int ntw, const double* ws, size_t slot,
+                                const double* alpha, double* log_ev);
+// ... and the keep-best step of gpc_dense_select: candidate h's rows go from `cand` to `out` where it wins the patch by the sum of its
+// planes' log_ev.  Any pointer of `out` may be nullptr; cur_best, cur_ev [P] hold the state between the candidates.
+struct GaussRows {
+    double *f;                // [P][ny][m]
+    double *v;                // [P][m]
+    double *alpha;            // [ny][n_total]
+    double *log_ev;           // [P][ny]
+    int32_t *status;          // [P]
+};
+int dense_gauss_keep_launch(gpc_ctx* ctx, const DenseSite& site, int h, int P, int ny, int m, int n_total, const int32_t* off,
+                            const GaussRows& cand, const GaussRows& out, int32_t* best, double* log_ev_all_h, int32_t* cur_best,
+                            double* cur_ev);
 // One candidate's outputs (gpc_dense_irls_select, include/gpc.h) and the keep-best step behind it: where candidate h wins a patch its rows
 // are copied from `cand` to `out`.  Any pointer of `out` may be nullptr; cur_best, cur_lq [P] hold the state between the candidates.
 struct SelectRows {

@@ -69,19 +69,6 @@ static int irls_rules(gpc_ctx* ctx, IrlsCall& c, bool host)
     return GPC_OK;
 }
 
-// Regions of the workspace, one behind the other, each rounded up to 256 bytes; take() answers the region's byte offset (pointers are
-// formed after the reserve, which may move the workspace).
-struct WsCarve {
-    size_t bytes = 0;
-    template <class T> size_t take(size_t count)
-    {
-        const size_t at = bytes;
-        bytes += (sizeof(T) * count + 255) & ~(size_t)255;
-        return at;
-    }
-};
-template <class T> static inline T* ws_at(char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
-
 // The workspace of one fit.  Plain: a factor slot per workgroup.  With the export: a factor slot per patch | a (when the caller does not
 // take it) | s of the last solve | the variance kernel's per-wave V scratch | the grid as points | the status (when the caller does not
 // take it) | with the evidence wanted: fhat (when the caller does not take it)

@@ -888,29 +888,43 @@ static int launch_nt(gpc_ctx* ctx, hipStream_t stream, const MfmaParams& g, int 
 // Predictive variance (gaussian_process::predict_measurements, /root/reference/src/gaussian_process.cpp:35-43): the fit runs as
 // usual and additionally writes its factor (operand images of every L_ik and of the L_ii^-1) into the context's workspace,
 // 272 KB per patch at NT = 16; dense_variance.hip then evaluates V* = k** - ||L^-1 k*||^2 from there.
+static size_t mfma_factor_bytes(const DenseArgs& a, int nt_max)
+{
+    return sizeof(double) * (size_t)a.P * (nt_max * (nt_max + 1) / 2) * MF_IMG;
+}
+
+size_t dense_mfma_ws_bytes(const DenseArgs& a, const DenseRoute& r)
+{
+    if (!a.v_star && !a.log_ev) return 0;
+    // dense_variance_kernel fetches the factor in whole chunks of eight images: 10, 36 and 78 images per patch (NT = 4, 8, 12) end
+    // inside a chunk, and the last patch's last fetch reaches up to six images past the export -- one chunk of slack behind alpha
+    // keeps that read inside the workspace however few weights follow it
+    const size_t chunk_slack = sizeof(double) * 8 * MF_IMG;
+    return mfma_factor_bytes(a, r.nt) + sizeof(double) * (size_t)a.n_total * a.ny + chunk_slack;
+}
+
 int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, const DenseRoute& r)
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
+    double* log_ev = a.log_ev;
     a.v_star = nullptr;
+    a.log_ev = nullptr;
+    const bool exported = v_star || log_ev;      // the export is on for either; the variance kernel runs for v_star only
     const int nt_max = r.nt;      // (the factor is exported by the n <= 256 shapes only: 4 .. 16)
-    size_t fbytes = 0;
-    if (v_star) {
+    if (exported) {
         if (a.sel) return gpc_fail(ctx, GPC_EINVAL, "variance + size-class dispatch is not supported");
-        fbytes = sizeof(double) * (size_t)a.P * (nt_max * (nt_max + 1) / 2) * MF_IMG;
-        // dense_variance_kernel fetches the factor in whole chunks of eight images: 10, 36 and 78 images per patch (NT = 4, 8, 12) end
-        // inside a chunk, and the last patch's last fetch reaches up to six images past the export -- one chunk of slack behind alpha
-        // keeps that read inside the workspace however few weights follow it
-        const size_t chunk_slack = sizeof(double) * 8 * MF_IMG;
-        const int rc = gpc_ws_reserve(ctx, site, fbytes + sizeof(double) * (size_t)a.n_total * a.ny + chunk_slack);
+        const size_t fbytes = mfma_factor_bytes(a, nt_max);
+        const int rc = gpc_ws_reserve(ctx, site, dense_mfma_ws_bytes(a_in, r));
         if (rc != GPC_OK) return rc;
-        // the variance kernel evaluates K* anyway: it forms the mean from the same tiles, so the fit predicts nothing
-        a.m = 0;
+        // the variance kernel evaluates K* anyway: it forms the mean from the same tiles, so the fit predicts nothing (with the evidence
+        // alone the fit keeps its own prediction phase)
+        if (v_star) a.m = 0;
         if (!a.alpha_out) a.alpha_out = reinterpret_cast<double*>(dense_ws(ctx, site) + fbytes);
     }
     MfmaParams g;
     g.a = a;
-    g.export_L = v_star ? reinterpret_cast<double*>(dense_ws(ctx, site)) : nullptr;
+    g.export_L = exported ? reinterpret_cast<double*>(dense_ws(ctx, site)) : nullptr;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.pivot_tol = GPC_PIVOT_RTOL * (a.prm.sigmaf_sq + a.prm.noise);
     g.stamps = nullptr;
@@ -996,16 +1010,20 @@ int dense_mfma_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in
         }
     } tdump{site.stream, g.stamps, grid};
 #endif
-    if (v_star) {
+    if (exported) {
         int rc;
         if (nt_max == 4) rc = launch_nt<4, true>(ctx, site.stream, g, grid);
         else if (nt_max == 8) rc = launch_nt<8, true>(ctx, site.stream, g, grid);
         else if (nt_max == 12) rc = launch_nt<12, true>(ctx, site.stream, g, grid);
         else rc = launch_nt<16, true>(ctx, site.stream, g, grid);
         if (rc != GPC_OK) return rc;
-        DenseArgs av = a;
-        av.m = a_in.m;
-        return dense_variance_launch(ctx, site, av, nt_max, r.var_w4, g.export_L, a.alpha_out, v_star);
+        if (v_star) {
+            DenseArgs av = a;
+            av.m = a_in.m;
+            if ((rc = dense_variance_launch(ctx, site, av, nt_max, r.var_w4, g.export_L, a.alpha_out, v_star)) != GPC_OK) return rc;
+        }
+        // the read-out goes behind the variance kernel, which only reads the factor (see dense_big_launch)
+        return log_ev ? dense_gauss_evidence_launch(ctx, site, a, nt_max, 0, g.export_L, 0, a.alpha_out, log_ev) : GPC_OK;
     }
     switch (nt_max) {
         case 4: return launch_nt<4>(ctx, site.stream, g, grid);

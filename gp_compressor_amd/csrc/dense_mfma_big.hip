@@ -975,10 +975,11 @@ size_t dense_big_ws_bytes(const gpc_ctx* ctx, const DenseArgs& a, const DenseRou
     const int cap = ctx->num_cus * r.per_cu;
     const int grid = a.P < cap ? a.P : cap;
     if (grid_out) *grid_out = grid;
-    // with the variance requested the factor of every patch is kept (one slot per patch) + alpha + the per-wave V scratch of
-    // dense_variance_big_kernel
-    const size_t slots = a.v_star ? (size_t)a.P : (size_t)grid;
-    const size_t extra = a.v_star ? sizeof(double) * ((size_t)a.n_total * a.ny + dense_variance_big_scratch_doubles(ctx, ntw)) : 0;
+    // with the variance (or the evidence, gpc_dense_fit_predict_ev) requested the factor of every patch is kept (one slot per patch)
+    // + alpha + the per-wave V scratch of dense_variance_big_kernel
+    const bool exported = a.v_star || a.log_ev;
+    const size_t slots = exported ? (size_t)a.P : (size_t)grid;
+    const size_t extra = exported ? sizeof(double) * ((size_t)a.n_total * a.ny + dense_variance_big_scratch_doubles(ctx, ntw)) : 0;
     return sizeof(double) * big_slot_doubles(ntw) * slots + extra;
 }
 
@@ -1025,18 +1026,23 @@ int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in,
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
+    double* log_ev = a.log_ev;
+    const bool exported = v_star || log_ev;      // the export is on for either; the variance kernel runs for v_star only
+    if (exported && r.npad == 256) return gpc_fail(ctx, GPC_EINVAL, "the 256-point shapes of the tiled kernel have no read-out of their factor");
     const int ntw_ = (a.n_max + MF_TS - 1) / MF_TS;
     double* ws_alpha = nullptr;
-    if (v_star) {
-        // the variance kernel forms the mean from the same K* tiles: the fit predicts nothing, and leaves alpha behind
+    if (exported) {
+        // the variance kernel forms the mean from the same K* tiles: the fit predicts nothing, and leaves alpha behind (with the evidence
+        // alone the fit keeps its own prediction phase)
         ws_alpha = reinterpret_cast<double*>(dense_ws(ctx, site)) + big_slot_doubles(ntw_) * (size_t)a.P;
         a.v_star = nullptr;
-        a.m = 0;
+        a.log_ev = nullptr;
+        if (v_star) a.m = 0;
         if (!a.alpha_out) a.alpha_out = ws_alpha;
     }
     BigParams g;
     g.a = a;
-    g.export_factor = v_star ? 1 : 0;
+    g.export_factor = exported ? 1 : 0;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.pivot_tol = GPC_PIVOT_RTOL * (a.prm.sigmaf_sq + a.prm.noise);
     g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
@@ -1074,9 +1080,13 @@ int dense_big_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in,
     if (waves == 4 && npad == 256) return big_launch_t<4, 256, 2, 2>(ctx, site.stream, g, grid);
     const int rc = waves == 4 ? big_launch_t<4, 512, 2, 2, false, 1>(ctx, site.stream, g, grid)
                               : big_launch_t<8, 1024, 2, 2>(ctx, site.stream, g, grid);
-    if (rc != GPC_OK || !v_star) return rc;
-    DenseArgs av = a;
-    av.m = a_in.m;
-    return dense_variance_big_launch(ctx, site, av, g.ntw, g.ws, g.slot, a.alpha_out,
-                                     ws_alpha + (size_t)a.n_total * a.ny, v_star);
+    if (rc != GPC_OK || !exported) return rc;
+    if (v_star) {
+        DenseArgs av = a;
+        av.m = a_in.m;
+        if (const int rcv = dense_variance_big_launch(ctx, site, av, g.ntw, g.ws, g.slot, a.alpha_out, ws_alpha + (size_t)a.n_total * a.ny, v_star))
+            return rcv;
+    }
+    // the read-out goes BEHIND the variance kernel, which only reads the factor: in front of it, it delayed that kernel's start
+    return log_ev ? dense_gauss_evidence_launch(ctx, site, a, 0, g.ntw, g.ws, g.slot, a.alpha_out, log_ev) : GPC_OK;
 }

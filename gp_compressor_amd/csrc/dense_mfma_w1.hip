@@ -860,25 +860,29 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, 
 {
     DenseArgs a = a_in;
     double* v_star = a.v_star;
+    double* log_ev = a.log_ev;
     a.v_star = nullptr;
+    a.log_ev = nullptr;
+    const bool exported = v_star || log_ev;           // the export is on for either; the variance kernel runs for v_star only
     W1Params g;
     g.c_exp = (double)(-0.5f) / a.prm.l_sq;
     g.ws = reinterpret_cast<double*>(dense_ws(ctx, site));
     const int npad = r.w1_npad;
     g.linvt = g.ws + (size_t)W1_TRI_OF(npad) * MF_IMG * (size_t)grid;
-    g.export_factor = v_star ? 1 : 0;
+    g.export_factor = exported ? 1 : 0;
     const double sf = a.prm.sigmaf_sq;
-    const bool unit = !v_star;                        // unit scale (see the kernel) unless the factor is exported
+    const bool unit = !exported;                      // unit scale (see the kernel) unless the factor is exported
     g.cs = sqrt(-g.c_exp);
     g.noise_u = unit ? a.prm.noise / sf : a.prm.noise;
     g.pivot_tol = GPC_PIVOT_RTOL * (unit ? 1.0 + a.prm.noise / sf : sf + a.prm.noise);
     g.sfp = unit ? 1.0 : sf;
     g.a_out = unit ? 1.0 / sf : 1.0;
     g.stamps = nullptr;
-    if (v_star) {
+    if (exported) {
         // Predictive variance (gaussian_process::predict_measurements, /root/reference/src/gaussian_process.cpp:35-43): the slots are the
-        // factor export dense_variance_kernel<16> reads, the fit predicts nothing (the solve forms the mean from the same K* tiles)
-        a.m = 0;
+        // factor export dense_variance_kernel<16> reads, the fit predicts nothing (the solve forms the mean from the same K* tiles).
+        // With the evidence alone (gpc_dense_fit_predict_ev) the fit keeps its own prediction phase.
+        if (v_star) a.m = 0;
         if (!a.alpha_out) a.alpha_out = g.linvt + (size_t)W1_LNV_OF(npad) * MF_IMG * (size_t)grid;
     }
 #ifdef W1_STAMPS
@@ -903,6 +907,11 @@ int dense_w1_launch(gpc_ctx* ctx, const DenseSite& site, const DenseArgs& a_in, 
             DenseArgs av = g.a;
             av.m = a_in.m;
             const int rc = dense_variance_launch(ctx, site, av, W1_NT_OF(256), r.var_w4, g.ws, a.alpha_out, v_star + (size_t)base * a_in.m);
+            if (rc != GPC_OK) return rc;
+        }
+        // the read-out of this launch's slots, behind the variance kernel (which only reads them) and before the next launch reuses them
+        if (log_ev) {
+            const int rc = dense_gauss_evidence_launch(ctx, site, g.a, W1_NT_OF(256), 0, g.ws, 0, a.alpha_out, log_ev + (size_t)base * a.ny);
             if (rc != GPC_OK) return rc;
         }
     }

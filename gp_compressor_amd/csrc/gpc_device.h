@@ -390,3 +390,13 @@ __device__ static inline void gpc_probit_q_r(int model, double s20, double y, do
     const double first = efprim / ef;                             // :29
     *r = (efprimprim / ef - first * first) / sigma2;              // :30
 }
+
+// ---- the evidence read-outs (dense_evidence.hip, and the generic kernel's own in dense_generic.hip): the one order of their sums ------
+// the 64 lanes' values in one fixed order; every lane gets the sum
+__device__ static __forceinline__ double ev_wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+#define EV_HALF_LOG_2PI 0.91893853320467274178   // 0.5 log(2 pi)

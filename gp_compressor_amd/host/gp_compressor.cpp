@@ -288,6 +288,9 @@ void gp_compressor::drop_dense_grids()
 
 void gp_compressor::set_devices(const std::vector<int>& devices)
 {
+    if (!devices.empty() && (!dense_cand_depth_.empty() || !dense_cand_rgb_.empty()))
+        throw std::runtime_error("set_devices: dense candidates are set; per-leaf selection runs in the single-device flows only "
+                                 "(set_dense_candidates({}, {}) first)");
     for (gpc_sparse* q : shard_gps_) if (q) gpc_sparse_destroy(q);
     for (gpc_sparse* q : shard_rgb_) if (q) gpc_sparse_destroy(q);
     shard_gps_.clear();
@@ -634,6 +637,36 @@ void gp_compressor::shuffle(std::vector<int32_t>& perm, int n)
     }
 }
 
+static const char* const dense_candidates_sharded =
+    "dense candidates and set_devices() do not combine: gpc_dense_select runs every candidate on the device that holds the patch, and the "
+    "sharded flow balances its partition for one fit per patch -- clear one of the two";
+
+void gp_compressor::set_dense_candidates(const std::vector<gpc_hyper>& depth, const std::vector<gpc_hyper>& rgb)
+{
+    if ((!depth.empty() || !rgb.empty()) && !devices_.empty()) throw std::runtime_error(dense_candidates_sharded);
+    dense_cand_depth_ = depth;
+    dense_cand_rgb_ = rgb;
+}
+
+void gp_compressor::dense_plane(bool on_device, const std::vector<gpc_hyper>& cand, const int32_t* off, int n_max, int n_total,
+                                const double* x0, const double* x1, const double* y, int ny, double* grid, int32_t* status, int32_t* best,
+                                double* ev, const char* what)
+{
+    const int P = batch_.patches(), H = (int)cand.size();
+    const std::string tag = std::string(H ? (on_device ? "gpc_dense_select_dev(" : "gpc_dense_select(")
+                                          : (on_device ? "gpc_dense_fit_predict_grid_dev(" : "gpc_dense_fit_predict_grid(")) + what + ")";
+    int rc;
+    if (H == 0)
+        rc = on_device ? gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, off, n_max, n_total, x0, x1, y, ny, res_, sz_, grid, nullptr, status)
+                       : gpc_dense_fit_predict_grid(ctx_, &dense_params, P, off, x0, x1, y, ny, res_, sz_, grid, nullptr, status);
+    else
+        rc = on_device ? gpc_dense_select_dev(ctx_, &dense_params, H, cand.data(), P, off, n_max, n_total, x0, x1, y, ny, 0, nullptr, nullptr,
+                                              res_, sz_, grid, nullptr, nullptr, ev, best, nullptr, status)
+                       : gpc_dense_select(ctx_, &dense_params, H, cand.data(), P, off, x0, x1, y, ny, 0, nullptr, nullptr, res_, sz_, grid,
+                                          nullptr, nullptr, ev, best, nullptr, status);
+    check(rc, ctx_, tag.c_str());
+}
+
 // src/gp_compressor.cpp:121-175, batched
 void gp_compressor::train_processes()
 {
@@ -647,15 +680,27 @@ void gp_compressor::train_processes()
     const bool on_device = dev_patches_ != nullptr;
     if (on_device) gpc_patches_view_dev(dev_patches_, &dv);
     if (model_ == gp_model::dense) {
+        const bool sel_d = !dense_cand_depth_.empty(), sel_c = !dense_cand_rgb_.empty();
+        if ((sel_d || sel_c) && !devices_.empty()) throw std::runtime_error(dense_candidates_sharded);
+        dense_best_depth_.clear();
+        dense_best_rgb_.clear();
+        dense_ev_depth_.clear();
+        if (sel_d) { dense_best_depth_.assign(P, -1); dense_ev_depth_.assign(P, 0.0); }
+        if (sel_c) dense_best_rgb_.assign(P, -1);
         if (on_device) {
             // depth and colour grids predicted straight from the device batch; they stay in HBM for load_compressed()
             drop_dense_grids();
             dev_buf f(ctx_, sizeof(double) * (size_t)P * m), c(ctx_, sizeof(double) * (size_t)P * 3 * m), st(ctx_, sizeof(int32_t) * (size_t)P);
-            check(gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.y, 1, res_, sz_,
-                                                 f.as<double>(), nullptr, st.as<int32_t>()), ctx_, "gpc_dense_fit_predict_grid_dev(depth)");
-            check(gpc_dense_fit_predict_grid_dev(ctx_, &dense_params, P, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.rgb, 3, res_, sz_,
-                                                 c.as<double>(), nullptr, st.as<int32_t>()), ctx_, "gpc_dense_fit_predict_grid_dev(rgb)");
+            dev_buf bd, bc, ev;
+            if (sel_d) { bd = dev_buf(ctx_, sizeof(int32_t) * (size_t)P); ev = dev_buf(ctx_, sizeof(double) * (size_t)P); }
+            if (sel_c) bc = dev_buf(ctx_, sizeof(int32_t) * (size_t)P);
+            dense_plane(true, dense_cand_depth_, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.y, 1, f.as<double>(), st.as<int32_t>(),
+                        bd.as<int32_t>(), ev.as<double>(), "depth");
+            dense_plane(true, dense_cand_rgb_, dv.off, dv.n_max, dv.n_total, dv.x0, dv.x1, dv.rgb, 3, c.as<double>(), st.as<int32_t>(),
+                        bc.as<int32_t>(), nullptr, "rgb");
             st.download(status_.data(), sizeof(int32_t) * (size_t)P);
+            if (sel_d) { bd.download(dense_best_depth_.data(), sizeof(int32_t) * (size_t)P); ev.download(dense_ev_depth_.data(), sizeof(double) * (size_t)P); }
+            if (sel_c) bc.download(dense_best_rgb_.data(), sizeof(int32_t) * (size_t)P);
             d_dense_f_ = f.release<double>();         // kept only once both grids exist
             d_dense_c_ = c.release<double>();
         } else if (!devices_.empty()) {
@@ -663,12 +708,10 @@ void gp_compressor::train_processes()
         } else {
             dense_f_.assign((size_t)P * m, 0.0);
             dense_c_.assign((size_t)P * 3 * m, 0.0);
-            check(gpc_dense_fit_predict_grid(ctx_, &dense_params, P, batch_.off.data(), batch_.x0.data(), batch_.x1.data(),
-                                             batch_.y.data(), 1, res_, sz_, dense_f_.data(), nullptr, status_.data()),
-                  ctx_, "gpc_dense_fit_predict_grid(depth)");
-            check(gpc_dense_fit_predict_grid(ctx_, &dense_params, P, batch_.off.data(), batch_.x0.data(), batch_.x1.data(),
-                                             batch_.rgb.data(), 3, res_, sz_, dense_c_.data(), nullptr, status_.data()),
-                  ctx_, "gpc_dense_fit_predict_grid(rgb)");
+            dense_plane(false, dense_cand_depth_, batch_.off.data(), 0, 0, batch_.x0.data(), batch_.x1.data(), batch_.y.data(), 1,
+                        dense_f_.data(), status_.data(), dense_best_depth_.data(), dense_ev_depth_.data(), "depth");
+            dense_plane(false, dense_cand_rgb_, batch_.off.data(), 0, 0, batch_.x0.data(), batch_.x1.data(), batch_.rgb.data(), 3,
+                        dense_c_.data(), status_.data(), dense_best_rgb_.data(), nullptr, "rgb");
         }
         mean_added_ = 0;
         max_added_ = 0;
@@ -1383,9 +1426,36 @@ int gpc_host_project_device(void* h, char* err, int errlen)
     try { static_cast<gpc::gp_compressor*>(h)->project_cloud_device(); return 0; }
     catch (const std::exception& e) { return fail(e, err, errlen); }
 }
-void gpc_host_set_devices(void* h, const int* devices, int n)
+int gpc_host_set_devices(void* h, const int* devices, int n, char* err, int errlen)
 {
-    static_cast<gpc::gp_compressor*>(h)->set_devices(std::vector<int>(devices, devices + (n > 0 ? n : 0)));
+    try { static_cast<gpc::gp_compressor*>(h)->set_devices(std::vector<int>(devices, devices + (n > 0 ? n : 0))); return 0; }
+    catch (const std::exception& e) { return fail(e, err, errlen); }
+}
+// candidates as (sigmaf_sq, l_sq, noise) triples, nd for the depth plane and nc for the colour planes (0: that plane keeps dense_params)
+int gpc_host_set_dense_candidates(void* h, const double* depth, int nd, const double* rgb, int nc, char* err, int errlen)
+{
+    try {
+        std::vector<gpc_hyper> d, c;
+        for (int i = 0; i < nd; ++i) d.push_back(gpc_hyper{depth[3 * i], depth[3 * i + 1], depth[3 * i + 2]});
+        for (int i = 0; i < nc; ++i) c.push_back(gpc_hyper{rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]});
+        static_cast<gpc::gp_compressor*>(h)->set_dense_candidates(d, c);
+        return 0;
+    } catch (const std::exception& e) { return fail(e, err, errlen); }
+}
+// which: 0 dense_best_depth, 1 dense_best_rgb; returns the length (0 without candidates); out may be NULL to ask for it
+int gpc_host_dense_best(void* h, int which, int32_t* out)
+{
+    const auto* g = static_cast<gpc::gp_compressor*>(h);
+    const std::vector<int32_t>& v = which ? g->dense_best_rgb() : g->dense_best_depth();
+    if (out && !v.empty()) std::memcpy(out, v.data(), sizeof(int32_t) * v.size());
+    return (int)v.size();
+}
+const char* gpc_host_last_dense_kernel(void* h) { return static_cast<gpc::gp_compressor*>(h)->last_dense_kernel(); }
+int gpc_host_dense_evidence_depth(void* h, double* out)
+{
+    const std::vector<double>& v = static_cast<gpc::gp_compressor*>(h)->dense_evidence_depth();
+    if (out && !v.empty()) std::memcpy(out, v.data(), sizeof(double) * v.size());
+    return (int)v.size();
 }
 void gpc_host_set_gpu_producer(void* h, int on) { static_cast<gpc::gp_compressor*>(h)->gpu_producer = on != 0; }
 int gpc_host_patch_count(void* h) { return static_cast<gpc::gp_compressor*>(h)->patches().patches(); }

@@ -147,6 +147,19 @@ public:
     // of a patch live on ITS device from train_processes() to load_compressed() (fixed affinity: the state never moves), which
     // predicts per device and gathers the grids once.
     void set_devices(const std::vector<int>& devices);
+    // Dense model: per-leaf hyper-parameter selection by the log marginal likelihood (gpc_dense_select, include/gpc.h).  With candidates
+    // set for a plane, train_processes() fits every leaf under each of them -- sigmaf_sq, l_sq and noise over dense_params -- and keeps
+    // the grid of the one with the largest evidence (the colour plane decides by the sum over its three channels); an empty vector
+    // leaves that plane at dense_params, and with both empty nothing changes.  Single-device flows only: the sharded flow deals
+    // patches to devices that each would have to run every candidate, so candidates together with set_devices() throw.
+    void set_dense_candidates(const std::vector<gpc_hyper>& depth, const std::vector<gpc_hyper>& rgb);
+    // per leaf, after train_processes(): the winning candidate of the plane (-1: none was eligible; empty without candidates) and the
+    // winner's log marginal likelihood of the depth plane
+    const std::vector<int32_t>& dense_best_depth() const { return dense_best_depth_; }
+    const std::vector<int32_t>& dense_best_rgb() const { return dense_best_rgb_; }
+    const std::vector<double>& dense_evidence_depth() const { return dense_ev_depth_; }
+    // name of the kernels the last dense call of this object's context ran ("" before any): gpc_last_dense_kernel
+    const char* last_dense_kernel() const { return ctx_ ? gpc_last_dense_kernel(ctx_) : ""; }
     // insertion-order source; default std::rand like sparse_gp::shuffle (src/sparse_gp.hpp:43-56)
     std::function<int()> rng;
     // hyper-parameters (defaults = the reference's compile-time constants)
@@ -178,6 +191,13 @@ protected:
     void release_device();
     void drop_dense_grids();
     void train_dense_sharded();
+    std::vector<gpc_hyper> dense_cand_depth_, dense_cand_rgb_;     // set_dense_candidates()
+    std::vector<int32_t> dense_best_depth_, dense_best_rgb_;
+    std::vector<double> dense_ev_depth_;
+    // one plane of the dense model on the whole batch, device or host pointers throughout: gpc_dense_select[_dev] in the grid form when
+    // the plane has candidates (best [P] and, when ev != nullptr, the winner's log_ev [P][ny] are written), else the plain grid entry
+    void dense_plane(bool on_device, const std::vector<gpc_hyper>& cand, const int32_t* off, int n_max, int n_total, const double* x0,
+                     const double* x1, const double* y, int ny, double* grid, int32_t* status, int32_t* best, double* ev, const char* what);
     void init_shards();
     void train_sparse_sharded(const std::vector<int32_t>& perm_d, const std::vector<int32_t>& perm_c);
     void predict_sparse_sharded(const std::vector<double>& xs0, const std::vector<double>& xs1, std::vector<double>& f_star,

@@ -37,7 +37,12 @@ def load():
         L.gpc_host_project.argtypes = [vp]
         L.gpc_host_project_device.argtypes = [vp, vp, i]
         L.gpc_host_set_gpu_producer.argtypes = [vp, i]
-        L.gpc_host_set_devices.argtypes = [vp, vp, i]
+        L.gpc_host_set_devices.argtypes = [vp, vp, i, vp, i]
+        L.gpc_host_set_dense_candidates.argtypes = [vp, vp, i, vp, i, vp, i]
+        L.gpc_host_dense_best.argtypes = [vp, i, vp]
+        L.gpc_host_dense_evidence_depth.argtypes = [vp, vp]
+        L.gpc_host_last_dense_kernel.restype = C.c_char_p
+        L.gpc_host_last_dense_kernel.argtypes = [vp]
         L.gpc_host_patch_count.argtypes = [vp]
         L.gpc_host_point_count.argtypes = [vp]
         L.gpc_host_get_batch.argtypes = [vp] * 9
@@ -87,7 +92,41 @@ class GpCompressor:
     def set_devices(self, devices):
         """multi-GPU mode of the dense model: one process drives these devices (gp_compressor::set_devices); [] switches it off"""
         d = np.ascontiguousarray(devices, dtype=np.int32)
-        self.L.gpc_host_set_devices(self.h, d.ctypes.data if len(d) else None, len(d))
+        err = C.create_string_buffer(512)
+        if self.L.gpc_host_set_devices(self.h, d.ctypes.data if len(d) else None, len(d), C.addressof(err), 512) != 0:
+            raise RuntimeError(f"set_devices failed: {err.value.decode()}")
+
+    def set_dense_candidates(self, depth=(), rgb=()):
+        """dense model: per-leaf hyper-parameter selection by the log marginal likelihood (gp_compressor::set_dense_candidates);
+        depth, rgb: (sigmaf_sq, l_sq, noise) triples, an empty list leaves that plane at dense_params.  Before training."""
+        d = np.ascontiguousarray(depth, dtype=np.float64).reshape(-1, 3)
+        c = np.ascontiguousarray(rgb, dtype=np.float64).reshape(-1, 3)
+        err = C.create_string_buffer(512)
+        if self.L.gpc_host_set_dense_candidates(self.h, d.ctypes.data if len(d) else None, len(d), c.ctypes.data if len(c) else None, len(c),
+                                                C.addressof(err), 512) != 0:
+            raise RuntimeError(f"set_dense_candidates failed: {err.value.decode()}")
+
+    def _dense_best(self, which):
+        out = np.zeros(self.L.gpc_host_dense_best(self.h, which, None), dtype=np.int32)
+        self.L.gpc_host_dense_best(self.h, which, out.ctypes.data if len(out) else None)
+        return out
+
+    def dense_best_depth(self):
+        """per leaf, after training with depth candidates: the winner's index (-1: no candidate eligible); empty without candidates"""
+        return self._dense_best(0)
+
+    def dense_best_rgb(self):
+        return self._dense_best(1)
+
+    def last_dense_kernel(self):
+        """the kernels the object's last dense call ran (gpc_last_dense_kernel of its context)"""
+        return self.L.gpc_host_last_dense_kernel(self.h).decode()
+
+    def dense_evidence_depth(self):
+        """per leaf, after training with depth candidates: the winner's log marginal likelihood"""
+        out = np.zeros(self.L.gpc_host_dense_evidence_depth(self.h, None), dtype=np.float64)
+        self.L.gpc_host_dense_evidence_depth(self.h, out.ctypes.data if len(out) else None)
+        return out
 
     def set_sparse_kernel(self, sigmaf_sq, l_sq, s20_depth, s20_rgb, capacity):
         self.L.gpc_host_set_sparse_kernel(self.h, sigmaf_sq, l_sq, s20_depth, s20_rgb, capacity)

@@ -158,6 +158,95 @@ int gpc_dense_fit_predict_grid_dev(gpc_ctx* ctx, const gpc_params* params, int P
  * The other columns of a call with a non-finite X* agree with the clean call to rounding, not to the bit (the variance kernel bounds
  * its exponential by the extent of all of X*). */
 
+/* ... with the log marginal likelihood log p(y | X, theta) (Rasmussen & Williams 2006, Alg. 2.1 line 7, eq. 2.30): what tells whether
+ * sigmaf_sq, l_sq and noise fit the data of a patch.
+ * Definition.  Let A be the matrix the fit factorises, K + noise I, or K + 2 noise I with ref_double_noise, and L its Cholesky factor.
+ * Per patch i of n points and per target plane c
+ *     log_ev[i][c] = -0.5 sum_j y_c[j] alpha_c[j]  -  sum_{j<n} log L_jj  -  0.5 n log(2 pi)
+ *   - the padding rows j >= n of the last tile are never summed;
+ *   - each sum has one fixed order: point j goes to lane j mod 64 of one wave, then a fixed shuffle tree; no atomics.  From the same
+ *     alpha and factor two calls give the same bits: that is every call on the one-wave, the tiled and the generic kernel.  The register
+ *     kernel (n_max <= 256 below the one-wave kernel's batch size, and every ny == 3 batch of that size) forms alpha with LDS atomic adds
+ *     in no fixed order, so there alpha_out, f_star and the y^T alpha term repeat to a rounding or two, as in gpc_dense_fit_predict; the
+ *     factor, v_star and sum log L_jj repeat bit for bit on every route;
+ *   - an empty patch gives 0;
+ *   - status GPC_STATUS_NOT_SPD (and GPC_STATUS_NAN) gives NaN in every plane;
+ *   - a non-finite y in plane c gives a non-finite log_ev[i][c] and leaves the other planes as they are;
+ *   - L_jj = 1 / (L_kk^-1)_jj is read from the L_kk^-1 image of tile k = j / 16 that the fit exported, so -log L_jj is taken as
+ *     log (L_kk^-1)_jj, as the probit read-out below does.  (Under GPC_FORCE_GENERIC the generic kernel forms the same sums from its own
+ *     pivots, without any export: the value the other routes are cross-checked against.)
+ * Arguments: those of gpc_dense_fit_predict[_dev], plus res, sz and log_ev [P][ny].  X* is point-wise (xs0, xs1, m) or, when xs0 == NULL,
+ * the sz x sz grid of load_compressed (res, sz; m is ignored, m = sz sz, cell p = y sz + x).  The variance kernels have no separable
+ * form, so the library materialises the grid as m points in its workspace and evaluates point-wise throughout: f_star may differ from
+ * gpc_dense_fit_predict_grid[_dev] by O(1 ulp) per kernel value.
+ * A call with log_ev takes the variance route with the factor export on, whatever params->want_variance says: a caller who wants v_star
+ * passes it, and NULL means no variance.
+ *   - log_ev == NULL: the call IS gpc_dense_fit_predict[_dev] (point-wise form; grid form without a variance to compute:
+ *     gpc_dense_fit_predict_grid[_dev]): the same launches, the same bits.
+ *   - log_ev and v_star: f_star, v_star and alpha_out are bit for bit those of gpc_dense_fit_predict_dev with want_variance = 1.
+ *   - log_ev without v_star: the fit runs with the export on and predicts f_star itself; no variance kernel runs, so the call costs a
+ *     fit, not a fit plus an n^2 m solve.  f_star and alpha_out are the export-on fit's own: correct to the tolerances of the plain entry,
+ *     not held to its bits (the one-wave kernel factorises K / sigmaf_sq without the export and K itself with it).
+ *   - m == 0 is allowed: the call returns the evidence (and alpha_out, status) only.
+ * Rules, checked in this order; the first one broken decides the code, and no output is written on an error:
+ *   1. ctx NULL or dead                                                                              GPC_EINVAL (no text)
+ *   2. params NULL
+ *   3. select only: H < 1 or cand NULL; a candidate with a non-finite field, sigmaf_sq <= 0, l_sq <= 0 or noise < 0
+ *   4. grid form (xs0 == NULL): sz outside 0 .. 1024
+ *   5. host forms only: P < 0; off NULL with P > 0; off[0] != 0 or off decreasing
+ *   6. the dense rules: a negative size; ny not 1 or 3; off, x0, x1 or y NULL where there is something to read; f_star NULL with P > 0
+ *      and m > 0 (not under select, whose every output may be NULL); n_max > GPC_MAX_POINTS: GPC_ERANGE; l_sq <= 0, sigmaf_sq < 0 or
+ *      noise < 0
+ *   7. point-wise form: xs1 NULL with m > 0
+ *   8. P == 0: GPC_OK, nothing is launched and nothing written
+ * Everything but the one GPC_ERANGE is GPC_EINVAL.
+ * Workspace.  In front: a status word per patch when status == NULL, alpha (ny n_total + 1 doubles) when alpha_out == NULL and m == 0
+ * (with something to predict the kernels keep alpha in their own region, counted below), the grid
+ * points (2 m doubles) in the grid form, each rounded up to 256 bytes; behind them what the route's kernel keeps for the variance path,
+ * with nt = 4 ceil(n_max / 64), ntw = ceil(n_max / 16), slot(ntw) = 256 ((ntw + 1) ntw + 2 ntw):
+ *     n_max <= 256, register kernel:    8 (128 nt (nt + 1) P + ny n_total + 2048)
+ *     193 .. 256 points, one-wave:      8 (38912 min(P, 8192) + n_total)          (ny == 1, batches of at least four patches per CU)
+ *     257 .. 1024 points, tiled kernel: 8 (slot(ntw) P + ny n_total + 2048 CUs ntw)
+ *     GPC_FORCE_GENERIC:                8 ((n_max + ny)^2 + n_max ceil64(m) [with v_star]) per resident workgroup
+ * A refusal returns GPC_ENOMEM.  The batch is not chunked beyond what the one-wave launcher already does (launches of at most 8192
+ * patches that reuse the slots; the read-out follows each launch), and where only the one-wave kernel's workspace is refused the call
+ * stays GPC_ENOMEM.  The _dev form enqueues on the context's stream and never synchronises; the host form stages its arguments through
+ * device buffers of its own and returns when the outputs are in host memory. */
+int gpc_dense_fit_predict_ev(gpc_ctx* ctx, const gpc_params* params, int P, const int32_t* off, const double* x0, const double* x1,
+                             const double* y, int ny, int m, const double* xs0, const double* xs1, double res, int sz, double* f_star,
+                             double* v_star, double* alpha_out, int32_t* status, double* log_ev);
+int gpc_dense_fit_predict_ev_dev(gpc_ctx* ctx, const gpc_params* params, int P, const int32_t* off, int n_max, int n_total,
+                                 const double* x0, const double* x1, const double* y, int ny, int m, const double* xs0, const double* xs1,
+                                 double res, int sz, double* f_star, double* v_star, double* alpha_out, int32_t* status, double* log_ev);
+/* Model selection among H candidate hyper-parameter sets, per patch, by that evidence.  params is the base; for candidate h its
+ * sigmaf_sq, l_sq and noise are replaced by cand[h]'s (struct gpc_hyper).  cand is a HOST array of H >= 1 entries, read at call
+ * time, in the _dev form too.
+ * Rule per patch.  The deciding value is sum_c log_ev[c], taken in plane order.  Candidate h is eligible iff its fit ended with
+ * GPC_STATUS_OK and that sum is finite.  best is the lowest h that attains the maximum over the eligible candidates (the comparison is a
+ * strict >: ties and duplicates go to the lower index, a NaN never wins).  Every output of the patch is the winner's, bit for bit what
+ * gpc_dense_fit_predict_ev[_dev] gives with that candidate's parameters and the same outputs requested.  With no eligible candidate
+ * best = -1, f*, v*, alpha and log_ev are NaN and status is candidate 0's.  An empty patch has log_ev = 0 under every candidate:
+ * best = 0 with candidate 0's outputs, f* = 0 and v* = cand[0].sigmaf_sq.
+ * Outputs, each may be NULL: f_star [P][ny][m], v_star [P][m], alpha_out [ny][n_total], log_ev [P][ny], best [P],
+ * log_ev_all [H][P][ny] (every candidate's log_ev), status [P].
+ * The candidates run one after another on the context's stream into temporaries in the workspace, and after each a keep-best kernel
+ * copies the rows of the patches it won so far into the outputs.  Workspace: that of gpc_dense_fit_predict_ev[_dev] with alpha_out and
+ * status given, plus the temporaries and the state of the keep-best step --
+ *     bytes = ev_bytes + 8 (ny P m + 1 + [P m with v_star] + ny n_total + 1 + ny P + P) + 4 (2 P)
+ * (each term rounded up to 256 bytes); a refusal returns GPC_ENOMEM.  The _dev form never synchronises.
+ * Errors: rule 3 above, then the shared rules. */
+typedef struct gpc_hyper {
+    double sigmaf_sq, l_sq, noise;
+} gpc_hyper;
+int gpc_dense_select(gpc_ctx* ctx, const gpc_params* params, int H, const gpc_hyper* cand, int P, const int32_t* off,
+                     const double* x0, const double* x1, const double* y, int ny, int m, const double* xs0, const double* xs1, double res,
+                     int sz, double* f_star, double* v_star, double* alpha_out, double* log_ev, int32_t* best, double* log_ev_all,
+                     int32_t* status);
+int gpc_dense_select_dev(gpc_ctx* ctx, const gpc_params* params, int H, const gpc_hyper* cand, int P, const int32_t* off, int n_max,
+                         int n_total, const double* x0, const double* x1, const double* y, int ny, int m, const double* xs0,
+                         const double* xs1, double res, int sz, double* f_star, double* v_star, double* alpha_out, double* log_ev,
+                         int32_t* best, double* log_ev_all, int32_t* status);
+
 /* ---- dense GP with the probit functor: Newton / IRLS loop on the GPU (BASELINE config 5) ---------------------------- */
 /* The reference never instantiates probit_noise and holds no IRLS loop (its occupancy map is a ray-cast boolean mask,
  * src/gp_mapping.cpp:154-211 -- gpc_patches_raycast + gpc_occupancy_batch_dev below turn it into this entry's labels): what it fixes is the Noise contract, q = dx_ln(y, x, sigma_x), r = dx2_ln(y, x, sigma_x)
@@ -280,9 +369,7 @@ int gpc_dense_irls_fit_predict_ev_dev(gpc_ctx* ctx, const gpc_params* params, co
  *     bytes = ev_bytes + 8 (3 P m + 2 n_total + 2 P) + 4 (3 P)
  * (each term rounded up to 256 bytes); not chunked over patches, a refusal returns GPC_ENOMEM.  The _dev form never synchronises.
  * Errors: rule 3 above, then the shared rules. */
-typedef struct gpc_hyper {
-    double sigmaf_sq, l_sq, noise;
-} gpc_hyper;
+/* (struct gpc_hyper: with gpc_dense_select above) */
 int gpc_dense_irls_select(gpc_ctx* ctx, const gpc_params* params, const gpc_irls_params* irls, int H, const gpc_hyper* cand, int P,
                           const int32_t* off, const double* x0, const double* x1, const double* y, int m, const double* xs0,
                           const double* xs1, double res, int sz, double* f_star, double* v_star, double* p_star, double* alpha_out,
