@@ -270,9 +270,8 @@ int gpc_sparse_decode_dev(gpc_sparse* depth, gpc_sparse* rgb, double res, int sz
                           const double* rotations, const double* means, const double* rgb_means, int capacity, gpc_point_xyzrgb* cloud,
                           int32_t* leaf, int32_t* point, int32_t* count, int32_t* n_points)
 {
-    if (!depth) return GPC_EINVAL;
-    gpc_ctx* ctx = depth->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    gpc_ctx* ctx = sp_live(depth);
+    if (!ctx) return GPC_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (int rc = dc_check(ctx, depth, rgb, res, sz, rotations, means, rgb_means, capacity, cloud, n_points)) return rc;
     GPC_HIP(ctx, hipSetDevice(ctx->device));
@@ -317,9 +316,8 @@ int gpc_sparse_decode(gpc_sparse* depth, gpc_sparse* rgb, double res, int sz, co
                       const double* means, const double* rgb_means, int capacity, gpc_point_xyzrgb* cloud, int32_t* leaf, int32_t* point,
                       int32_t* count, int32_t* n_points)
 {
-    if (!depth) return GPC_EINVAL;
-    gpc_ctx* ctx = depth->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    gpc_ctx* ctx = sp_live(depth);
+    if (!ctx) return GPC_EINVAL;
     size_t Pz = 0;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);

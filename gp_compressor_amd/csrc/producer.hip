@@ -37,6 +37,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "producer_internal.h"   // (switches floating-point contraction off)
+#include "sparse_internal.h"     // sp_live
 
 // ---- 1: bounds; 2: keys, leaf table (PcGrid and the key arithmetic: producer_internal.h) -------------------------------------
 // out[0..2] = ordered min, out[3..5] = ordered max, out[6] = 1 if a coordinate is not finite
@@ -657,9 +658,8 @@ int gpc_patches_view_dev(const gpc_patches* p, gpc_patches_view* view)
 int gpc_patches_fetch(const gpc_patches* p, int32_t* off, double* x0, double* x1, double* y, double* rgb, double* rotations,
                       double* means, double* rgb_means, uint8_t* W, int32_t* src)
 {
-    if (!p) return GPC_EINVAL;
-    gpc_ctx* ctx = p->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the batch can only be destroyed
+    gpc_ctx* ctx = sp_live(p);
+    if (!ctx) return GPC_EINVAL;
     GPC_HIP(ctx, hipSetDevice(ctx->device));
     const gpc_patches_view& v = p->v;
     const size_t P = (size_t)v.P, N = (size_t)v.n_total;

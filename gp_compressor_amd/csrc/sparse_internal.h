@@ -24,8 +24,13 @@ struct gpc_sparse {
 // so finite data keeps its bits) and NaN when a coordinate is NaN or +-inf (X - X = NaN): no select, three operations.
 __device__ static __forceinline__ double sp_kstar(double sf, double x0, double x1) { return sf + ((x0 - x0) + (x1 - x1)); }
 
-// ---- launchers implemented beside their kernels.  The caller (sparse_api.hip) has checked the arguments, holds ctx->mu, has set the
-// device and made the poison call; all pointers are device pointers.
+// The live context of an object of the C-ABI (gpc_sparse, gpc_patches), or nullptr: the object is NULL, or the context went first and the
+// object can only be destroyed (include/gpc.h).  The first question of every entry that takes an object.
+template <class Object> static inline gpc_ctx* sp_live(const Object* g) { return g && !g->ctx->dead.load() ? g->ctx : nullptr; }
+
+// ---- launchers implemented beside their kernels.  The caller has checked the arguments (the *_rules of sparse_api.hip) and is inside
+// sp_locked (sparse_api.hip), which holds ctx->mu, has set the device and made the poison call; a caller elsewhere (render.hip,
+// sparse_scatter.hip) has done the same itself.  All pointers are device pointers.
 
 // sparse.hip: the phases of one add call
 int sp_add_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y, const int32_t* perm,

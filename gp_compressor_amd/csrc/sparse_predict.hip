@@ -590,8 +590,8 @@ int sp_predict_launch(gpc_sparse* g, int m, const int32_t* off, int n_total, con
 int sp_likelihood_launch(gpc_sparse* g, const int32_t* off, int n_total, const double* x0, const double* x1, const double* y,
                          double* dX, double* l, double* raw)
 {
-    gpc_ctx* ctx = g->ctx;
-    if (ctx->dead.load()) return GPC_EINVAL;   // the context went first: the object can only be destroyed (include/gpc.h)
+    gpc_ctx* ctx = sp_live(g);
+    if (!ctx) return GPC_EINVAL;
     SpLikParams A;
     A.prm = g->prm;
     A.raw = raw;
