@@ -618,6 +618,7 @@ int gpc_patches_normals_dev(const gpc_patches* p, int n, float* normals)
     if (n == 0) return GPC_OK;
     GPC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
     if (n_total > 0) {                                        // a src entry >= n is found out before anything is written
         if (int rc = gpc_ws_reserve(ctx, 256)) return rc;
         int32_t* flag = static_cast<int32_t*>(ctx->ws);

@@ -271,6 +271,7 @@ int gpc_noise_eval(gpc_ctx* ctx, int noise_model, double s20, int n, const doubl
     if (!y || !x || !sigma_x || !q || !r) return gpc_fail(ctx, GPC_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(ctx->mu);
     GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
     const size_t nb = 8 * (size_t)n;
     hipStream_t s = ctx->stream;
     GpcStaging st(ctx, "gpc_noise_eval", s);   // (under ctx->mu: the stream is handed in)

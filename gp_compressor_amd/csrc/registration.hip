@@ -355,6 +355,7 @@ int rg_set_cloud_locked(gpc_registration* r, const gpc_point_xyzrgb* cloud, int 
 {
     gpc_ctx* ctx = r->ctx;
     GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
     hipStream_t st = ctx->stream;
     if (n > r->cap) {
         GPC_HIP(ctx, hipStreamSynchronize(st));

@@ -516,6 +516,7 @@ int gpc_camera_rays_dev(gpc_ctx* ctx, const double R[9], double fx, double fy, d
     if (!dirs_dev) return gpc_fail(ctx, GPC_EINVAL, "dirs_dev is NULL");
     std::lock_guard<std::mutex> lk(ctx->mu);
     GPC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcp = gpc_debug_poison_lds(ctx)) return rcp;
     hipLaunchKernelGGL(rn_camera_kernel, dim3((unsigned)((total + PC_THREADS - 1) / PC_THREADS)), dim3(PC_THREADS), 0, ctx->stream, width,
                        (size_t)total, fx, fy, cx, cy, R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], dirs_dev);
     GPC_HIP(ctx, hipGetLastError());

@@ -207,14 +207,13 @@ static int sp_train_rules(gpc_ctx* ctx, const gpc_sparse* g, SpBatch& b, double 
 
 // ---- what a _dev entry does with the answer of its rules: return it, or enter the critical section -- the context's lock, its device, the
 // LDS poison of diagnostic runs (gpc_debug_poison_lds) -- and call the launcher, which expects exactly that of its caller (sparse_internal.h)
-template <class Launch> static int sp_locked(const gpc_sparse* g, int rules, bool poison, Launch launch)
+template <class Launch> static int sp_locked(const gpc_sparse* g, int rules, Launch launch)
 {
     if (rules != GPC_OK) return sp_done(rules);
     gpc_ctx* ctx = g->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     GPC_HIP(ctx, hipSetDevice(ctx->device));
-    if (poison)
-        if (int rc = gpc_debug_poison_lds(ctx)) return rc;
+    if (int rc = gpc_debug_poison_lds(ctx)) return rc;
     return launch();
 }
 
@@ -298,12 +297,15 @@ int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_
     if (int rc = gpc_sparse_create(ctx, &old->prm, P_new, old->ny, &g)) return rc;      // every patch empty, as after gpc_sparse_reset
     if (P == 0) { *out = g; return GPC_OK; }
     hipError_t e;
+    int rcp = GPC_OK;                                     // the poison call of diagnostic runs: its own code and text
     void* d_map = nullptr;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         hipStream_t st = ctx->stream;
         const size_t n_map = 4 * (size_t)P;
         e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) rcp = gpc_debug_poison_lds(ctx);
+        if (rcp != GPC_OK) e = hipErrorUnknown;
         if (e == hipSuccess) e = hipMalloc(&d_map, n_map);
         if (e == hipSuccess) e = hipMemcpyAsync(d_map, old_to_new, n_map, hipMemcpyHostToDevice, st);
         // the patches no old one moves into: a zero state, not what the allocation happened to hold (gpc_sparse_get_state reads it back)
@@ -322,7 +324,7 @@ int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_
         if (d_map) (void)hipFree(d_map);
     }
     if (e != hipSuccess) {
-        const int rc = gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_remap: %s", hipGetErrorString(e));
+        const int rc = rcp != GPC_OK ? rcp : gpc_fail(ctx, e == hipErrorOutOfMemory ? GPC_ENOMEM : GPC_EHIP, "gpc_sparse_remap: %s", hipGetErrorString(e));
         gpc_sparse_destroy(g);
         return rc;
     }
@@ -413,7 +415,7 @@ int gpc_sparse_add_dev(gpc_sparse* g, const int32_t* off, int n_max, int n_total
                        const double* y, const int32_t* perm, int32_t* status)
 {
     SpBatch b{off, n_max, n_total, x0, x1, y};
-    return sp_locked(g, sp_add_rules(sp_live(g), g, b, perm, false), true, [&] { return sp_add_launch(g, off, n_total, x0, x1, y, perm, status); });
+    return sp_locked(g, sp_add_rules(sp_live(g), g, b, perm, false), [&] { return sp_add_launch(g, off, n_total, x0, x1, y, perm, status); });
 }
 
 int gpc_sparse_add(gpc_sparse* g, const int32_t* off, const double* x0, const double* x1, const double* y,
@@ -436,7 +438,7 @@ int gpc_sparse_add(gpc_sparse* g, const int32_t* off, const double* x0, const do
 int gpc_sparse_prune_dev(gpc_sparse* g, int keep, const int32_t* target, double score_tol, int32_t* removed, int32_t* order,
                          double* scores, int32_t* status)
 {
-    return sp_locked(g, sp_prune_rules(sp_live(g), g, keep, target, score_tol), true,
+    return sp_locked(g, sp_prune_rules(sp_live(g), g, keep, target, score_tol),
                      [&] { return sp_prune_launch(g, keep, target, score_tol, removed, order, scores, status); });
 }
 
@@ -466,7 +468,7 @@ int gpc_sparse_prune_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, cons
                             double* scores, double* mse, double* mse0, double* mse_next, int32_t* status)
 {
     SpBatch b{off, 0, n_total, x0, x1, y};
-    return sp_locked(g, sp_prune_rd_rules(sp_live(g), g, b, keep, target, max_mse, max_mse_p, false), true, [&] {
+    return sp_locked(g, sp_prune_rd_rules(sp_live(g), g, b, keep, target, max_mse, max_mse_p, false), [&] {
         return sp_prune_rd_launch(g, off, n_total, x0, x1, y, keep, target, max_mse, max_mse_p, removed, order, scores, mse, mse0, mse_next, status);
     });
 }
@@ -510,7 +512,7 @@ int gpc_sparse_quantize_rd_dev(gpc_sparse* g, const int32_t* off, int n_total, c
                                uint16_t* q_bv, float* range, double* mse0, double* mse_q, double* curve, int32_t* status)
 {
     SpBatch b{off, 0, n_total, x0, x1, y};
-    return sp_locked(g, sp_quantize_rd_rules(sp_live(g), g, b, bits_min, bits_max, max_mse, max_mse_p, false), true, [&] {
+    return sp_locked(g, sp_quantize_rd_rules(sp_live(g), g, b, bits_min, bits_max, max_mse, max_mse_p, false), [&] {
         return sp_quantize_rd_launch(g, off, n_total, x0, x1, y, bits_min, bits_max, max_mse, max_mse_p, bits, q_alpha, q_bv, range, mse0, mse_q,
                                      curve, status);
     });
@@ -556,8 +558,7 @@ int gpc_sparse_quantize_rd(gpc_sparse* g, const int32_t* off, const double* x0, 
 int gpc_sparse_dequantize_dev(gpc_sparse* g, const int32_t* bv_count, const int32_t* bits, const uint16_t* q_alpha, const uint16_t* q_bv,
                               const float* range)
 {
-    // (no poison call: the kernel uses no LDS)
-    return sp_locked(g, sp_dequantize_rules(sp_live(g), g, bv_count, bits, q_alpha, q_bv, range, false), false,
+    return sp_locked(g, sp_dequantize_rules(sp_live(g), g, bv_count, bits, q_alpha, q_bv, range, false),
                      [&] { return sp_dequantize_launch(g, bv_count, bits, q_alpha, q_bv, range); });
 }
 
@@ -579,7 +580,7 @@ int gpc_sparse_predict_dev(gpc_sparse* g, int m, const double* xs0, const double
                            int conf, int32_t* status)
 {
     // (mean only: a patch is a few hundred kernel evaluations, more resident blocks hide their latency)
-    return sp_locked(g, sp_predict_rules(sp_live(g), g, m, xs0, xs1, f_star), true,
+    return sp_locked(g, sp_predict_rules(sp_live(g), g, m, xs0, xs1, f_star),
                      [&] { return sp_predict_launch(g, m, nullptr, 0, xs0, xs1, f_star, sigma, conf, status, sigma ? 4 : 8); });
 }
 
@@ -606,7 +607,7 @@ int gpc_sparse_predict_points_dev(gpc_sparse* g, const int32_t* off, int n_total
                                   double* f, double* sigma, int conf, int32_t* status)
 {
     SpBatch b{off, 0, n_total, x0, x1, f};
-    return sp_locked(g, sp_predict_points_rules(sp_live(g), g, b, false), true,
+    return sp_locked(g, sp_predict_points_rules(sp_live(g), g, b, false),
                      [&] { return sp_predict_launch(g, 0, off, n_total, x0, x1, f, sigma, conf, status, 4); });
 }
 
@@ -633,7 +634,7 @@ int gpc_sparse_predict_points(gpc_sparse* g, const int32_t* off, const double* x
 int gpc_sparse_predict_scattered_dev(gpc_sparse* g, int n, const int32_t* patch, const double* x0, const double* x1, int stride,
                                      double* f, double* sigma, int conf, int32_t* status)
 {
-    return sp_locked(g, sp_scattered_rules(sp_live(g), g, n, patch, x0, x1, stride, status), true,
+    return sp_locked(g, sp_scattered_rules(sp_live(g), g, n, patch, x0, x1, stride, status),
                      [&] { return sp_scatter_launch(g, n, patch, x0, x1, stride, f, sigma, conf, status); });
 }
 
@@ -670,7 +671,7 @@ int gpc_sparse_likelihood_dev(gpc_sparse* g, const int32_t* off, int n_total, co
                               const double* y, double* dX, double* l)
 {
     SpBatch b{off, 0, n_total, x0, x1, y};
-    return sp_locked(g, sp_likelihood_rules(sp_live(g), g, b, dX, l, false), true,
+    return sp_locked(g, sp_likelihood_rules(sp_live(g), g, b, dX, l, false),
                      [&] { return sp_likelihood_launch(g, off, n_total, x0, x1, y, dX, l, nullptr); });
 }
 
@@ -695,7 +696,7 @@ int gpc_sparse_train_sigmaf_dev(gpc_sparse* g, const int32_t* off, int n_total, 
                                 double step, int max_counter, double* p0, int32_t* iters, double* ls, double* delta)
 {
     SpBatch b{off, 0, n_total, x0, x1, y};
-    return sp_locked(g, sp_train_rules(sp_live(g), g, b, step, max_counter, p0, iters, ls, delta, false), true, [&] {
+    return sp_locked(g, sp_train_rules(sp_live(g), g, b, step, max_counter, p0, iters, ls, delta, false), [&] {
         gpc_ctx* ctx = g->ctx;
         int rc = gpc_ws_reserve(ctx, sizeof(double) * 3 * (size_t)(n_total > 0 ? n_total : 1));
         if (rc != GPC_OK) return rc;
