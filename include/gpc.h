@@ -92,7 +92,10 @@ int gpc_version(void);
 typedef struct gpc_ctx gpc_ctx;
 int gpc_ctx_create(gpc_ctx** out, int device);
 /* hip_stream: a hipStream_t passed as void*, used as is (NULL is HIP's default stream); GPC_STREAM_OWN selects the
- * non-blocking stream the context created for itself (the initial setting).  Not owned. */
+ * non-blocking stream the context created for itself (the initial setting).  Not owned.
+ * The call only swaps the handle: work enqueued on the new stream is NOT ordered behind work still in flight on the old one, and both
+ * use the context's workspace and events.  (The library cannot record an event on the old stream: it does not own that stream, and the
+ * caller may have destroyed it.)  While work of this context is in flight, call gpc_ctx_synchronize before switching. */
 #define GPC_STREAM_OWN ((void*)(intptr_t)-1)
 int gpc_ctx_set_stream(gpc_ctx* ctx, void* hip_stream);
 int gpc_ctx_synchronize(gpc_ctx* ctx);
@@ -465,7 +468,7 @@ int gpc_sparse_set_state(gpc_sparse* g, const int32_t* bv_count, const double* a
 /* The map grew (gpc_patches_insert_cloud): a NEW object of P_new patches with old's parameters, ny and leading dimension, in which
  * patch old_to_new[i] holds the state of old's patch i -- alpha, C, Q, BV, basis count and the per-patch counters, copied exactly
  * on the device -- and every other patch is empty, as after gpc_sparse_reset, its state zero.  old_to_new: host, old's P entries, strictly
- * increasing, < P_new (else GPC_EINVAL).  old is untouched; the two objects are destroyed independently. */
+ * increasing, < P_new (else GPC_EINVAL).  old is untouched; the two objects are destroyed independently.  Synchronises the stream. */
 int gpc_sparse_remap(gpc_sparse* old, int P_new, const int32_t* old_to_new, gpc_sparse** out);
 /* Rate control: prune every patch's basis IN PLACE by continuing the reference's capacity deletion (src/sparse_gp.hpp:206-223 with
  * delete_bv :252-295; field variant src/sparse_gp_field.hpp:219-263) as a step of its own.  Per patch, with b its basis count and
@@ -723,7 +726,8 @@ void gpc_patches_destroy(gpc_patches* p);
  * Deviations: upstream lets to_be_added of a leaf below min_nbr pile up across scans and pairs it with a mis-indexed last_inds
  * (:261); here the threshold looks at the current scan only -- the reference's behaviour for a leaf's first scan.
  * train_classification (the ray-cast free mask, :154-211) is its own entry: gpc_patches_raycast below.
- * The same inputs give the same bits.  Follow with gpc_sparse_remap on both GPs and gpc_sparse_add_dev on the new batch. */
+ * The same inputs give the same bits.  Follow with gpc_sparse_remap on both GPs and gpc_sparse_add_dev on the new batch.
+ * Both forms synchronise the context's stream, like the cutters: the sizes of the new batch and old_to_new go to the host. */
 int gpc_patches_insert_cloud(gpc_ctx* ctx, const gpc_patches* model, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud, int n,
                              int min_nbr, gpc_patches** out, int32_t* old_to_new);
 int gpc_patches_insert_cloud_dev(gpc_ctx* ctx, const gpc_patches* model, const gpc_sparse* depth, const gpc_point_xyzrgb* cloud,
@@ -995,11 +999,13 @@ void gpc_registration_destroy(gpc_registration* r);
 int gpc_registration_set_cloud(gpc_registration* r, const gpc_point_xyzrgb* cloud, int n);
 int gpc_registration_set_cloud_dev(gpc_registration* r, const gpc_point_xyzrgb* cloud, int n);
 /* one registration_step (:73-92).  out (host): delta[6] (translation, rotation), ls, cls (get_likelihood, get_color_likelihood
- * :248-256), n_used (points that found a leaf).  No point used: all zero.  The same state gives the same bits. */
+ * :248-256), n_used (points that found a leaf).  No point used: all zero.  The same state gives the same bits.
+ * The call synchronises the context's stream: `out` is read back before it returns. */
 int gpc_registration_step(gpc_registration* r, const gpc_registration_params* params, double out[9]);
 /* steps until registration_done() (:67-70): after a step has raised the step count to s, stop when s > min_steps and either
  * s >= max_steps or both |delta[0:3]| < tol and |delta[3:6]| < tol.  trace (host, [max_steps][9], may be NULL): row k = the out
- * of the k-th step of this call (rows beyond max_steps, possible when min_steps >= max_steps, are not written); steps: how many. */
+ * of the k-th step of this call (rows beyond max_steps, possible when min_steps >= max_steps, are not written); steps: how many.
+ * Synchronises the context's stream once per step, as gpc_registration_step does. */
 int gpc_registration_run(gpc_registration* r, const gpc_registration_params* params, double* trace, int32_t* steps);
 /* get_cloud_transformation (:18-22): the accumulated R_cloud [9] column-major and t_cloud [3] (host) */
 int gpc_registration_get_transform(gpc_registration* r, double R[9], double t[3]);

@@ -6,25 +6,9 @@ import os
 import re
 
 import poison_cases as PC
+from gpc_header import OBJECT_CALLS, ROOT, declared as _declared, launching as _launching      # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.join(ROOT, "tests")
-OBJECT_CALLS = {"gpc_sparse_remap", "gpc_registration_step", "gpc_registration_run"}
-
-
-def _declared():
-    """as test_capi_cpu.py::test_library_exports_every_declared_symbol reads the header"""
-    hdr = open(os.path.join(ROOT, "include", "gpc.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(gpc_[a-z0-9_]+)\s*\(", hdr))
-    assert len(declared) > 80, "no declarations parsed"
-    return declared
-
-
-def _launching(declared):
-    dev = {s for s in declared if s.endswith("_dev")}
-    assert OBJECT_CALLS <= declared and len(dev) > 30
-    return dev | OBJECT_CALLS
 
 
 def _uncovered(declared, cased, covered, exempt):
